@@ -19,13 +19,21 @@ the requested values (default 0.7 / 0.9), so the loop runs in the regime specula
 random-init number of round 1 (acceptance ~0.01: the loop's worst case) is measured in the same process afterwards and
 reported as ``random_weights``.
 
-value = tokens emitted in the K timed steps / wall time (tokens/s, whole job).
+value = tokens emitted in the K timed steps / wall time (tokens/s, whole job); ms_per_step = wall time / K.
 roofline = the dominant kernel (split-KV target-verify attention, tf_attn_decode): algorithmic bytes per launch
 2*S*H*D*2 / mean launch duration from HIP events recorded on the launch stream INSIDE the timed region:
 every --roofline-every-th step runs its target verify eagerly instead of replaying the hipGraph, and every 8th
 attention launch of such a verify is bracketed (an event record is a queue packet of its own).
+
+A plain run (N=1) sets up, prefills, warms up, times the K steps and prints the line.  --full adds every measurement
+that takes runs of its own after the timed steps: stage latencies and stage rooflines, the autoregressive baseline and
+the speedup over it, the committed acceptance-sweep points, the random-weight run (random_weights), and
 cpu_baseline = the CPU oracle (oracle/, kind "port") timed on this host for a bounded per-layer sample of the same
 step, extrapolated to the step.
+
+--dump-outputs DIR (N=1) writes what the last timed step computed: tokens.npy (the tokens it emitted, float64) and
+verify_probs.npy (its target verify's probabilities after temperature / top-p, rows x vocab, float32).  Inputs, weights
+and the uniform stream are seeded, so the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -60,9 +68,14 @@ def parse(argv=None):
                     help="auto = local checkpoints if present, else aligned:0.7:0.9 | aligned[:draft_acc[:retrieval_acc"
                          "[:seed]]] | random[:seed] | <local HF dir of the target> (draft: --draft-weights)")
     ap.add_argument("--draft-weights", default=None, help="local HF dir of the 68M draft (with a checkpoint target)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure stage latencies / rooflines, the AR baseline, the random-weight "
+                         "run and the CPU baseline (single-GPU engine; a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (single-GPU engine)")
     ap.add_argument("--random-steps", type=int, default=-1,
-                    help="steps of the secondary random-init measurement (-1 = min(steps, 12); 0 = skip)")
-    ap.add_argument("--ar-steps", type=int, default=16, help="autoregressive steps timed for the AR baseline")
+                    help="steps of the secondary random-init measurement with --full (-1 = min(steps, 12); 0 = skip)")
+    ap.add_argument("--ar-steps", type=int, default=16, help="autoregressive steps timed for the AR baseline (--full)")
     ap.add_argument("--roofline-every", type=int, default=4,
                     help="every N-th step's target verify runs eagerly with HIP-event brackets (0 = never)")
     ap.add_argument("--prefill-mode", default="real", choices=["real", "synthetic"],
@@ -91,16 +104,22 @@ def parse(argv=None):
                     help="tensor-parallel path: fail (rc != 0, JSON field 'failed') unless the decode forwards were "
                          "captured in this form")
     ap.add_argument("--eager-comparator", action="store_true",
-                    help="also time the same-hardware un-tuned comparator (eager PyTorch-ROCm restatement, ~20 s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="also time the same-hardware un-tuned comparator (eager PyTorch-ROCm restatement, ~20 s; implies "
+                         "--full: it is priced against the full line's AR baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--rebuild-every", type=int, default=0,
                     help="re-select the retrieval cache every N target verifies (0 = the reference: once per prompt)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.eager_comparator:
+        args.full = True
     if args.random_steps < 0:
         args.random_steps = min(args.steps, 12)
     # a step emits at most gamma + 2 tokens: size the KV slack for the worst case of the requested run
-    # (never more than the retrieval budget: its tail holds every generated token, reference cache.py:180-182)
+    # (never more than the retrieval budget: its tail holds every generated token, reference cache.py:180-182); the --full
+    # measurements are counted with or without --full, so the same arguments always allocate the same caches
     total = args.steps + args.warmup + args.random_steps + 8
     args.gen_cap = max(args.gen_cap, min(total * (args.gamma + 2) + args.ar_steps + 64, args.budget))
     return args
@@ -590,8 +609,9 @@ def timed_steps(run, steps, eager_every=0, sample_attn=False):
     torch.cuda.synchronize()
     t1 = time.time()
     stamps = [t1]
+    last = 0
     for _ in range(steps):
-        run.step()
+        last = run.step()
         stamps.append(time.time())       # (host clock behind the step's record read: no extra device sync)
     torch.cuda.synchronize()
     t2 = time.time()
@@ -604,7 +624,52 @@ def timed_steps(run, steps, eager_every=0, sample_attn=False):
     inner = run.inner_iters - in0
     return dict(seconds=t2 - t1, tokens=run.n - n0, accepted=accepted, drafted=drafted, inner=inner, timer=timer, stamps=stamps,
                 per_token_acceptance=accepted / max(tests, 1),
-                middle_acceptance=sum(mids) / max(len(mids), 1))
+                middle_acceptance=sum(mids) / max(len(mids), 1),
+                last_tokens=run.emitted[len(run.emitted) - last:])      # what the last step emitted (step() returns the count)
+
+
+class VerifyCapture:
+    """--dump-outputs: keeps a reference to the probabilities of the latest target verify, whichever of its three forms
+    TriForceRunner.step issues (in-place hipGraph replay, ids-as-arguments replay, verify_probs).  Instance attributes
+    shadow the engine's methods until remove(); nothing is copied or synchronised inside them."""
+
+    def __init__(self, ge):
+        self.probs, self.patched = None, []
+        self._wrap(ge, "verify_probs", lambda out: out)
+        self._wrap(ge, "verify_probs_ids", lambda out: out[0])
+        for tg in ge.target_graphs.values():
+            self._wrap(tg, "replay_in_place", lambda out: out)
+
+    def _wrap(self, obj, name, pick):
+        fn = getattr(obj, name, None)
+        if fn is None:
+            return
+
+        def wrapped(*a, **k):
+            out = fn(*a, **k)
+            if out is not None:
+                self.probs = pick(out)
+            return out
+        setattr(obj, name, wrapped)
+        self.patched.append((obj, name))
+
+    def remove(self):
+        for obj, name in self.patched:
+            delattr(obj, name)
+        self.patched = []
+
+
+def write_outputs(out_dir, tokens, probs):
+    """DIR/tokens.npy (float64) and DIR/verify_probs.npy (float32, rows x vocab): about 1 MB for the 7B workload."""
+    import numpy as np
+    if probs is None:
+        raise RuntimeError("--dump-outputs: no target verify was seen in the timed steps")
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"tokens": np.asarray(tokens, dtype=np.float64),
+              "verify_probs": probs.detach().float().reshape(-1, probs.shape[-1]).cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def self_launch(args):
@@ -622,58 +687,18 @@ def self_launch(args):
     return subprocess.call(cmd, env=env)
 
 
-def main():
-    args = parse()
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(self_launch(args))
-    rank = int(os.environ.get("RANK", 0))
-    world = int(os.environ.get("WORLD_SIZE", 1))
-    local = int(os.environ.get("LOCAL_RANK", 0))
-    if world != args.gpus:
-        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with --nproc-per-node {args.gpus}")
-    if world > 1 or args.engine == "tp" or args.on_chip >= 0 or os.environ.get("TRIFORCE_BENCH_FORCE_TP") == "1":
-        from bench_tp import run_tp                  # tensor-parallel decode (heads sharded, RCCL all-reduce)
-        return run_tp(args, rank, world, local)
-    torch.cuda.set_device(local)
-    device = torch.device("cuda", local)
-
-    from triforce_amd.utils.decoding import TriForceRunner
-    from triforce_amd.utils.sampling import UniformSource
-
-    t_setup = time.time()
-    kind, tspec, dspec, wlabel = resolve_weights(args)
-    target, draft = load_models(args, device, kind, tspec, dspec)
-    ge = build_engine(args, device, target, draft)
-    tcfg, _ = target_config(args.target)
-    gen = torch.Generator().manual_seed(args.seed)
-    input_ids = torch.randint(3, tcfg.vocab_size, (1, args.prefill), generator=gen).to(device)
-
-    def new_runner(seed):
-        return TriForceRunner(_Tok(), ge, args.gamma, top_k=-1, top_p=args.top_p, temperature=args.temp,
-                              rng=UniformSource(device, seed=seed), rebuild_every=args.rebuild_every)
-
-    run = new_runner(args.seed)
-    torch.cuda.synchronize()
-    t0 = time.time()
-    do_prefill(run, ge, input_ids, args.prefill_mode)
-    torch.cuda.synchronize()
-    t_prefill = time.time() - t0
-
-    for _ in range(args.warmup):
-        run.step()
-    # graphs: every --roofline-every-th verify is eager and sampled; --no-graphs: every verify is eager already
-    m = timed_steps(run, args.steps, 0 if args.no_graphs else args.roofline_every,
-                    sample_attn=args.no_graphs or args.roofline_every > 0)
+def full_measurements(result, args, ge, run, m, label, target, draft, kind, input_ids, new_runner, device):
+    """--full: everything beyond the headline, measured after the timed steps in this order (each one in runs of its
+    own): stage latencies + stage rooflines, the autoregressive baseline, the committed acceptance-sweep points, the
+    step overhead, the eager comparator (--eager-comparator), the random-weight run and the CPU baseline."""
+    tcfg, dcfg = target_config(args.target)
     seconds, tokens = m["seconds"], m["tokens"]
     value = tokens / seconds
-    roof = attn_roofline(m["timer"], args.budget + args.gamma + 1, tcfg.num_attention_heads, tcfg.head_dim)
-
+    inner_per_step = m["inner"] / max(args.steps, 1)
     stages = stage_latencies(ge, args, device)
-    label = baseline_config_label(args.target, args.prefill, args.budget, args.gamma, -1, tcfg.num_hidden_layers, 1)
     S_now = ge.engine.kv_cache.seq_len
     rv_bytes, w_layer, rv_kv = forward_bytes(tcfg, args.budget + args.gamma + 1)
     tv_bytes, _, tv_kv = forward_bytes(tcfg, S_now + args.gamma + 2)
-    dcfg = target_config(args.target)[1]
     d_bytes = (dcfg.num_hidden_layers * (4 * dcfg.hidden_size ** 2 + 3 * dcfg.intermediate_size * dcfg.hidden_size)
                + dcfg.vocab_size * dcfg.hidden_size) * 2
     how = "HIP events around hipGraph replays on the launch stream (stage_latency_us)"
@@ -691,60 +716,18 @@ def main():
     except Exception as ex:                                        # a probe must never cost the bench line
         roofline_stages.append({"stage": "retrieval build", "failed": f"{type(ex).__name__}: {ex}"[:300]})
     ar_tps = autoregressive_baseline(ge, args, run.next_token)
-    inner_per_step = m["inner"] / max(args.steps, 1)
-    cal = (target.weights.aligned or {}).get("calibration") if kind == "aligned" else None
-    result = {
-        "metric": metric_label(args.target, args.prefill),
-        "value": round(value, 3), "unit": "tokens/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(seconds / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None, "dtype": "f16", "data": "synthetic",
-        "config": {"workload": f"{label}: {tcfg._name_or_path} on-chip TriForce decode, prefill "
-                               f"{args.prefill}, budget {args.budget}, chunk {args.chunk_size}, gamma {args.gamma}, "
-                               f"T={args.temp}, top_p={args.top_p}, 1xMI355X",
-                   "prefill_mode": args.prefill_mode, "weights": wlabel, "weights_kind": kind,
-                   "hipgraphs": not args.no_graphs, "target_verify_graph": bool(ge.target_graphs),
-                   "retrieval_rebuild_every": args.rebuild_every},
-        "avg_accepted_len": round(m["accepted"] / max(m["drafted"], 1) * args.gamma, 4),
-        "acceptance_rate": round(m["accepted"] / max(m["drafted"], 1), 4),
-        "per_token_acceptance_target": round(m["per_token_acceptance"], 4),
-        "per_token_acceptance_middle": round(m["middle_acceptance"], 4),
-        "tokens": tokens, "tokens_per_step": round(tokens / args.steps, 3),
-        "drafted_per_step": round(m["drafted"] / max(args.steps, 1), 3),
-        "inner_iterations_per_step": round(inner_per_step, 3),
+    result.update({
         "stage_latency_us": stages,
         "ar_baseline_tokens_per_s": round(ar_tps, 2),
         "speedup_vs_autoregressive": round(value / ar_tps, 3),
         "reference_speedup_vs_autoregressive": {"value": REFERENCE_SPEEDUP, "hardware": "1x A100, trained weights",
                                                 "source": "reference README.md:49-55"},
-        "prefill_seconds": round(t_prefill, 2), "setup_seconds": round(t0 - t_setup, 2),
-        "kv_seq_len": ge.engine.kv_cache.seq_len,
-        "roofline": roof, "roofline_stages": roofline_stages,
-    }
-    bs = block_stats(m["stamps"])
-    if bs is not None:
-        result["ms_per_step_blocks"] = bs
+        "roofline_stages": roofline_stages,
+    })
     if kind == "aligned":
         op = operating_points(label)
         if op is not None:
             result["operating_points"] = op
-    dp = getattr(draft, "_persist", None)
-    result["draft_forward"] = {
-        "form": "one launch: tf_draft_forward_68m_persist, 256 co-resident workgroups, arrival counters + READY flags"
-                if dp is not None else "13-launch chain: tf_draft_forward_68m",
-        "error_word": dp.error() if dp is not None else None,
-        "draft_step_us_is": "the hipGraph replay the loop issues (shared token buffer); draft_step_with_io_us adds the input "
-                            "copy and the output clone of graph_draft_inference (what rounds 1-5 quoted as draft_step_us)"}
-    if kind == "aligned":
-        # the headline is CONDITIONAL on a dial: say so next to it (trained checkpoints are not available offline)
-        result["value_note"] = (f"configured-acceptance scenario: synthetic weights {wlabel} SET the draft->retrieval and "
-                                "retrieval->target acceptance rates (models/aligned.py); tokens/s and avg_accepted_len follow "
-                                "from that dial — stage_latency_us, roofline* and random_weights do not depend on it; other "
-                                "operating points: `operating_points` (newest profiles/*acceptance_sweep*.json); not comparable to the reference's "
-                                "trained-weights 2.2x")
-    elif kind == "random":
-        result["value_note"] = "random-init weights: acceptance ~0, the loop's worst case (gamma inner iterations per token)"
-    if cal is not None:
-        result["aligned_calibration"] = cal
     # what a step costs beyond its model calls (accept kernels, cache fix-ups, host round trips); the eager verifies
     # sampled for the roofline are priced at their own latency
     n_eager = (args.steps // args.roofline_every) if (args.roofline_every > 0 and not args.no_graphs) else 0
@@ -783,6 +766,109 @@ def main():
         except Exception as ex:                                    # host too small for the sample: report, don't fake
             result["cpu_baseline"] = {"value": None, "unit": "tokens/s", "cores": torch.get_num_threads(),
                                       "kind": "port", "sample": f"failed: {type(ex).__name__}: {ex}"}
+
+
+def main():
+    args = parse()
+    if args.dump_outputs and (args.gpus > 1 or args.engine == "tp" or args.on_chip >= 0
+                              or os.environ.get("TRIFORCE_BENCH_FORCE_TP") == "1"):
+        raise SystemExit("--dump-outputs: single-GPU engine only (--gpus 1, no --engine tp / --on-chip)")
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        sys.exit(self_launch(args))
+    rank = int(os.environ.get("RANK", 0))
+    world = int(os.environ.get("WORLD_SIZE", 1))
+    local = int(os.environ.get("LOCAL_RANK", 0))
+    if world != args.gpus:
+        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with --nproc-per-node {args.gpus}")
+    if world > 1 or args.engine == "tp" or args.on_chip >= 0 or os.environ.get("TRIFORCE_BENCH_FORCE_TP") == "1":
+        from bench_tp import run_tp                  # tensor-parallel decode (heads sharded, RCCL all-reduce)
+        return run_tp(args, rank, world, local)
+    torch.cuda.set_device(local)
+    device = torch.device("cuda", local)
+
+    from triforce_amd.utils.decoding import TriForceRunner
+    from triforce_amd.utils.sampling import UniformSource
+
+    t_setup = time.time()
+    kind, tspec, dspec, wlabel = resolve_weights(args)
+    target, draft = load_models(args, device, kind, tspec, dspec)
+    ge = build_engine(args, device, target, draft)
+    tcfg, _ = target_config(args.target)
+    gen = torch.Generator().manual_seed(args.seed)
+    input_ids = torch.randint(3, tcfg.vocab_size, (1, args.prefill), generator=gen).to(device)
+
+    def new_runner(seed):
+        return TriForceRunner(_Tok(), ge, args.gamma, top_k=-1, top_p=args.top_p, temperature=args.temp,
+                              rng=UniformSource(device, seed=seed), rebuild_every=args.rebuild_every)
+
+    run = new_runner(args.seed)
+    torch.cuda.synchronize()
+    t0 = time.time()
+    do_prefill(run, ge, input_ids, args.prefill_mode)
+    torch.cuda.synchronize()
+    t_prefill = time.time() - t0
+
+    for _ in range(args.warmup):
+        run.step()
+    capture = VerifyCapture(ge) if args.dump_outputs else None
+    # graphs: every --roofline-every-th verify is eager and sampled; --no-graphs: every verify is eager already
+    m = timed_steps(run, args.steps, 0 if args.no_graphs else args.roofline_every,
+                    sample_attn=args.no_graphs or args.roofline_every > 0)
+    if capture is not None:
+        capture.remove()
+        write_outputs(args.dump_outputs, m["last_tokens"], capture.probs)
+    seconds, tokens = m["seconds"], m["tokens"]
+    value = tokens / seconds
+    roof = attn_roofline(m["timer"], args.budget + args.gamma + 1, tcfg.num_attention_heads, tcfg.head_dim)
+
+    label = baseline_config_label(args.target, args.prefill, args.budget, args.gamma, -1, tcfg.num_hidden_layers, 1)
+    inner_per_step = m["inner"] / max(args.steps, 1)
+    cal = (target.weights.aligned or {}).get("calibration") if kind == "aligned" else None
+    result = {
+        "metric": metric_label(args.target, args.prefill),
+        "value": round(value, 3), "unit": "tokens/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(seconds / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": "f16", "data": "synthetic",
+        "config": {"workload": f"{label}: {tcfg._name_or_path} on-chip TriForce decode, prefill "
+                               f"{args.prefill}, budget {args.budget}, chunk {args.chunk_size}, gamma {args.gamma}, "
+                               f"T={args.temp}, top_p={args.top_p}, 1xMI355X",
+                   "prefill_mode": args.prefill_mode, "weights": wlabel, "weights_kind": kind,
+                   "hipgraphs": not args.no_graphs, "target_verify_graph": bool(ge.target_graphs),
+                   "retrieval_rebuild_every": args.rebuild_every},
+        "avg_accepted_len": round(m["accepted"] / max(m["drafted"], 1) * args.gamma, 4),
+        "acceptance_rate": round(m["accepted"] / max(m["drafted"], 1), 4),
+        "per_token_acceptance_target": round(m["per_token_acceptance"], 4),
+        "per_token_acceptance_middle": round(m["middle_acceptance"], 4),
+        "tokens": tokens, "tokens_per_step": round(tokens / args.steps, 3),
+        "drafted_per_step": round(m["drafted"] / max(args.steps, 1), 3),
+        "inner_iterations_per_step": round(inner_per_step, 3),
+        "prefill_seconds": round(t_prefill, 2), "setup_seconds": round(t0 - t_setup, 2),
+        "kv_seq_len": ge.engine.kv_cache.seq_len,
+        "roofline": roof, "full": args.full,
+    }
+    bs = block_stats(m["stamps"])
+    if bs is not None:
+        result["ms_per_step_blocks"] = bs
+    dp = getattr(draft, "_persist", None)
+    result["draft_forward"] = {
+        "form": "one launch: tf_draft_forward_68m_persist, 256 co-resident workgroups, arrival counters + READY flags"
+                if dp is not None else "13-launch chain: tf_draft_forward_68m",
+        "error_word": dp.error() if dp is not None else None,
+        "draft_step_us_is": "the hipGraph replay the loop issues (shared token buffer); draft_step_with_io_us adds the input "
+                            "copy and the output clone of graph_draft_inference (what rounds 1-5 quoted as draft_step_us)"}
+    if kind == "aligned":
+        # the headline is CONDITIONAL on a dial: say so next to it (trained checkpoints are not available offline)
+        result["value_note"] = (f"configured-acceptance scenario: synthetic weights {wlabel} SET the draft->retrieval and "
+                                "retrieval->target acceptance rates (models/aligned.py); tokens/s and avg_accepted_len follow "
+                                "from that dial — stage_latency_us, roofline* and random_weights do not depend on it; other "
+                                "operating points: `operating_points` with --full (newest profiles/*acceptance_sweep*.json); "
+                                "not comparable to the reference's trained-weights 2.2x")
+    elif kind == "random":
+        result["value_note"] = "random-init weights: acceptance ~0, the loop's worst case (gamma inner iterations per token)"
+    if cal is not None:
+        result["aligned_calibration"] = cal
+    if args.full:
+        full_measurements(result, args, ge, run, m, label, target, draft, kind, input_ids, new_runner, device)
     print(json.dumps(result), flush=True)
 
 

@@ -679,3 +679,47 @@ def test_draft_prefill_graph_equals_eager(monkeypatch):
     assert getattr(eng, "_dpf_graph", None) is not None and eng._dpf_graph[1] is not None, "the steady step was not captured"
     for (la, ka, va, sa), (lb, kb, vb, sb) in zip(results["0"], results["1"]):
         assert sa == sb and torch.equal(la, lb) and torch.equal(ka, kb) and torch.equal(va, vb)
+
+
+def _bench_line(*extra, timeout=600):
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--target", "tiny", "--prefill", "2048", "--budget",
+           "256", "--gamma", "4", "--steps", "4", "--warmup", "1", "--weights", "random:3", *extra]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=root)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [json.loads(ln) for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    return lines[0]
+
+
+def test_bench_plain_line_dumps_the_last_step_and_full_line_adds_the_extras(tmp_path):
+    """bench.py on the tiny target: a plain run times exactly --steps steps and carries the headline fields only; with
+    --dump-outputs it writes the last timed step's tokens (float64) and its target verify's probabilities (float32, one
+    row per verified token), the same in two runs with the same arguments; --full adds the measurements of their own."""
+    import numpy as np
+    from triforce_amd.models import zoo
+    gamma, vocab = 4, zoo.config("tiny").vocab_size
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"dump{k}"
+        j = _bench_line("--dump-outputs", str(out))
+        assert j["steps"] == 4 and j["warmup"] == 1 and j["n_gpus"] == 1 and not j["full"]
+        assert j["unit"] == "tokens/s" and j["higher_is_better"] is True and j["dtype"] == "f16"
+        assert j["value"] > 0 and j["ms_per_step"] > 0 and j["tokens"] >= 4
+        assert abs(j["value"] - j["tokens"] / (4 * j["ms_per_step"] * 1e-3)) < 0.01 * j["value"]
+        for key in ("stage_latency_us", "roofline_stages", "ar_baseline_tokens_per_s", "random_weights", "cpu_baseline"):
+            assert key not in j, key
+        tok, probs = np.load(out / "tokens.npy"), np.load(out / "verify_probs.npy")
+        assert tok.dtype == np.float64 and tok.ndim == 1 and 1 <= tok.size <= gamma + 2
+        assert np.all(tok == np.round(tok)) and np.all((tok >= 0) & (tok < vocab))
+        assert probs.dtype == np.float32 and probs.shape[0] in (gamma + 1, gamma + 2) and probs.shape[1] == vocab
+        assert np.all(probs >= 0) and np.allclose(probs.sum(axis=1), 1.0, atol=1e-3)
+        runs.append((tok, probs))
+    assert np.array_equal(runs[0][0], runs[1][0]) and np.array_equal(runs[0][1], runs[1][1])
+    j = _bench_line("--full", "--no-cpu-baseline", timeout=900)
+    assert j["full"] and j["steps"] == 4
+    assert j["stage_latency_us"]["target_verify_us"] > 0 and j["ar_baseline_tokens_per_s"] > 0 and j["roofline_stages"]

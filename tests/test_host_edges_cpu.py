@@ -265,6 +265,68 @@ def test_bench_helpers_on_cpu():
     assert kind == "aligned" and tspec == "aligned:0.5:0.95:7"
 
 
+def test_bench_full_and_dump_outputs_options(tmp_path):
+    """A plain bench run times the steps only; --full adds the measurements of their own (--eager-comparator implies it);
+    --steps must be at least 1.  --dump-outputs: VerifyCapture keeps the latest target verify's probabilities whichever
+    form issued it, remove() restores the engine's own methods, and write_outputs stores float64 tokens and float32
+    probabilities."""
+    import numpy as np
+    import bench
+    a = bench.parse(["--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert bench.parse(["--full"]).full and bench.parse(["--eager-comparator"]).full
+    assert bench.parse(["--dump-outputs", str(tmp_path)]).dump_outputs == str(tmp_path)
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+    class Graph:
+        def __init__(self, probs):
+            self.out_probs = probs
+
+        def replay_in_place(self):
+            return self.out_probs
+
+    class Engine:
+        def __init__(self):
+            self.target_graphs = {5: Graph(torch.full((5, 8), 0.125)), 6: Graph(torch.full((6, 8), 0.125))}
+
+        def verify_probs(self, ids, temperature, top_p, rebuild_retrieval=False, eager=False):
+            return torch.full((ids.shape[-1], 8), 0.25)
+
+        def verify_probs_ids(self, ids, temperature, top_p):
+            return torch.full((len(ids), 8), 0.5), None
+
+    ge = Engine()
+    cap = bench.VerifyCapture(ge)
+    assert cap.probs is None
+    ge.verify_probs(torch.zeros(1, 3), 0.6, 0.9, eager=True)
+    assert cap.probs.shape == (3, 8) and float(cap.probs[0, 0]) == 0.25
+    ge.verify_probs_ids([1, 2, 3, 4], 0.6, 0.9)
+    assert cap.probs.shape == (4, 8) and float(cap.probs[0, 0]) == 0.5
+    ge.target_graphs[6].replay_in_place()
+    assert cap.probs is ge.target_graphs[6].out_probs
+    cap.remove()
+    assert "verify_probs" not in vars(ge) and "replay_in_place" not in vars(ge.target_graphs[6])
+    ge.verify_probs(torch.zeros(1, 2), 0.6, 0.9)
+    assert cap.probs.shape == (6, 8)                                   # no longer captured
+
+    shapes = bench.write_outputs(str(tmp_path / "out"), [11, 12, 13], cap.probs)
+    assert shapes == {"tokens": [3], "verify_probs": [6, 8]}
+    tok, probs = np.load(tmp_path / "out" / "tokens.npy"), np.load(tmp_path / "out" / "verify_probs.npy")
+    assert tok.dtype == np.float64 and tok.tolist() == [11.0, 12.0, 13.0]
+    assert probs.dtype == np.float32 and probs.shape == (6, 8) and np.all(probs == 0.125)
+    with pytest.raises(RuntimeError):
+        bench.write_outputs(str(tmp_path / "none"), [1], None)
+    # the multi-rank engine does not dump: refused before anything starts
+    import sys
+    argv, sys.argv = sys.argv, ["bench.py", "--gpus", "2", "--dump-outputs", str(tmp_path)]
+    try:
+        with pytest.raises(SystemExit, match="single-GPU"):
+            bench.main()
+    finally:
+        sys.argv = argv
+
+
 def test_bench_self_launches_for_more_than_one_gpu():
     """``python bench.py --gpus 2`` without a launcher (the driver's command form) re-executes itself under
     torch.distributed.run with one rank per device, builds the process group and the sharded engine on every rank

@@ -5,7 +5,7 @@
 O=gpurun_out/inner; mkdir -p $O; REPS=${1:-1}
 python -m pytest tests/test_gpu_ops.py -q -x -k "narrow_panel or cursor_forms or accept or sample" > $O/pytest_ops.log 2>&1; echo "ops rc=$?"; tail -2 $O/pytest_ops.log
 python -m pytest tests/test_gpu_e2e.py -q -x > $O/pytest_e2e.log 2>&1; echo "e2e rc=$?"; tail -3 $O/pytest_e2e.log
-B="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --random-steps 0"
+B="python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --random-steps 0"
 rm -f $O/bench_ab.jsonl
 for rep in $(seq $REPS); do
   for v in "shipped:TRIFORCE_INNER_GRAPH=1" "host-setup:TRIFORCE_STEP_ON_DEVICE=0" "no-plans:TRIFORCE_STEP_ON_DEVICE=0 TRIFORCE_HOST_PLANS=0" \

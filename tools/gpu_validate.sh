@@ -50,7 +50,7 @@ cp gpurun_out/parity_notes.txt $O/parity_notes.txt 2>/dev/null; grep -c "" $O/pa
 # the tolerance table: every recorded check -> measured max / mean |d|, bound, slack
 cp gpurun_out/parity_table.jsonl $O/parity_table.jsonl 2>/dev/null; python tools/parity_table.py $O/parity_table.jsonl $O/parity_table.md --json $O/parity_table.json
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke.log
-python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 800 $O/bench.json
+python bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 800 $O/bench.json
 # 200 timed steps: ms_per_step as mean +- stdev over 10 blocks of 20 (what a sub-1 % claim is read against)
 python bench.py --steps 200 --warmup 5 --no-cpu-baseline --random-steps 0 --roofline-every 0 > $O/bench_200.json 2> $O/bench_200.err; echo "bench200 rc=$?"; python -c "import json;j=json.loads([l for l in open('$O/bench_200.json') if l.startswith('{')][-1]);print(j['value'],j['ms_per_step'],j.get('ms_per_step_blocks'))"
 # the draft step: 13-launch chain against the one-launch form (hipGraph replays), with the per-role timeline
@@ -58,10 +58,10 @@ python tools/draft_persist_bench.py --rows 1 3 7 --stamps --tag validate --out $
 # temperature + top-p + softmax: one workgroup per row against the multi-workgroup launch
 rm -f $O/topp_bench.jsonl; python tools/topp_bench.py --tag validate --out $O/topp_bench.jsonl > $O/topp_bench.log 2>&1; echo "topp bench rc=$?"; grep -c "" $O/topp_bench.jsonl
 cd /tmp && export TMPDIR=/tmp
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --random-steps 0 > $R/$O/bench_prof.json 2> $R/$O/bench_prof.err; echo "rocprof rc=$?"
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -- python $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --random-steps 0 > $R/$O/bench_prof.json 2> $R/$O/bench_prof.err; echo "rocprof rc=$?"
 # target-verify / retrieval-verify launches of the split-KV kernel separated by duration cluster + priced (tracked copy -> profiles/)
 T=$(ls -S $R/$O/prof/*/*kernel_trace.csv | head -1)
-python $R/tools/attn_by_grid.py $T $R/$O/kernels_by_stage.json "rocprofv3 --kernel-trace of python bench.py --steps 20 --warmup 5 --no-cpu-baseline --random-steps 0 (tools/gpu_validate.sh)" > $R/$O/kernels_by_stage.log 2>&1; echo "by-stage rc=$?"
+python $R/tools/attn_by_grid.py $T $R/$O/kernels_by_stage.json "rocprofv3 --kernel-trace of python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --random-steps 0 (tools/gpu_validate.sh)" > $R/$O/kernels_by_stage.log 2>&1; echo "by-stage rc=$?"
 python $R/tools/gap_analysis.py $T --steps 19 > $R/$O/gap_analysis_decode_steps.txt 2>&1; head -3 $R/$O/gap_analysis_decode_steps.txt
 # HBM traffic of the roofline kernel (two separate --pmc passes, kernel-trace only) -> the figure bench.py quotes as roofline.traffic
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $R/$O/pmc_fetch -- python $R/tools/pmc_attn.py > $R/$O/pmc_fetch.log 2>&1; echo "pmc fetch rc=$?"
@@ -77,16 +77,16 @@ python tools/pmc_mfma.py $O/pmc_mfma $O/pmc_mfma_attn_target_verify.json "tools/
 find $O/prof $O/pmc_fetch $O/pmc_write $O/pmc_mfma $O/pmc_layer_fetch $O/pmc_layer_write -name "*kernel_trace.csv" -size +20M -delete
 # the other full-size configs (BASELINE configs[2], and configs[3] at world size 1: offloading tier), only with "all"
 if [ "$1" = "all" ]; then
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --random-steps 0 --eager-comparator > $O/bench_eager_comparator.json 2> $O/bench_eager_comparator.err; echo "eager comparator rc=$?"
-  python bench.py --target lwm-128K --steps 20 --warmup 5 --no-cpu-baseline --random-steps 0 > $O/bench_lwm.json 2> $O/bench_lwm.err; echo "lwm rc=$?"; tail -c 300 $O/bench_lwm.json
+  python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --random-steps 0 --eager-comparator > $O/bench_eager_comparator.json 2> $O/bench_eager_comparator.err; echo "eager comparator rc=$?"
+  python bench.py --target lwm-128K --steps 20 --warmup 5 --full --no-cpu-baseline --random-steps 0 > $O/bench_lwm.json 2> $O/bench_lwm.err; echo "lwm rc=$?"; tail -c 300 $O/bench_lwm.json
   python bench.py --prefill 130048 --budget 12288 --gamma 16 --on-chip 9 --steps 8 --warmup 2 --no-cpu-baseline --random-steps 0 > $O/bench_offload.json 2> $O/bench_offload.err; echo "offload rc=$?"; tail -c 300 $O/bench_offload.json
   # (the 9-point acceptance sweep costs ~6 GPU-minutes: only with SWEEP=1; the tracked sweep is profiles/r04_acceptance_sweep.json)
   if [ "$SWEEP" = "1" ]; then python tools/acceptance_sweep.py $O/acceptance_sweep.json > $O/acceptance_sweep.log 2>&1; echo "sweep rc=$?"; tail -3 $O/acceptance_sweep.log; fi
   python tools/verify_bench.py final > $O/verify_bench.json 2> $O/verify_bench.err; echo "verify_bench rc=$?"; tail -c 400 $O/verify_bench.json
   # BASELINE configs[4] parameters at world size 1 (13B, gamma 16): the single-GPU line of the gamma = 16 path
-  python bench.py --target llama-13B-128K --prefill 130048 --budget 12288 --gamma 16 --steps 10 --warmup 2 --no-cpu-baseline --random-steps 0 > $O/bench_13b_cfg4.json 2> $O/bench_13b_cfg4.err; echo "13B rc=$?"; tail -c 300 $O/bench_13b_cfg4.json
+  python bench.py --target llama-13B-128K --prefill 130048 --budget 12288 --gamma 16 --steps 10 --warmup 2 --full --no-cpu-baseline --random-steps 0 > $O/bench_13b_cfg4.json 2> $O/bench_13b_cfg4.err; echo "13B rc=$?"; tail -c 300 $O/bench_13b_cfg4.json
   # BASELINE configs[3] parameters with every layer resident (the loop statistics of the gamma = 16 7B line of the prediction)
-  python bench.py --prefill 130048 --budget 12288 --gamma 16 --steps 10 --warmup 2 --no-cpu-baseline --random-steps 0 > $O/bench_7b_cfg3_resident.json 2> $O/bench_7b_cfg3_resident.err; echo "7B cfg3 resident rc=$?"; tail -c 300 $O/bench_7b_cfg3_resident.json
+  python bench.py --prefill 130048 --budget 12288 --gamma 16 --steps 10 --warmup 2 --full --no-cpu-baseline --random-steps 0 > $O/bench_7b_cfg3_resident.json 2> $O/bench_7b_cfg3_resident.err; echo "7B cfg3 resident rc=$?"; tail -c 300 $O/bench_7b_cfg3_resident.json
   # per-rank stage latencies at W = 1 / 2 / 4 / 8 for configs[1] / [3] / [4] (rank 0's shard on this GPU, exchanges in their
   # shipped form against a one-rank group) -> the predicted scaling table the first multi-GPU run is judged against
   rm -f $O/tp_shard_by_world.jsonl
