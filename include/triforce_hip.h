@@ -348,6 +348,36 @@ int tf_skinny_qkv_rope_n8(const void* wqkv_n8, const void* x, int64_t xs_m, int6
                           const float* ss_in, const void* cos, const void* sin, const int64_t* positions, void* q_out,
                           void* k_cache, void* v_cache, int64_t stride_t, int64_t stride_h, int slot0,
                           const int32_t* slot0_dev, int M, int H, int D, int K, int rotate_k, void* stream);
+/* FP8-WEIGHT forms of the three fused skinny GEMMs (csrc/gemv_fp8.hip) — the retrieval-cache ("spec") forward of the
+ * target model with TRIFORCE_RETRIEVAL_WEIGHTS=fp8.  That forward only drafts: the target verify keeps
+ * the fp16 weights and the accept rule keeps the output exact for the distribution the draft tokens were sampled from.
+ * Numerics contract:
+ *   quantization (host, triforce_amd.ops.quantize_fp8_rows, once per weight): per output row s[n] = amax_k |W[n][k]| / 448
+ *     in fp32 (an all-zero row: s = 1); code = e4m3fn (OCP, not fnuz) of W / s, clamped to +-448 BEFORE the cast,
+ *     rounded to nearest even.  Rows in the order the kernel reads them: q|k|v in ops.rope_row_order, gate and up apart;
+ *   weight-only: activations stay fp16; the codes are decoded to fp16 exactly (scale 1.0) and multiplied on the 16-bit
+ *     kernel's f16 MFMA with fp32 accumulation (no fp8 x fp8 / MX-scaled MFMA: those would quantize the activations);
+ *   the row scale is applied ONCE, in fp32, on the accumulator, where the 16-bit kernel rounds: fp16(s[n] * acc) instead
+ *     of fp16(acc); gate|up: s_gate and s_up before their separate fp16 roundings.  Every other rounding point — norm
+ *     prologue, residual add, SwiGLU, RoPE + append, the fp32 cast of the logits, ss_in / ss_out — is the 16-bit form's.
+ * Codes packed by triforce_amd.ops.pack_weight_fp8: [N/16][K/64][4 (g)][16 (i)][16 B], the 16 bytes of piece (g, i) =
+ * W[n0+i][k0+8g .. +7] then W[n0+i][k0+32+8g .. +7]: one 16x64 tile is one contiguous KiB.  `scale` / `gate_scale` /
+ * `up_scale`: [N] fp32 in the same row order.  Operands, activation layouts and fused epilogues as tf_skinny_gemm_act /
+ * tf_skinny_gemm_swiglu_act / tf_skinny_qkv_rope_act.  NULL codes or scales, K % 64 != 0, N % 16 != 0, M > 32 -> -EINVAL
+ * before anything is launched. */
+int tf_skinny_gemm_fp8_act(const void* w_fp8, const float* scale, const void* x, int64_t xs_m, int64_t xs_k,
+                           const void* ln_w, float eps, const float* ss_in, const void* resid, int64_t rs_m, int64_t rs_k,
+                           float* ss_out, void* y, int64_t ys_m, int64_t ys_k, int M, int N, int K, int out_f32,
+                           void* stream);
+int tf_skinny_gemm_swiglu_fp8_act(const void* gate_fp8, const float* gate_scale, const void* up_fp8,
+                                  const float* up_scale, const void* x, int64_t xs_m, int64_t xs_k, const void* ln_w,
+                                  float eps, const float* ss_in, void* act, int64_t ys_m, int64_t ys_k, int M, int I, int K,
+                                  void* stream);
+int tf_skinny_qkv_rope_fp8_act(const void* wqkv_fp8, const float* scale, const void* x, int64_t xs_m, int64_t xs_k,
+                               const void* ln_w, float eps, const float* ss_in, const void* cos, const void* sin,
+                               const int64_t* positions, void* q_out, void* k_cache, void* v_cache, int64_t stride_t,
+                               int64_t stride_h, int slot0, const int32_t* slot0_dev, int M, int H, int D, int K,
+                               int rotate_k, void* stream);
 /* Split-K workspace of the CURRENT device (csrc/gemv.hip, SgKsplit): GEMMs with few output panels — the q|k|v and
  * gate|up shards of a tensor-parallel rank — split K across up to 4 workgroups per panel; their partial sums meet in
  * `ws` (zero-filled device memory, first 16 KiB = per-panel tickets, left zero by every launch; 8 MiB covers every shape

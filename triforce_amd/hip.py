@@ -61,6 +61,12 @@ SIGNATURES = {
     "tf_skinny_qkv_rope_n8": (_i32, [_vp, _vp, _i64, _i64, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32,
                                      _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "tf_sg_tune": (_i32, [_i32, _i32]),
+    "tf_skinny_gemm_fp8_act": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _f32, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32,
+                                      _i32, _i32, _i32, _vp]),
+    "tf_skinny_gemm_swiglu_fp8_act": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _f32, _vp, _vp, _i64, _i64, _i32, _i32,
+                                             _i32, _vp]),
+    "tf_skinny_qkv_rope_fp8_act": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
+                                          _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "tf_sg_workspace": (_i32, [_vp, _i64]),
     "tf_topp_probs": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _vp]),
     "tf_sample_inverse_cdf": (_i32, [_vp, _vp, _vp, _i32, _vp]),

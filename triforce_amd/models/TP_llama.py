@@ -26,7 +26,8 @@ from ..utils.sampling import norm_logits
 from .cache import (DistributedKVCacheBuffer, DistributedRetrievalCache, DistributedRetrievalCache_Seqouia,
                     DistributedSimpleCache)
 from .config_yarn import LlamaConfig
-from .llama_core import LlamaWeights, parse_random_spec, rope_tables_for, softmax_scale_for
+from .llama_core import (RETRIEVAL_WEIGHTS_ENV, LlamaWeights, parse_random_spec, retrieval_weights, rope_tables_for,
+                         softmax_scale_for)
 from .TP_layers import DistributedOffloadingConfig
 
 
@@ -53,6 +54,9 @@ class DistributedLlama:
                  temperature=0.6, top_p=0.9, ssl=0, draft=None, draft_cache=None, flash_attn=True, config=None,
                  device=None, tree_size=0) -> None:
         assert dtype == torch.float16
+        if retrieval_weights() == "fp8":
+            raise NotImplementedError(f"{RETRIEVAL_WEIGHTS_ENV}=fp8: the FP8 retrieval tier exists only on the single-GPU "
+                                      "engine (models/modeling_llama.py), not on the tensor-parallel / Sequoia engine")
         self.device = torch.device(device) if device is not None else torch.device("cuda", local_rank)
         self.dtype = dtype
         self.local_rank, self.world_size = local_rank, world_size

@@ -314,7 +314,14 @@ def calibrate_engine(graph_engine, gamma, temperature, top_p, n_probe=8):
         eng.model(input_ids=ids, kv_cache=eng.kv_cache, graph_cache=None)
         eng.kv_cache.seq_len = S                               # roll the probe back
 
-    return calibrate(W, run_retrieval, run_full, gamma + 1, temperature, top_p, n_probe=n_probe)
+    # calibrated on the fp16 tier whatever TRIFORCE_RETRIEVAL_WEIGHTS says, so that aligned:a:b names the same weights with
+    # or without the FP8 tier; the lm_head refresh inside calibrate() re-quantizes its FP8 copy in place
+    tier, W.fp8_tier = W.fp8_tier, False
+    try:
+        out = calibrate(W, run_retrieval, run_full, gamma + 1, temperature, top_p, n_probe=n_probe)
+    finally:
+        W.fp8_tier = tier
+    return out
 
 
 def calibrate_llm(llm, gamma, temperature, top_p, n_probe=8):

@@ -59,6 +59,22 @@ def softmax_scale_for(head_dim):
     return float(1 / torch.sqrt(torch.tensor(head_dim, dtype=torch.float16)))
 
 
+# ---- retrieval-verify weight tier ----------------------------------------------------------------------
+RETRIEVAL_WEIGHTS_ENV = "TRIFORCE_RETRIEVAL_WEIGHTS"
+
+
+def retrieval_weights():
+    """TRIFORCE_RETRIEVAL_WEIGHTS: ``fp16`` (default) or ``fp8`` — the weights the target's retrieval-cache (spec) forward
+    streams.  Read when a target model is built; fp8 needs the fused decode layer (TRIFORCE_FUSE=all)."""
+    v = os.environ.get(RETRIEVAL_WEIGHTS_ENV, "fp16").strip().lower() or "fp16"
+    if v not in ("fp16", "fp8"):
+        raise ValueError(f"{RETRIEVAL_WEIGHTS_ENV}={v!r}: expected fp16 or fp8")
+    if v == "fp8" and ops.FUSE_MODE != "all":
+        raise ValueError(f"{RETRIEVAL_WEIGHTS_ENV}=fp8 needs the fused decode layer (TRIFORCE_FUSE=all, got {ops.FUSE_MODE!r}): "
+                         "the FP8 kernels exist only in that form")
+    return v
+
+
 class CausalLMOutput:
     __slots__ = ("logits", "probs")
 
@@ -87,6 +103,8 @@ class LlamaWeights:
         self.wqkv, self.wo, self.wgu, self.wd, self.ln1, self.ln2 = [], [], [], [], [], []
         self.aligned = None       # models/aligned.py: spec + read-out state of an aligned synthetic pair
         self.capture = None       # list -> the forward appends its final residual stream (pre-norm), for calibration
+        self.retrieval_fp8 = False    # finalize() builds FP8 copies of the five decode GEMM weights (build_fp8_)
+        self.fp8_tier = True          # ... which the spec forward uses while this is set (calibration clears it)
 
     # -- loading ---------------------------------------------------------------------------
     def _shard_rows(self, w, n_local):
@@ -189,7 +207,21 @@ class LlamaWeights:
         self.wo = [PL(w) for w in self.wo]
         self.wgu = [PL(w, split=2) for w in self.wgu]
         self.wd = [PL(w) for w in self.wd]
+        if self.retrieval_fp8:
+            self.build_fp8_()
         return self
+
+    def build_fp8_(self):
+        """FP8 copies (ops.Fp8Linear) of q|k|v, o, gate|up, down and lm_head for the retrieval-cache forward; each is
+        re-quantized in place whenever its PackedLinear is refreshed."""
+        for pl in [self.lm_head] + self.wqkv + self.wo + self.wgu + self.wd:
+            if pl.fp8 is None:
+                pl.fp8 = ops.Fp8Linear(pl)
+        return self
+
+    def fp8_active(self):
+        """Does the spec forward stream the FP8 copies right now?"""
+        return self.retrieval_fp8 and self.fp8_tier and self.lm_head.fp8 is not None
 
     def nbytes(self):
         ts = [self.embed, self.lm_head, self.norm] + self.wqkv + self.wo + self.wgu + self.wd + self.ln1 + self.ln2

@@ -15,7 +15,7 @@ from .. import ops
 from .cache import RetrievalCache
 from .config_yarn import LlamaConfig
 from .llama_core import (CausalLMOutput, LlamaWeights, load_checkpoint_state_dict, parse_random_spec,
-                         rope_tables_for, softmax_scale_for)
+                         retrieval_weights, rope_tables_for, softmax_scale_for)
 
 
 class LlamaForCausalLM:
@@ -24,6 +24,9 @@ class LlamaForCausalLM:
         self.device = torch.device(device)
         self.dtype = torch.float16
         self.weights = LlamaWeights(config, self.device)
+        # TRIFORCE_RETRIEVAL_WEIGHTS=fp8: the retrieval-cache (spec) forward streams FP8 copies of its five GEMM weights
+        # (DESIGN section 16); every other forward keeps the fp16 weights
+        self.weights.retrieval_fp8 = retrieval_weights() == "fp8"
         cos, sin = rope_tables_for(config)
         self.cos, self.sin = cos.to(self.device), sin.to(self.device)
         self.scale = softmax_scale_for(config.hidden_size // config.num_attention_heads)
@@ -100,6 +103,13 @@ class LlamaForCausalLM:
         mode = ops.FUSE_MODE if (ops.can_fuse_rows(q_len, W.embed, W.wqkv[0], W.wo[0], W.wgu[0], W.wd[0], W.lm_head)
                                  and W.wqkv[0].wp_rope is not None) else "none"
         fused = mode in ("all", "all2")
+        # the retrieval-verify tier: a spec forward with FP8 weights (ops.Fp8Linear) in its five GEMMs
+        f8 = spec and W.fp8_active()
+        if f8 and mode != "all":
+            raise RuntimeError(f"the FP8 retrieval tier needs the fused decode layer (mode {mode!r}, {q_len} rows)")
+        Wqkv, Wo, Wgu, Wd, Wlm = ((W.wqkv, W.wo, W.wgu, W.wd, W.lm_head) if not f8 else
+                                  ([w.fp8 for w in W.wqkv], [w.fp8 for w in W.wo], [w.fp8 for w in W.wgu],
+                                   [w.fp8 for w in W.wd], W.lm_head.fp8))
         # the fused layer keeps residual stream / attention output / SwiGLU output k-octet-major (ops.Act): the GEMMs' B
         # operand is then read in 256-byte runs (ops.py, "activation layouts")
         packed = fused and ops.act_packed(q_len)
@@ -119,7 +129,7 @@ class LlamaForCausalLM:
                 slot = kv_cache.append_slot(i, q_len)
                 sk = slot + q_len
             if fused:
-                q = ops.qkv_rope(x, W.wqkv[i], W.ln1[i], W.eps, self.cos, self.sin, pos, kl, vl, slot, H, D,
+                q = ops.qkv_rope(x, Wqkv[i], W.ln1[i], W.eps, self.cos, self.sin, pos, kl, vl, slot, H, D,
                                  ss_in=ss if i > 0 else None, slot0_dev=dev_len[0] if dev_len is not None else None)
             else:
                 if d is None:
@@ -148,9 +158,9 @@ class LlamaForCausalLM:
                 if streaming:
                     kv_cache.layer_done(i, slot, q_len)
             if fused:
-                ops.linear(a, W.wo[i], resid=x, out=x, ss_out=ss)                               # x += attn_out
-                act = ops.mlp_act(x, W.wgu[i], ln=W.ln2[i], eps=W.eps, ss_in=ss)
-                ops.linear(act, W.wd[i], resid=x, out=x, ss_out=ss)                             # x += mlp_out
+                ops.linear(a, Wo[i], resid=x, out=x, ss_out=ss)                                 # x += attn_out
+                act = ops.mlp_act(x, Wgu[i], ln=W.ln2[i], eps=W.eps, ss_in=ss)
+                ops.linear(act, Wd[i], resid=x, out=x, ss_out=ss)                               # x += mlp_out
             else:
                 o = ops.linear(a, W.wo[i])
                 h = ops.rmsnorm(o, W.ln2[i], W.eps, residual=x, sum_out=x)           # x += attn_out
@@ -161,7 +171,7 @@ class LlamaForCausalLM:
         if fused:
             if W.capture is not None:
                 W.capture.append(x.rows() if packed else x.clone())
-            logits = ops.linear(x, W.lm_head, out_f32=True, ln=W.norm, eps=W.eps, ss_in=ss).unsqueeze(0)
+            logits = ops.linear(x, Wlm, out_f32=True, ln=W.norm, eps=W.eps, ss_in=ss).unsqueeze(0)
         else:
             h = ops.rmsnorm(d, W.norm, W.eps, residual=x, sum_out=x)
             if W.capture is not None:

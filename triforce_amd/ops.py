@@ -165,6 +165,7 @@ class PackedLinear:
             self.parts_n8 = [pack_weight_n8(b) for b in w.chunk(split, dim=0)]
         if self.wp_rope is not None and w.is_cuda and n8_applies(self.N, self.K):
             self.wp_rope_n8 = pack_weight_n8(w[rope_row_order_n8(rope[0], rope[1], w.device)])
+        self.fp8 = None           # Fp8Linear of the retrieval-verify tier (models/llama_core.LlamaWeights.build_fp8_)
 
     def refresh_(self):
         """Re-pack IN PLACE after ``self.w`` was modified in place (captured hipGraphs keep their pointers)."""
@@ -178,7 +179,100 @@ class PackedLinear:
                 dst.copy_(pack_weight_n8(blk))
         if self.wp_rope_n8 is not None:
             self.wp_rope_n8.copy_(pack_weight_n8(self.w[rope_row_order_n8(self.rope[0], self.rope[1], self.w.device)]))
+        if self.fp8 is not None:
+            self.fp8.refresh_()
         return self
+
+
+# ---- FP8 weights of the retrieval-verify tier (csrc/gemv_fp8.hip; TRIFORCE_RETRIEVAL_WEIGHTS=fp8, DESIGN section 16) ------
+# Weight-only e4m3fn codes with one fp32 scale per output row; the kernels decode the codes to fp16 exactly and apply the
+# scale to the fp32 accumulator where the 16-bit kernel rounds (include/triforce_hip.h, "FP8-WEIGHT forms").
+FP8_MAX = 448.0
+
+
+def quantize_fp8_rows(w):
+    """[N, K] weight -> (codes [N, K] uint8, scale [N] fp32): s[n] = amax_k |W[n, k]| / 448 in fp32 (1 for an all-zero
+    row), code = e4m3fn(W / s) rounded to nearest even, clamped to +-448 BEFORE the cast (the cast itself turns values
+    past the largest finite e4m3fn value into NaN)."""
+    w32 = w.float()
+    amax = w32.abs().amax(dim=1)
+    s = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax))
+    q = (w32 / s[:, None]).clamp_(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
+    return q.view(torch.uint8), s
+
+
+def dequantize_fp8_rows(codes, scale):
+    """s[n] * decode(code[n, k]) in fp32 (exact: every e4m3fn value is an fp32 value)."""
+    return codes.view(torch.float8_e4m3fn).float() * scale.float()[:, None]
+
+
+def pack_weight_fp8(codes):
+    """[N, K] uint8 e4m3fn codes -> [N/16][K/64][4 (g)][16 (i)][16]: per 16-row panel and 64-wide super-chunk one contiguous
+    KiB; the 16 bytes of piece (g, i) are row i's k-octet g of the even 32-wide chunk, then its k-octet g of the odd one
+    (the A operands of the two f16 MFMAs that 16-byte load feeds)."""
+    N, K = codes.shape
+    assert N % 16 == 0 and K % 64 == 0 and codes.dtype == torch.uint8
+    return codes.view(N // 16, 16, K // 64, 2, 4, 8).permute(0, 2, 4, 1, 3, 5).reshape(N // 16, K // 64, 4, 16, 16).contiguous()
+
+
+def unpack_weight_fp8(packed):
+    """Inverse of pack_weight_fp8."""
+    P, S = packed.shape[0], packed.shape[1]
+    return packed.view(P, S, 4, 16, 2, 8).permute(0, 3, 1, 4, 2, 5).reshape(P * 16, S * 64).contiguous()
+
+
+class Fp8Linear:
+    """FP8 copy of a PackedLinear for the FP8-weight skinny GEMMs: per weight stream (one; two for a fused gate|up) the
+    packed e4m3fn codes and the fp32 row scales, rows in the order the kernel reads them (a q|k|v weight, ``rope``, in
+    rope_row_order).  Built from — and re-quantized by ``refresh_()`` from — the PackedLinear's fp16 ``w``."""
+
+    def __init__(self, pl):
+        assert isinstance(pl, PackedLinear)
+        self.src, self.N, self.K, self.split, self.rope = pl, pl.N, pl.K, pl.split, pl.rope
+        if not pl.w.is_cuda:
+            raise hip.TriforceHipError("FP8 weights need a HIP device tensor (no CPU fallback)")
+        if self.K % 64 or (self.N // self.split) % 16 or self.N % self.split:
+            raise hip.TriforceHipError(f"FP8 weights: unsupported shape {self.N} x {self.K} (rows per stream % 16, K % 64)")
+        if self.rope is not None and (self.rope[1] % 32 or self.N != 3 * self.rope[0] * self.rope[1]):
+            raise hip.TriforceHipError(f"FP8 weights: q|k|v weight {self.N} x {self.K} does not match H, D = {self.rope}")
+        self.codes, self.scales = [], []
+        for blk in self._streams():
+            c, s = quantize_fp8_rows(blk)
+            self.codes.append(pack_weight_fp8(c))
+            self.scales.append(s.contiguous())
+
+    def _streams(self):
+        w = self.src.w
+        if self.rope is not None:
+            return [w[rope_row_order(self.rope[0], self.rope[1], w.device)]]
+        return list(w.chunk(self.split, dim=0))
+
+    def refresh_(self):
+        """Re-quantize IN PLACE after the fp16 weight changed (captured hipGraphs keep these pointers)."""
+        for dst_c, dst_s, blk in zip(self.codes, self.scales, self._streams()):
+            c, s = quantize_fp8_rows(blk)
+            dst_c.copy_(pack_weight_fp8(c))
+            dst_s.copy_(s)
+        return self
+
+    def dequantized(self):
+        """The fp32 weight this copy stands for, in the fp16 weight's row order (oracles of the tests)."""
+        rows = [dequantize_fp8_rows(unpack_weight_fp8(c), s) for c, s in zip(self.codes, self.scales)]
+        w = torch.cat(rows, dim=0)
+        if self.rope is not None:
+            out = torch.empty_like(w)
+            out[rope_row_order(self.rope[0], self.rope[1], w.device)] = w
+            return out
+        return w
+
+    def nbytes(self):
+        return sum(c.numel() + 4 * s.numel() for c, s in zip(self.codes, self.scales))
+
+
+def _fp8_rows_ok(x, w):
+    if not (x.is_cuda and x.shape[0] <= SKINNY_MAX_ROWS and x.dtype == _HALF and x.shape[1] == w.K):
+        raise hip.TriforceHipError(f"FP8 weights run only on the skinny decode kernels (<= {SKINNY_MAX_ROWS} fp16 device rows "
+                                   f"of width {w.K}); got {tuple(x.shape)} {x.dtype}")
 
 
 def _w(w):
@@ -349,7 +443,11 @@ def linear(x, w, out_f32=False, ln=None, eps=0.0, resid=None, out=None, ss_in=No
     x / resid / out may be ``Act`` blocks (k-octet-major); an Act input gives an Act output unless ``out`` says
     otherwise (fp32 logits are always a row-major tensor)."""
     M = x.shape[0]
-    if isinstance(w, PackedLinear) and w.wp is not None and M <= SKINNY_MAX_ROWS and x.is_cuda:
+    f8 = isinstance(w, Fp8Linear)
+    if f8:
+        _fp8_rows_ok(x, w)
+        assert w.split == 1 and w.rope is None, "an FP8 gate|up / q|k|v weight runs through mlp_act / qkv_rope"
+    if f8 or (isinstance(w, PackedLinear) and w.wp is not None and M <= SKINNY_MAX_ROWS and x.is_cuda):
         assert x.dtype == _HALF and x.shape[1] == w.K
         if out is None:
             if out_f32 or not isinstance(x, Act):
@@ -370,6 +468,11 @@ def linear(x, w, out_f32=False, ln=None, eps=0.0, resid=None, out=None, ss_in=No
             yp, ysm, ysk = _ptr(out), out.stride(0), 8
         else:
             yp, ysm, ysk = _lay(out)
+        if f8:
+            hip.check(hip.lib().tf_skinny_gemm_fp8_act(_ptr(w.codes[0]), _ptr(w.scales[0]), xp, xsm, xsk, _ptr(ln), float(eps),
+                                                       _ptr(ss_in), rp, rsm, rsk, _ptr(ss_out), yp, ysm, ysk, M, w.N, w.K,
+                                                       1 if out_f32 else 0, _stream()), "tf_skinny_gemm_fp8_act")
+            return out
         hip.check(hip.lib().tf_skinny_gemm_act(_ptr(w.wp), xp, xsm, xsk, _ptr(ln), float(eps), _ptr(ss_in), rp, rsm, rsk,
                                                _ptr(ss_out), yp, ysm, ysk, M, w.N, w.K, 1 if out_f32 else 0, _stream()),
                   "tf_skinny_gemm_act")
@@ -385,6 +488,17 @@ def mlp_act(h, wgu, ln=None, eps=0.0, ss_in=None):
     """fp16(silu(gate(h))) * up(h) for a fused gate|up weight: one kernel for <=32 rows (optionally with the
     RMSNorm of h folded in, ``ln``), GEMM + silu_mul otherwise.  An Act input gives an Act output."""
     M = h.shape[0]
+    if isinstance(wgu, Fp8Linear):
+        _fp8_rows_ok(h, wgu)
+        assert wgu.split == 2, "mlp_act takes a fused gate|up weight"
+        I = wgu.N // 2
+        act = Act.empty(M, I, h.device) if isinstance(h, Act) else torch.empty(M, I, dtype=_HALF, device=h.device)
+        hp, hsm, hsk = _lay(h)
+        ap, asm, ask = _lay(act)
+        hip.check(hip.lib().tf_skinny_gemm_swiglu_fp8_act(_ptr(wgu.codes[0]), _ptr(wgu.scales[0]), _ptr(wgu.codes[1]),
+                                                          _ptr(wgu.scales[1]), hp, hsm, hsk, _ptr(ln), float(eps), _ptr(ss_in),
+                                                          ap, asm, ask, M, I, wgu.K, _stream()), "tf_skinny_gemm_swiglu_fp8_act")
+        return act
     if isinstance(wgu, PackedLinear) and wgu.parts is not None and wgu.split == 2 and M <= SKINNY_MAX_ROWS \
             and h.is_cuda:
         I = wgu.N // 2
@@ -415,7 +529,10 @@ def qkv_rope(x, wqkv, ln, eps, cos, sin, positions, k_layer, v_layer, slot0, H, 
     (ln = input_layernorm weight, or None when x is already normalised; a row-major tensor or an Act); q (rows,H,D)
     is returned rotated, the k (rotated unless rotate_k is False) and v rows land in the cache at slot0+i."""
     _dev(ln, cos, sin, positions, k_layer, v_layer, slot0_dev)
-    assert isinstance(wqkv, PackedLinear) and wqkv.wp_rope is not None and wqkv.rope == (H, D)
+    f8 = isinstance(wqkv, Fp8Linear)
+    if f8:
+        _fp8_rows_ok(x, wqkv)
+    assert (f8 or (isinstance(wqkv, PackedLinear) and wqkv.wp_rope is not None)) and wqkv.rope == (H, D)
     rows = x.shape[0]
     assert x.is_cuda and x.dtype == _HALF and x.shape[1] == wqkv.K and rows <= SKINNY_MAX_ROWS
     assert positions.dtype == torch.int64 and positions.numel() == rows and positions.is_contiguous()
@@ -424,6 +541,13 @@ def qkv_rope(x, wqkv, ln, eps, cos, sin, positions, k_layer, v_layer, slot0, H, 
     assert _kv(v_layer) == (st, sh)
     q = torch.empty(rows, H, D, dtype=_HALF, device=x.device)
     xp, xsm, xsk = _lay(x)
+    if f8:
+        hip.check(hip.lib().tf_skinny_qkv_rope_fp8_act(_ptr(wqkv.codes[0]), _ptr(wqkv.scales[0]), xp, xsm, xsk, _ptr(ln),
+                                                       float(eps), _ptr(ss_in), _ptr(cos), _ptr(sin), _ptr(positions), _ptr(q),
+                                                       _ptr(k_layer), _ptr(v_layer), st, sh, int(slot0), _ptr(slot0_dev), rows,
+                                                       H, D, wqkv.K, 1 if rotate_k else 0, _stream()),
+                  "tf_skinny_qkv_rope_fp8_act")
+        return q
     if wqkv.wp_rope_n8 is not None and ln is not None and rows <= N8_MAX_ROWS:      # few-panel shard: 8-row panels
         hip.check(hip.lib().tf_skinny_qkv_rope_n8(_ptr(wqkv.wp_rope_n8), xp, xsm, xsk, _ptr(ln), float(eps), _ptr(ss_in),
                                                   _ptr(cos), _ptr(sin), _ptr(positions), _ptr(q), _ptr(k_layer),
