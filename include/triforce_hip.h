@@ -378,6 +378,41 @@ int tf_skinny_qkv_rope_fp8_act(const void* wqkv_fp8, const float* scale, const v
                                const int64_t* positions, void* q_out, void* k_cache, void* v_cache, int64_t stride_t,
                                int64_t stride_h, int slot0, const int32_t* slot0_dev, int M, int H, int D, int K,
                                int rotate_k, void* stream);
+/* FP8 KV CACHE (csrc/kv_fp8.hip, csrc/attn.hip) — the target's full KV cache stored as OCP e4m3fn codes with
+ * TRIFORCE_KV_CACHE=fp8.  TriForce stays lossless with respect to the target whose attention reads the
+ * dequantized K / V, not with respect to the fp16 model.
+ * Numerics contract — one exponent per (layer, head, token) row of D = 128 values, separately for K and V (K after RoPE):
+ *   exponent: a = max |x| of the row (fp16 -> fp32); e = the smallest integer with 448 * 2^e >= a, clamped to [-15, 7]
+ *     (an all-zero row: e = -15); stored as one uint8 per row, b = e + 127, in an [L][H][T] array for K and one for V;
+ *   code = e4m3fn(clamp(x * 2^-e, -448, 448)), rounded to nearest even (x * 2^-e is exact in fp32; the clamp comes before
+ *     the cast); rows with a > 57 344 saturate; NaN / Inf inputs are undefined;
+ *   deq = fp16(code) * 2^e, EXACT in fp16: the smallest code step 2^-9 times 2^-15 is fp16's 2^-24, 448 * 2^7 = 57 344.
+ *   Every attention read of the full cache sees deq, including the rows appended by the same forward (they are
+ *   quantized before the attention that reads them).
+ * Codes: [H][T][D] bytes per layer (strides in bytes); exponents: [H][exp_stride_h] bytes per layer, one per key.
+ *
+ * tf_kv_quant_rows: n fp16 rows of K and of V, row (h, i) at k_in / v_in + h * in_stride_h + i * in_stride_t (halves),
+ *   quantized into the codes / exponents at token slot0 + i — or *slot0_dev + i when slot0_dev != NULL (the captured
+ *   forward).  k_deq / v_deq (both or neither; same strides as the input, may alias it): deq is written there too.  No
+ *   bounds check of the slot against the cache: the caller sizes it.  Bit-identical to the host restatement
+ *   triforce_amd.ops.kv_quantize_ref.  NULL pointers, D != 128, bad strides -> -EINVAL (checked before n == 0, a no-op).
+ * tf_attn_decode_fp8_act: tf_attn_decode_act over the codes (D = 128, sq <= 32).  The output is bit-identical to
+ *   tf_attn_decode_act on deq(K), deq(V) with the same nsplit (same tiles, same order, same merge).  stride_t / stride_h of
+ *   the codes: multiples of 16 bytes; exp_stride_h >= sk.
+ * tf_kv_dequant_rows_pair: tf_kv_copy_rows_pair from codes + exponents ((L,H,T,D) byte views, exponents (L,H,T) with token
+ *   stride 1) to fp16 (L,H,T,D) views: dst[l,h,dst_t0+i] = deq(src[l,h,src_t0+i]).  D = 128. */
+int tf_kv_quant_rows(const void* k_in, const void* v_in, int64_t in_stride_t, int64_t in_stride_h, void* k_codes,
+                     void* v_codes, void* k_exp, void* v_exp, int64_t code_stride_t, int64_t code_stride_h,
+                     int64_t exp_stride_h, int slot0, const int32_t* slot0_dev, int n, int H, int D, void* k_deq,
+                     void* v_deq, void* stream);
+int tf_attn_decode_fp8_act(const void* q, const void* k_codes, const void* v_codes, const void* k_exp, const void* v_exp,
+                           void* out, int64_t out_sm, int64_t out_sk, int64_t stride_t, int64_t stride_h,
+                           int64_t exp_stride_h, int sq, int sk, const int32_t* sk_dev, int H, int D, float scale,
+                           int nsplit, float* ws, int64_t ws_floats, uint32_t* tickets, void* stream);
+int tf_kv_dequant_rows_pair(const void* src_k, const void* src_v, int64_t src_stride_l, int64_t src_stride_t,
+                            int64_t src_stride_h, const void* exp_k, const void* exp_v, int64_t exp_stride_l,
+                            int64_t exp_stride_h, void* dst_k, void* dst_v, int64_t dst_stride_l, int64_t dst_stride_t,
+                            int64_t dst_stride_h, int src_t0, int dst_t0, int n, int L, int H, int D, void* stream);
 /* Split-K workspace of the CURRENT device (csrc/gemv.hip, SgKsplit): GEMMs with few output panels — the q|k|v and
  * gate|up shards of a tensor-parallel rank — split K across up to 4 workgroups per panel; their partial sums meet in
  * `ws` (zero-filled device memory, first 16 KiB = per-panel tickets, left zero by every launch; 8 MiB covers every shape

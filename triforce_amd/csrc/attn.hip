@@ -211,6 +211,85 @@ __device__ __forceinline__ void rows_to_frags(const half8 (&kr)[D / 32], const h
     }
 }
 
+// ---- FP8 (e4m3fn) KV rows: tf_attn_decode_fp8_act (include/triforce_hip.h, "FP8 KV cache") ----
+// A 16-key tile is 2 KiB of K codes + 2 KiB of V codes: lane l of instruction j reads the 16 codes [16 (l % 8), +16) of row
+// 8 j + l / 8 (128-byte rows, eight per instruction) and that row's exponent byte.  The codes are decoded into the SAME
+// wave-private LDS tile rows_to_frags fills (exactly: fp16(code) is exact and x 2^e is exact in fp16 by the contract), so the
+// fragments, the tile order and attn_tile are those of the fp16 kernel: the output bits equal tf_attn_decode_act's on the
+// dequantized cache.
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+
+struct F8Tile {
+    u32x4 kc[2], vc[2];    // codes of rows 8 j + lane / 8, j = 0, 1
+    int ke[2], ve[2];      // their exponent bytes (b = e + 127)
+};
+
+__device__ __forceinline__ void load_kv_rows_f8(const uint8_t* __restrict__ kbase, const uint8_t* __restrict__ vbase,
+                                                const uint8_t* __restrict__ kebase, const uint8_t* __restrict__ vebase,
+                                                int64_t stride_t, int tile, int sk, int lane, F8Tile& x) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        int key = tile * 16 + 8 * j + (lane >> 3);
+        key = key < sk ? key : sk - 1;                 // clamp: masked later, but must stay in-bounds
+        const int64_t off = (int64_t)key * stride_t + 16 * (lane & 7);
+        x.kc[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kbase + off));
+        x.vc[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vbase + off));
+        x.ke[j] = kebase[key];
+        x.ve[j] = vebase[key];
+    }
+}
+
+// 2^e as an fp16 pair for an exponent byte b = e + 127, e in [-15, 7] (2^-15 is the fp16 subnormal 0x0200)
+__device__ __forceinline__ half2v f8_pow2_h2(int b) {
+    const int e = b - 127;
+    const unsigned short bits = e >= -14 ? (unsigned short)((e + 15) << 10) : (unsigned short)0x0200;
+    const h16 p = __builtin_bit_cast(h16, bits);
+    return half2v{p, p};
+}
+
+// 16 codes -> two half8 of deq = fp16(code) * 2^e (both steps exact)
+__device__ __forceinline__ void f8_decode_row16(u32x4 w, int b, half8& lo, half8& hi) {
+    const half2v s = f8_pow2_h2(b);
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        const half2v p0 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[d], 1.0f, false) * s;   // bytes 0, 1 of the dword
+        const half2v p1 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[d], 1.0f, true) * s;    // bytes 2, 3
+        half8& o = d < 2 ? lo : hi;
+        const int e = (d & 1) * 4;
+        o[e] = p0[0];
+        o[e + 1] = p0[1];
+        o[e + 2] = p1[0];
+        o[e + 3] = p1[1];
+    }
+}
+
+// the FP8 counterpart of rows_to_frags (D = 128): decoded rows into the same [2][16][D + 8] staging tile, same fragment reads
+__device__ __forceinline__ void f8_rows_to_frags(const F8Tile& x, h16* stage, int lane, int li, int g, half8 (&kf)[4], half8 (&vf)[4]) {
+    constexpr int D = 128, LDR = D + 8;
+    const int rl = lane >> 3, p = lane & 7;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        half8 lo, hi;
+        f8_decode_row16(x.kc[j], x.ke[j], lo, hi);
+        *reinterpret_cast<half8*>(stage + (8 * j + rl) * LDR + 16 * p) = lo;
+        *reinterpret_cast<half8*>(stage + (8 * j + rl) * LDR + 16 * p + 8) = hi;
+        f8_decode_row16(x.vc[j], x.ve[j], lo, hi);
+        *reinterpret_cast<half8*>(stage + (16 + 8 * j + rl) * LDR + 16 * p) = lo;
+        *reinterpret_cast<half8*>(stage + (16 + 8 * j + rl) * LDR + 16 * p + 8) = hi;
+    }
+#pragma unroll
+    for (int c = 0; c < D / 32; ++c) {
+        kf[c] = *reinterpret_cast<const half8*>(stage + li * LDR + 32 * c + 8 * g);
+        vf[c] = *reinterpret_cast<const half8*>(stage + (16 + li) * LDR + 32 * c + 8 * g);
+    }
+}
+// Tiles in flight per wave of the FP8 stream: a ring of 3 (two loaded under each tile's MFMAs) = 8 KiB, the bytes the fp16
+// two-deep loop keeps in flight (half or twice that loses 10-25 %).
+#ifndef TF_ATTN_F8_RING
+#define TF_ATTN_F8_RING 3
+#endif
+
 struct TreeMask {                      // tree-attention visibility bits (block kernel, TREE = true)
     const uint32_t* rows;              // [n_rows][words] uint32, bit j of a row = tree key j visible
     int words, row0, start;            // words per row, first row of this launch, key index of tree key 0
@@ -305,11 +384,13 @@ __device__ __forceinline__ void attn_tile(AttnState<D, QT>& st, const half8 (&kf
 
 
 // ws layout: o[H][nsplit][QR][D] | m[H][nsplit][QR] | l[H][nsplit][QR],  QR = QT*16
-template <int D, int QT, int DEEP = 0, int NW = 4>
+// F8: k / v are e4m3fn codes (strides in bytes) with exponent bytes ke / ve ([H][e_sh] per head, one per key)
+template <int D, int QT, int DEEP = 0, int NW = 4, bool F8 = false>
 __device__ __forceinline__ void attn_split_body(
     const h16* __restrict__ q, const h16* __restrict__ k, const h16* __restrict__ v, int64_t stride_t,
     int64_t stride_h, int sq, int sk_host, const int32_t* __restrict__ sk_dev, int H, float scale, int nsplit,
-    float* __restrict__ ws, unsigned* __restrict__ tickets, h16* __restrict__ out, int64_t osm, int64_t osk) {
+    float* __restrict__ ws, unsigned* __restrict__ tickets, h16* __restrict__ out, int64_t osm, int64_t osk,
+    const uint8_t* __restrict__ ke = nullptr, const uint8_t* __restrict__ ve = nullptr, int64_t e_sh = 0) {
     constexpr int NC = D / 32, NT = D / 16, QR = QT * 16;
     const int split = blockIdx.x, h = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -352,7 +433,8 @@ __device__ __forceinline__ void attn_split_body(
     constexpr int HALVES = NW > 4 ? 2 : 1, DH = D / HALVES, NTH = NT / HALVES;
     constexpr bool ROWS = TF_ATTN_ROW_LOADS > 0 && NW == 4;
     constexpr size_t MERGE_BYTES = sizeof(float) * ((size_t)NW * 16 * (DH + 1) + 2 * NW * 16);
-    constexpr size_t STAGE_BYTES = ROWS ? (size_t)NW * 2 * 16 * (D + 8) * sizeof(h16) : 0;
+    static_assert(!F8 || (D == 128 && NW == 4 && DEEP == 0), "FP8 stream: D = 128, 4 waves");
+    constexpr size_t STAGE_BYTES = (ROWS || F8) ? (size_t)NW * 2 * 16 * (D + 8) * sizeof(h16) : 0;
     __shared__ __attribute__((aligned(16))) unsigned char sm_raw[MERGE_BYTES > STAGE_BYTES ? MERGE_BYTES : STAGE_BYTES];
     h16* stage = reinterpret_cast<h16*>(sm_raw) + (size_t)wave * 2 * 16 * (D + 8);
 
@@ -387,7 +469,34 @@ __device__ __forceinline__ void attn_split_body(
     // with twice as much in flight — so the form is chosen by the length of the wave's stream.
     static_assert(NW == 4 || (DEEP == 0 && (QT == 1 ? TF_ATTN_RING_Q1 : TF_ATTN_RING_Q2) == 0), "deep / ring forms: 4 waves");
     int t = t_begin + wave;
-    if constexpr (DEEP > 0) {
+    if constexpr (F8) {
+        // a ring of TF_ATTN_F8_RING tiles, every load unconditional (past the last tile it re-reads it: the waitcnt pass then
+        // keeps the younger tiles in flight in front of each use); tiles consumed in the fp16 loops' order
+        constexpr int RING = TF_ATTN_F8_RING;
+        const uint8_t* kb8 = reinterpret_cast<const uint8_t*>(k) + (int64_t)h * stride_h;
+        const uint8_t* vb8 = reinterpret_cast<const uint8_t*>(v) + (int64_t)h * stride_h;
+        const uint8_t* keb = ke + (int64_t)h * e_sh;
+        const uint8_t* veb = ve + (int64_t)h * e_sh;
+        if (t < t_end) {
+            F8Tile ring[RING];
+            const int tl = t_end - 1;
+#pragma unroll
+            for (int s = 0; s < RING; ++s) load_kv_rows_f8(kb8, vb8, keb, veb, stride_t, min(t + 4 * s, tl), sk, lane, ring[s]);
+            while (t < t_end) {
+#pragma unroll
+                for (int s = 0; s < RING; ++s) {
+                    const int ti = t + 4 * s;
+                    if (ti < t_end) {
+                        half8 kf_[NC], vf_[NC];
+                        f8_rows_to_frags(ring[s], stage, lane, li, g, kf_, vf_);
+                        ATTN_TILE_FRAGS(kf_, vf_, ti);
+                    }
+                    load_kv_rows_f8(kb8, vb8, keb, veb, stride_t, min(ti + 4 * RING, tl), sk, lane, ring[s]);
+                }
+                t += 4 * RING;
+            }
+        }
+    } else if constexpr (DEEP > 0) {
         // rounds of N tiles: all N loads issued (tiles past the end re-read the last one: no conditional load, so the
         // waitcnt pass keeps vmcnt(8 (N - 1 - i)) in front of tile i), then consumed in order
 #define ATTN_DEEP_ROUND(N)                                                                                   \
@@ -463,7 +572,7 @@ __device__ __forceinline__ void attn_split_body(
     float (*sm_o)[16][DH + 1] = reinterpret_cast<float (*)[16][DH + 1]>(sm_raw);
     float (*sm_m)[16] = reinterpret_cast<float (*)[16]>(sm_raw + sizeof(float) * (size_t)NW * 16 * (DH + 1));
     float (*sm_l)[16] = sm_m + NW;
-    if constexpr (ROWS) __syncthreads();               // another wave may still be reading its staging tile where this one is about to write
+    if constexpr (ROWS || F8) __syncthreads();        // another wave may still be reading its staging tile where this one is about to write
     float* ws_o = ws;
     float* ws_m = ws + (int64_t)H * nsplit * QR * D;
     float* ws_l = ws_m + (int64_t)H * nsplit * QR;
@@ -705,6 +814,19 @@ __global__ __launch_bounds__(64 * TF_ATTN_Q2_WAVES, TF_ATTN_Q2_WAVES == 8 ? 2 : 
                                                tickets, out, osm, osk);
 }
 #endif
+
+// The FP8-KV form (tf_attn_decode_fp8_act): k / v are code pointers, ke / ve the exponent bytes.  The one-q-tile form keeps the
+// fp16 kernel's bounds, the two-q-tile form its TF_ATTN_QT2_OCC waves per SIMD.
+template <int QT>
+__global__ __launch_bounds__(256, QT == 2 && TF_ATTN_QT2_OCC > 0 ? TF_ATTN_QT2_OCC : 1) void attn_split_f8_kernel(
+    const h16* __restrict__ q, const uint8_t* __restrict__ k, const uint8_t* __restrict__ v, const int32_t* __restrict__ sk_dev,
+    int sq, int sk_host, int H, int nsplit, int stride_t, int stride_h, float scale,      // <- 14 dwords preloaded into SGPRs
+    float* __restrict__ ws, unsigned* __restrict__ tickets, h16* __restrict__ out, int64_t osm, int64_t osk,
+    const uint8_t* __restrict__ ke, const uint8_t* __restrict__ ve, int64_t e_sh) {
+    attn_split_body<128, QT, 0, 4, true>(q, reinterpret_cast<const h16*>(k), reinterpret_cast<const h16*>(v), (int64_t)stride_t,
+                                         (int64_t)stride_h, sq, sk_host, sk_dev, H, scale, nsplit, ws, tickets, out, osm, osk,
+                                         ke, ve, e_sh);
+}
 
 // ---- 32-key step of the block kernel: two 16-key tiles A, B per softmax update ----------------------------
 // The QK^T products of both tiles give a lane 8 keys of one query (A keys 4g..4g+3, B keys 4g..4g+3); the V tiles
@@ -2063,6 +2185,46 @@ extern "C" int tf_attn_decode_act(const void* q, const void* k, const void* v, v
                                   float scale, int nsplit, float* ws, int64_t ws_floats, uint32_t* tickets, void* stream) {
     return attn_decode_any(q, k, v, out, out_sm, out_sk, stride_t, stride_h, sq, sk, sk_dev, H, D, scale, nsplit, ws,
                            ws_floats, tickets, stream);
+}
+
+// FP8 KV cache (include/triforce_hip.h): the same split / merge as tf_attn_decode_act (bit-identical to it on the
+// dequantized cache for the same nsplit), K / V read as e4m3fn codes with one exponent byte per (head, key).
+template <int QT>
+static int launch_attn_f8(const void* q, const void* k, const void* v, const void* ke, const void* ve, void* out, int64_t osm,
+                          int64_t osk, int64_t stride_t, int64_t stride_h, int64_t e_sh, int sq, int sk, const int32_t* sk_dev,
+                          int H, float scale, int nsplit, float* ws, unsigned* tickets, hipStream_t st) {
+    constexpr int D = 128;
+    if (tickets && nsplit > FUSED_MERGE_MAX_SPLITS &&
+        (H > 64 || nsplit > FUSED_MERGE_BIG_SPLITS || (int64_t)nsplit * H > FUSED_MERGE_BIG_MAX_WGS || !g_attn_rendezvous))
+        tickets = nullptr;
+    hipLaunchKernelGGL((attn_split_f8_kernel<QT>), dim3(nsplit, H), dim3(256), 0, st, (const h16*)q, (const uint8_t*)k,
+                       (const uint8_t*)v, sk_dev, sq, sk, H, nsplit, (int)stride_t, (int)stride_h, scale, ws, tickets,
+                       (h16*)out, osm, osk, (const uint8_t*)ke, (const uint8_t*)ve, e_sh);
+    TF_LAUNCH_CHECK();
+    if (tickets) return TF_OK;
+    hipLaunchKernelGGL((attn_combine_kernel<D>), dim3(H, sq), dim3(D, COMBINE_GROUPS), 0, st, (const float*)ws,
+                       (h16*)out, sq, H, nsplit, QT * 16, osm, osk);
+    TF_LAUNCH_CHECK();
+    return TF_OK;
+}
+
+extern "C" int tf_attn_decode_fp8_act(const void* q, const void* k_codes, const void* v_codes, const void* k_exp,
+                                      const void* v_exp, void* out, int64_t out_sm, int64_t out_sk, int64_t stride_t,
+                                      int64_t stride_h, int64_t exp_stride_h, int sq, int sk, const int32_t* sk_dev, int H,
+                                      int D, float scale, int nsplit, float* ws, int64_t ws_floats, uint32_t* tickets,
+                                      void* stream) {
+    if (!q || !k_codes || !v_codes || !k_exp || !v_exp || !out || !ws) return TF_EINVAL;
+    if (D != 128 || sq < 1 || sq > 32 || sk < 1 || H < 1 || nsplit < 1 || nsplit > COMBINE_MAX_SPLITS) return TF_EINVAL;
+    if (stride_t < D || (stride_t % 16) || (stride_h % 16) || stride_t > 0x7fffffff || stride_h > 0x7fffffff) return TF_EINVAL;
+    if (exp_stride_h < sk) return TF_EINVAL;                              // one exponent byte per key of a head
+    if (out_sm < 8 || out_sk < 8 || (out_sm % 4) || (out_sk % 4)) return TF_EINVAL;
+    if (ws_floats < tf_attn_decode_ws_floats(H, sq, D, nsplit)) return TF_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    if (sq <= 16)
+        return launch_attn_f8<1>(q, k_codes, v_codes, k_exp, v_exp, out, out_sm, out_sk, stride_t, stride_h, exp_stride_h, sq, sk,
+                                 sk_dev, H, scale, nsplit, ws, tickets, st);
+    return launch_attn_f8<2>(q, k_codes, v_codes, k_exp, v_exp, out, out_sm, out_sk, stride_t, stride_h, exp_stride_h, sq, sk,
+                             sk_dev, H, scale, nsplit, ws, tickets, st);
 }
 
 extern "C" int64_t tf_attn_block_ws_floats(int H, int D, int nsplit) { return (int64_t)H * nsplit * 128 * (D + 2); }

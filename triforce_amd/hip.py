@@ -68,6 +68,12 @@ SIGNATURES = {
     "tf_skinny_qkv_rope_fp8_act": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
                                           _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "tf_sg_workspace": (_i32, [_vp, _i64]),
+    "tf_kv_quant_rows": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _vp,
+                                _vp, _vp]),
+    "tf_attn_decode_fp8_act": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _i32, _i32,
+                                      _f32, _i32, _vp, _i64, _vp, _vp]),
+    "tf_kv_dequant_rows_pair": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i32, _i32,
+                                       _i32, _i32, _i32, _i32, _vp]),
     "tf_topp_probs": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _vp]),
     "tf_sample_inverse_cdf": (_i32, [_vp, _vp, _vp, _i32, _vp]),
     "tf_accept_chain": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp]),

@@ -11,11 +11,35 @@ SURVEY §8b B3).
 Reference quirks kept on purpose: RetrievalCache.reset() does not clear
 ``init_graph``; StreamingLLMEvictionCache.reset() does not reset ``seq_len``.
 """
+import os
 from typing import Tuple
 
 import torch
 
 from .. import ops
+
+# TRIFORCE_KV_CACHE: storage of the target's full KV cache (FlashSimpleCache).  "fp16" (default) or "fp8": OCP e4m3fn codes with
+# one exponent byte per (layer, head, token) row (include/triforce_hip.h "FP8 KV CACHE", DESIGN section 17).  With fp8 the
+# decoding stays lossless with respect to the target whose attention reads the dequantized K / V, not the fp16 model.
+KV_CACHE_ENV = "TRIFORCE_KV_CACHE"
+
+
+def kv_cache_dtype(override=None):
+    """"fp16" or "fp8": ``override`` if given, else TRIFORCE_KV_CACHE.  fp8 needs the fused decode layer (TRIFORCE_FUSE=all)."""
+    v = override if override is not None else os.environ.get(KV_CACHE_ENV, "fp16")
+    v = str(v).strip().lower() or "fp16"
+    if v not in ("fp16", "fp8"):
+        raise ValueError(f"{KV_CACHE_ENV}={v!r}: expected fp16 or fp8")
+    if v == "fp8" and ops.FUSE_MODE != "all":
+        raise ValueError(f"{KV_CACHE_ENV}=fp8 needs the fused decode layer (TRIFORCE_FUSE=all, got {ops.FUSE_MODE!r}): "
+                         "the FP8 attention exists only in that form")
+    return v
+
+
+def _refuse_fp8(what):
+    if kv_cache_dtype() == "fp8":
+        raise NotImplementedError(f"{KV_CACHE_ENV}=fp8 is implemented for the single-GPU resident cache (FlashSimpleCache) "
+                                  f"only, not for {what}")
 
 
 class Cache:
@@ -48,27 +72,96 @@ def _rows(x):
 
 
 class FlashSimpleCache(Cache):
-    """Full KV cache of the target model (reference cache.py:20-61)."""
+    """Full KV cache of the target model (reference cache.py:20-61).
 
-    def __init__(self, model, max_budget=1024) -> None:
+    ``kv_dtype`` (None: TRIFORCE_KV_CACHE) = "fp8" stores e4m3fn codes ``kc`` / ``vc`` [L][H][T][D] with exponent bytes ``ke`` /
+    ``ve`` [L][H][T]; ``.k`` / ``.v`` do not exist then.  Fresh decode-sized rows pass through the fp16 staging ``stage_k`` /
+    ``stage_v`` [H][32][D]; prefill chunks and the retrieval build read one dequantized layer in ``scratch_k`` / ``scratch_v``
+    [H][T][D]."""
+
+    fp8 = False
+
+    def __init__(self, model, max_budget=1024, kv_dtype=None) -> None:
         self.seq_len = 0
         self.max_budget = max_budget
         self.layers, self.num_heads, self.head_dim = _geom(model)
         self.hidden_size = model.config.hidden_size
         self.device = model.device
+        self.scores = []
+        if kv_cache_dtype(kv_dtype) == "fp8":
+            self._init_fp8()
+            return
         self.k, self.v = _alloc(self.layers, self.num_heads, max_budget, self.head_dim, self.device)
         self.key_cache, self.value_cache = _ref_view(self.k), _ref_view(self.v)
-        self.scores = []
+
+    def _init_fp8(self):
+        L, H, T, D = self.layers, self.num_heads, self.max_budget, self.head_dim
+        assert D == 128, f"{KV_CACHE_ENV}=fp8 needs head_dim 128 (got {D})"
+        self.fp8 = True
+        f8 = torch.float8_e4m3fn
+        self.kc = torch.zeros(L, H, T, D, dtype=f8, device=self.device)
+        self.vc = torch.zeros(L, H, T, D, dtype=f8, device=self.device)
+        self.ke = torch.full((L, H, T), ops.KV_FP8_EMIN + 127, dtype=torch.uint8, device=self.device)
+        self.ve = torch.full((L, H, T), ops.KV_FP8_EMIN + 127, dtype=torch.uint8, device=self.device)
+        self.stage_k = torch.zeros(H, ops.SKINNY_MAX_ROWS, D, dtype=torch.float16, device=self.device)
+        self.stage_v = torch.zeros(H, ops.SKINNY_MAX_ROWS, D, dtype=torch.float16, device=self.device)
+        self.scratch_k = torch.zeros(H, T, D, dtype=torch.float16, device=self.device)
+        self.scratch_v = torch.zeros(H, T, D, dtype=torch.float16, device=self.device)
+        self.key_cache, self.value_cache = _ref_view(self.kc), _ref_view(self.vc)
+
+    def __getattr__(self, name):
+        # only reached for missing attributes: .k / .v of an FP8 cache (fp16 storage that does not exist)
+        if name in ("k", "v") and self.__dict__.get("fp8", False):
+            raise AttributeError(f"FlashSimpleCache.{name}: the cache holds FP8 codes ({KV_CACHE_ENV}=fp8), there is no fp16 "
+                                 f"storage to index; use kc / vc / ke / ve or dequantize(layer)")
+        raise AttributeError(name)
+
+    def nbytes(self):
+        """Device bytes of the cache storage (FP8: codes, exponents, staging and layer scratch)."""
+        if not self.fp8:
+            return self.k.nbytes + self.v.nbytes
+        return sum(t.nbytes for t in (self.kc, self.vc, self.ke, self.ve, self.stage_k, self.stage_v, self.scratch_k,
+                                      self.scratch_v))
+
+    def dequantize(self, layer, rows=None):
+        """(k, v): fresh (H, rows, D) fp16 tensors of deq(K), deq(V) of ``layer``, rows [0, rows) (default seq_len)."""
+        n = self.seq_len if rows is None else rows
+        if not self.fp8:
+            return self.k[layer, :, :n].clone(), self.v[layer, :, :n].clone()
+        H, D = self.num_heads, self.head_dim
+        k = torch.empty(1, H, n, D, dtype=torch.float16, device=self.device)
+        v = torch.empty_like(k)
+        ops.kv_dequant_rows_pair(self.kc[layer:layer + 1], self.vc[layer:layer + 1], self.ke[layer:layer + 1],
+                                 self.ve[layer:layer + 1], k, v, 0, 0, n)
+        return k[0], v[0]
+
+    def scratch_layer(self, layer, rows):
+        """FP8: dequantize rows [0, rows) of ``layer`` into the layer scratch and return its (H,T,D) views."""
+        ops.kv_dequant_rows_pair(self.kc[layer:layer + 1], self.vc[layer:layer + 1], self.ke[layer:layer + 1],
+                                 self.ve[layer:layer + 1], self.scratch_k.unsqueeze(0), self.scratch_v.unsqueeze(0), 0, 0, rows)
+        return self.scratch_k, self.scratch_v
+
+    def layer_codes(self, layer):
+        """FP8: (k codes, v codes, k exponents, v exponents) of ``layer``: (H,T,D) and (H,T) views."""
+        return self.kc[layer], self.vc[layer], self.ke[layer], self.ve[layer]
 
     def print_status(self):
         print("[Full Cache] Cached:", self.seq_len, "| Budget:", self.max_budget)
 
     def reset(self):
         self.seq_len = 0
+        if self.fp8:
+            for t in (self.kc, self.vc):
+                t.view(torch.uint8).zero_()
+            self.ke.fill_(ops.KV_FP8_EMIN + 127)
+            self.ve.fill_(ops.KV_FP8_EMIN + 127)
+            return
         self.k.zero_()
         self.v.zero_()
 
     def layer_kv(self, layer_idx):
+        if self.fp8:                                  # fp16 views of the layer: its rows [0, seq_len) dequantized into the scratch
+            return self.scratch_layer(layer_idx, self.seq_len)
         return self.k[layer_idx], self.v[layer_idx]
 
     def tail_source(self, layers, prefill):
@@ -89,6 +182,13 @@ class FlashSimpleCache(Cache):
         k, v = _rows(key_states), _rows(value_states)
         n = k.shape[0]
         s = self.seq_len
+        if self.fp8:                                  # quantize, return deq of rows [0, s + n) in the reference's shape
+            kr, vr = k.permute(1, 0, 2).contiguous(), v.permute(1, 0, 2).contiguous()
+            ops.kv_quant_rows(kr, vr, *self.layer_codes(layer_idx), s)
+            kd, vd = self.dequantize(layer_idx, s + n)
+            if layer_idx == self.layers - 1:
+                self.seq_len += n
+            return kd.permute(1, 0, 2).unsqueeze(0), vd.permute(1, 0, 2).unsqueeze(0)
         self.k[layer_idx, :, s:s + n] = k.permute(1, 0, 2)
         self.v[layer_idx, :, s:s + n] = v.permute(1, 0, 2)
         key = self.key_cache[layer_idx][:, :s + n]
@@ -108,6 +208,7 @@ class OffloadingFlashSimpleCache(Cache):
     serves RetrievalCache.update_graph_cache without touching host memory."""
 
     def __init__(self, model, max_budget=1024, tail_capacity=None) -> None:
+        _refuse_fp8("OffloadingFlashSimpleCache")
         self.seq_len = 0
         self.max_budget = max_budget
         self.layers, self.num_heads, self.head_dim = _geom(model)
@@ -225,7 +326,10 @@ class RetrievalCache(Cache):
     def init_graph_cache(self, kv_cache, query_states, layer_idx):
         q = query_states.reshape(-1, self.num_heads, self.head_dim)
         assert 1 == q.shape[0], "query_states should be 1 for init"
-        src_k, src_v = kv_cache.layer_kv(layer_idx)
+        if getattr(kv_cache, "fp8", False):           # FP8 cache: score / select / gather over the dequantized prefill rows
+            src_k, src_v = kv_cache.scratch_layer(layer_idx, self.prefill)
+        else:
+            src_k, src_v = kv_cache.layer_kv(layer_idx)
         scores = ops.retrieval_score(src_k, q[0].contiguous(), self.chunks, self.chunk_size)
         idx = ops.retrieval_topk(scores, self.select_sets)
         ops.retrieval_gather(src_k, src_v, idx, self.k[layer_idx], self.v[layer_idx], self.chunk_size)
@@ -237,6 +341,10 @@ class RetrievalCache(Cache):
         g = kv_cache.seq_len - self.prefill
         if g > self.max_budget:
             raise IndexError(f"generated tail ({g}) exceeds the retrieval budget ({self.max_budget})")
+        if getattr(kv_cache, "fp8", False):           # FP8 cache: the generated rows are dequantized into the retrieval cache
+            ops.kv_dequant_rows_pair(kv_cache.kc[layers], kv_cache.vc[layers], kv_cache.ke[layers], kv_cache.ve[layers],
+                                     self.k[layers], self.v[layers], self.prefill, self.max_budget - g, g)
+            return
         whole = layers == slice(0, self.layers)
         if whole and ops.HOST_PLANS and self.k.is_cuda and type(kv_cache) is FlashSimpleCache:
             # the per-step refresh over all layers: the same tensors every step -> a launch plan (ops.KvCopyPairPlan); only for
@@ -364,6 +472,7 @@ class DistributedSimpleCache(Cache):
     288 GB of HBM) is allowed."""
 
     def __init__(self, config, max_budget=1024, device=None, on_chip_layers=0, ssl=0):
+        _refuse_fp8("DistributedSimpleCache (the tensor-parallel and Sequoia engines)")
         self.config = config
         self.world_size, self.local_rank = config.world_size, config.local_rank
         self.device = torch.device(device)

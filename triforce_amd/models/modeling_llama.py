@@ -115,12 +115,28 @@ class LlamaForCausalLM:
         packed = fused and ops.act_packed(q_len)
         x = ops.embed_rows(W.embed, input_ids, packed)   # (q, hidden) fp16 gather
         ss = ops.ss_buffer(x.shape[1], x.device) if mode == "all" else None     # sum(x^2) hand-off between GEMMs
+        # FP8 KV cache (TRIFORCE_KV_CACHE=fp8): the fresh rows are quantized before the attention that
+        # reads them.  Decode-sized (fused): q|k|v+RoPE into the fp16 staging, quantize into the cache, FP8 attention.
+        # Otherwise (prefill chunks): rows [0, slot) dequantized into the layer scratch, RoPE-append there, quantize with
+        # the dequantized values written back, and the fp16 attention over the scratch.
+        f8kv = (not spec) and kv_cache is not None and getattr(kv_cache, "fp8", False)
         d = None
         for i in range(W.L):
             if spec:                                    # :226-227  retrieval-cache forward
                 kl, vl = graph_cache.layer_kv(i)
                 assert q_len == graph_cache.gamma + 1, "spec forward takes exactly gamma+1 tokens (cache.py:184-189)"
                 slot, sk = graph_cache.spec_slot, graph_cache.real_budget
+            elif f8kv:
+                codes = kv_cache.layer_codes(i)
+                if dev_len is not None:
+                    slot, sk = 0, kv_cache.max_budget
+                else:
+                    slot = kv_cache.append_slot(i, q_len)
+                    sk = slot + q_len
+                if fused:
+                    kl, vl = kv_cache.stage_k, kv_cache.stage_v
+                else:
+                    kl, vl = kv_cache.scratch_layer(i, slot)
             elif dev_len is not None:                   # captured full-cache forward: lengths live on the device
                 kl, vl = kv_cache.layer_kv(i)
                 slot, sk = 0, kv_cache.max_budget
@@ -129,8 +145,14 @@ class LlamaForCausalLM:
                 slot = kv_cache.append_slot(i, q_len)
                 sk = slot + q_len
             if fused:
-                q = ops.qkv_rope(x, Wqkv[i], W.ln1[i], W.eps, self.cos, self.sin, pos, kl, vl, slot, H, D,
-                                 ss_in=ss if i > 0 else None, slot0_dev=dev_len[0] if dev_len is not None else None)
+                if f8kv:                                # fresh rows -> staging rows [0, q_len) -> the cache at slot / dev_len[0]
+                    q = ops.qkv_rope(x, Wqkv[i], W.ln1[i], W.eps, self.cos, self.sin, pos, kl, vl, 0, H, D,
+                                     ss_in=ss if i > 0 else None)
+                    ops.kv_quant_rows(kl[:, :q_len], vl[:, :q_len], *codes, slot,
+                                      slot0_dev=dev_len[0] if dev_len is not None else None)
+                else:
+                    q = ops.qkv_rope(x, Wqkv[i], W.ln1[i], W.eps, self.cos, self.sin, pos, kl, vl, slot, H, D,
+                                     ss_in=ss if i > 0 else None, slot0_dev=dev_len[0] if dev_len is not None else None)
             else:
                 if d is None:
                     h = ops.rmsnorm(x, W.ln1[i], W.eps)
@@ -140,11 +162,16 @@ class LlamaForCausalLM:
                     q = ops.qkv_rope(h, W.wqkv[i], None, 0.0, self.cos, self.sin, pos, kl, vl, slot, H, D)
                 else:
                     q = ops.rope_append(ops.linear(h, W.wqkv[i]), self.cos, self.sin, pos, kl, vl, slot, H, D)
+                if f8kv:
+                    ops.kv_quant_rows(kl[:, slot:slot + q_len], vl[:, slot:slot + q_len], *codes, slot, deq=True)
             if spec:
                 a = ops.attn_decode(q, kl, vl, sk, self.scale, packed=packed)
             elif dev_len is not None:
                 assert fused, "the captured full-cache forward needs the fused decode kernels"
-                a = ops.attn_decode(q, kl, vl, sk, self.scale, sk_dev=dev_len[1], packed=packed)
+                if f8kv:
+                    a = ops.attn_decode_fp8(q, *codes, sk, self.scale, sk_dev=dev_len[1], packed=packed)
+                else:
+                    a = ops.attn_decode(q, kl, vl, sk, self.scale, sk_dev=dev_len[1], packed=packed)
             else:
                 if build:
                     if not graph_cache.init_graph:
@@ -153,8 +180,13 @@ class LlamaForCausalLM:
                         graph_cache.update_graph_cache_retrieval(kv_cache, q, i)
                 elif rebuild:                           # generated tail is re-copied by update_graph_cache() after accept
                     graph_cache.init_graph_cache(kv_cache, q[:1], i)
-                a = ops.attn_decode(q, kl, vl, sk, self.scale, packed=True) if packed else \
-                    ops.attn_prefill(q, kl, vl, sk, self.scale)
+                if f8kv and fused:
+                    a = ops.attn_decode_fp8(q, *codes, sk, self.scale, packed=packed)
+                else:
+                    if f8kv and (build or rebuild):     # the build used the scratch: rows [0, sk) again
+                        kl, vl = kv_cache.scratch_layer(i, sk)
+                    a = ops.attn_decode(q, kl, vl, sk, self.scale, packed=True) if packed else \
+                        ops.attn_prefill(q, kl, vl, sk, self.scale)
                 if streaming:
                     kv_cache.layer_done(i, slot, q_len)
             if fused:

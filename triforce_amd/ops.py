@@ -682,6 +682,99 @@ def attn_decode(q, k_layer, v_layer, sk, scale, sk_dev=None, nsplit=None, packed
     return out
 
 
+# ---- FP8 KV cache (TRIFORCE_KV_CACHE=fp8; include/triforce_hip.h "FP8 KV CACHE") -------------------------
+KV_FP8_EMIN, KV_FP8_EMAX = -15, 7
+
+
+def kv_quantize_ref(x):
+    """Host restatement of the FP8 KV contract: x (..., D) fp16 rows -> (codes float8_e4m3fn, exponent bytes uint8 = e + 127,
+    deq fp16).  e = the smallest integer with 448 * 2^e >= max |x| of the row, clamped to [-15, 7]."""
+    a = x.float().abs().amax(dim=-1)
+    e = torch.full(a.shape, KV_FP8_EMIN, dtype=torch.int32, device=x.device)
+    for k in range(KV_FP8_EMIN, KV_FP8_EMAX):                  # the predicate falls as k grows: count the k that fail it
+        e += (448.0 * 2.0 ** k < a).to(torch.int32)
+    p = torch.pow(torch.tensor(2.0, device=x.device), e.float()).unsqueeze(-1)
+    codes = (x.float() / p).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)     # x / 2^e = x * 2^-e exactly
+    deq = (codes.float() * p).to(_HALF)
+    return codes, (e + 127).to(torch.uint8), deq
+
+
+def _f8_kv(t):
+    assert t.dim() == 3 and t.stride(2) == 1 and t.dtype == torch.float8_e4m3fn, "FP8 KV layer view must be (H,T,D) e4m3fn"
+    return t.stride(1), t.stride(0)
+
+
+def _f8_exp(t):
+    assert t.dim() == 2 and t.stride(1) == 1 and t.dtype == torch.uint8, "exponent view must be (H,T) uint8"
+    return t.stride(0)
+
+
+def kv_quant_rows(k_rows, v_rows, k_codes, v_codes, k_exp, v_exp, slot0, slot0_dev=None, deq=False):
+    """Quantize n fresh rows (k_rows / v_rows: (H,n,D) fp16 views) into an FP8 cache layer (codes (H,T,D), exponents (H,T))
+    at token slot0 (or the device scalar slot0_dev); deq=True writes the dequantized values back over the input rows."""
+    _dev(k_rows, v_rows, k_codes, v_codes, k_exp, v_exp, slot0_dev)
+    H, n, D = k_rows.shape
+    ist, ish = _kv(k_rows)
+    assert _kv(v_rows) == (ist, ish) and v_rows.shape == k_rows.shape
+    cst, csh = _f8_kv(k_codes)
+    assert _f8_kv(v_codes) == (cst, csh) and k_codes.shape[0] == H and k_codes.shape[2] == D
+    esh = _f8_exp(k_exp)
+    assert _f8_exp(v_exp) == esh
+    if slot0_dev is None and (slot0 < 0 or slot0 + n > k_codes.shape[1]):
+        raise IndexError(f"kv_quant_rows: rows [{slot0}, {slot0 + n}) leave the {k_codes.shape[1]}-row cache")
+    hip.check(hip.lib().tf_kv_quant_rows(_ptr(k_rows), _ptr(v_rows), ist, ish, _ptr(k_codes), _ptr(v_codes), _ptr(k_exp),
+                                         _ptr(v_exp), cst, csh, esh, int(slot0), _ptr(slot0_dev), n, H, D,
+                                         _ptr(k_rows) if deq else None, _ptr(v_rows) if deq else None, _stream()),
+              "tf_kv_quant_rows")
+
+
+def attn_decode_fp8(q, k_codes, v_codes, k_exp, v_exp, sk, scale, sk_dev=None, nsplit=None, packed=False):
+    """attn_decode over an FP8 cache layer: bit-identical to attn_decode on the dequantized K / V for the same nsplit.
+    Not timed into ATTN_TIMER (bench.py's roofline divides fp16 bytes by the kernel time)."""
+    _dev(q, k_codes, v_codes, k_exp, v_exp, sk_dev)
+    sq, H, D = q.shape
+    assert q.dtype == _HALF and q.is_contiguous()
+    st, sh = _f8_kv(k_codes)
+    assert _f8_kv(v_codes) == (st, sh)
+    esh = _f8_exp(k_exp)
+    assert _f8_exp(v_exp) == esh
+    if nsplit is None:
+        nsplit = _pick_nsplit(H, int(sk))
+    ws = _workspace(q.device, _ws_floats(H, sq, D, nsplit))
+    out = Act.empty(sq, H * D, q.device) if packed else torch.empty(sq, H * D, dtype=_HALF, device=q.device)
+    op, osm, osk = _lay(out)
+    stream = _stream()
+    tickets = _ticket_row(q.device, stream.value or 0) if ATTN_FUSED_MERGE and H <= _TICKET_WORDS else None
+    hip.check(hip.lib().tf_attn_decode_fp8_act(_ptr(q), _ptr(k_codes), _ptr(v_codes), _ptr(k_exp), _ptr(v_exp), op, osm, osk,
+                                               st, sh, esh, sq, int(sk), _ptr(sk_dev), H, D, float(scale), nsplit, _ptr(ws),
+                                               ws.numel(), _ptr(tickets), stream), "tf_attn_decode_fp8_act")
+    return out
+
+
+def kv_dequant_rows_pair(src_k, src_v, exp_k, exp_v, dst_k, dst_v, src_t0, dst_t0, n):
+    """dst[l,h,dst_t0+i] = deq(src[l,h,src_t0+i]) for K and V in one launch: src (L,H,T,D) e4m3fn views, exp (L,H,T) uint8
+    views (token stride 1), dst (L,H,T',D) fp16 views."""
+    if n <= 0:
+        return
+    _dev(src_k, src_v, exp_k, exp_v, dst_k, dst_v)
+    L, H, _, D = src_k.shape
+    for t in (src_k, src_v):
+        assert t.dim() == 4 and t.stride(3) == 1 and t.dtype == torch.float8_e4m3fn
+    assert src_k.stride() == src_v.stride() and src_k.shape == src_v.shape
+    for t in (exp_k, exp_v):
+        assert t.dim() == 3 and t.stride(2) == 1 and t.dtype == torch.uint8 and t.shape[:2] == (L, H)
+    assert exp_k.stride() == exp_v.stride()
+    assert dst_k.shape[0] == L and dst_k.shape[1] == H and dst_k.shape[3] == D and _lhtd(dst_k) == _lhtd(dst_v)
+    if src_t0 < 0 or dst_t0 < 0 or src_t0 + n > src_k.shape[2] or dst_t0 + n > dst_k.shape[2]:
+        raise IndexError(f"kv_dequant_rows_pair: rows [{src_t0}, {src_t0 + n}) of {src_k.shape[2]} -> [{dst_t0}, {dst_t0 + n}) "
+                         f"of {dst_k.shape[2]} leave the cache (the kernel does not bounds-check)")
+    dsl, dst_t, dsh = _lhtd(dst_k)
+    hip.check(hip.lib().tf_kv_dequant_rows_pair(_ptr(src_k), _ptr(src_v), src_k.stride(0), src_k.stride(2), src_k.stride(1),
+                                                _ptr(exp_k), _ptr(exp_v), exp_k.stride(0), exp_k.stride(1), _ptr(dst_k),
+                                                _ptr(dst_v), dsl, dst_t, dsh, int(src_t0), int(dst_t0), int(n), L, H, D,
+                                                _stream()), "tf_kv_dequant_rows_pair")
+
+
 def attn_block(q, k_layer, v_layer, sk, scale, nsplit=None, tree_mask=None, mask_row0=0, tree_start=0):
     """Attention of a block of <=128 query rows in one pass over the keys.  tree_mask None: bottom-right causal
     (a prefill chunk).  tree_mask (n_rows, words) int32 bit rows: Sequoia tree attention — keys [0, tree_start)
