@@ -346,7 +346,7 @@ class RetrievalCache(Cache):
                                      self.k[layers], self.v[layers], self.prefill, self.max_budget - g, g)
             return
         whole = layers == slice(0, self.layers)
-        if whole and ops.HOST_PLANS and self.k.is_cuda and type(kv_cache) is FlashSimpleCache:
+        if whole and self.k.is_cuda and type(kv_cache) is FlashSimpleCache:
             # the per-step refresh over all layers: the same tensors every step -> a launch plan (ops.KvCopyPairPlan); only for
             # the resident cache, whose storage never moves (the offloading cache re-allocates its tail mirror)
             plan = getattr(self, "_tail_plan", None)
@@ -443,7 +443,7 @@ class StreamingLLMEvictionCache(Cache):
         self.seq_len = self.start_size + self.recent_size - incoming
 
     def evict_for_spec(self, current_seq_len):
-        if ops.HOST_PLANS and self.k.is_cuda:
+        if self.k.is_cuda:
             plan = getattr(self, "_shift_plan", None)
             if plan is None:
                 plan = self._shift_plan = ops.KvShiftPairPlan(self.k, self.v)

@@ -1090,8 +1090,6 @@ def kv_shift_rows_pair(k_cache, v_cache, src_t0, dst_t0, n):
 # time (profiles/r05a_gap_analysis_decode_steps_inner_graph.txt: 36-108 us in front of each of them under the profiler).  A plan
 # validates its tensors ONCE (what the wrappers above do on every call: device, dtype, shapes, strides, slicing views) and keeps
 # the ctypes arguments; a call then checks its row range with integer arithmetic and goes straight into the library.
-# TRIFORCE_HOST_PLANS=0: the per-call wrappers.
-HOST_PLANS = _os.environ.get("TRIFORCE_HOST_PLANS", "1") != "0"
 
 
 class KvCopyPairPlan:

@@ -20,13 +20,6 @@ from .misc import log_csv, spec_stream
 from .sampling import UniformSource, norm_logits, sample
 
 PAD_TOKEN = 100            # filler id of verify_tokens / pass_tokens (decoding.py:94,177)
-# 0: round 3's host path between a record read and the next launch (ids through pinned staging, separate position / length
-#    launches, input checks on every draft replay) — kept for same-box A/B of DESIGN 13.6; 1 (default): ids as kernel arguments
-#    TRIFORCE_HOST_FAST_MASK selects pieces: 1 ids / positions of Middle_Spec, 2 check-free draft replay, 4 target verify,
-#    8 catch-up draft input, 16 the remaining host -> device token lists (eager / rebuild steps) without an H2D copy
-_HF = __import__("os").environ
-HOST_FAST_MASK = 0 if _HF.get("TRIFORCE_HOST_FAST", "1") == "0" else int(_HF.get("TRIFORCE_HOST_FAST_MASK", "31"))
-HOST_FAST = HOST_FAST_MASK != 0
 
 
 def _sync(device):
@@ -71,30 +64,6 @@ def Autoregressive(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, to
     return n / (time2 - time1)
 
 
-# The host waits for a decision record by polling pinned memory.  A poll loop that never yields can sit on the core a HIP
-# runtime thread needs (launch hand-off, completion signals): measured on 8-vCPU boxes, the hop between an accept kernel
-# and the next launch was 12 us in one process and 61 us in another for the same code (profiles/r04_host_path_ab.txt).
-# TRIFORCE_POLL_YIELD=1: sched_yield() per poll.
-_POLL_YIELD = __import__("os").environ.get("TRIFORCE_POLL_YIELD", "0") == "1"
-# The replay that follows a record read spends 36-69 us INSIDE hipGraphLaunch in the loop (tools/hop_trace.py) against ~9 us
-# from an idle, synchronised queue (tools/draft_launch_latency.py): the runtime retires the completed commands of the
-# 165-node verify graph at its next API call.  TRIFORCE_POLL_QUERY=1: hipStreamQuery every 16th poll, so that the
-# retirement happens while the host waits anyway.
-_POLL_QUERY = __import__("os").environ.get("TRIFORCE_POLL_QUERY", "0") == "1"
-# The record becomes visible a moment BEFORE its kernel completes; a hipGraphLaunch into a stream whose last command is still
-# in flight takes 35-56 us on the host here, into an idle stream ~9 us in all.  TRIFORCE_SYNC_AFTER_RECORD=1: wait for the
-# stream to drain (the kernel is ending anyway) before the replay.
-_SYNC_AFTER_RECORD = __import__("os").environ.get("TRIFORCE_SYNC_AFTER_RECORD", "0") == "1"
-_POLL_QUERY_MASK = int(__import__("os").environ.get("TRIFORCE_POLL_QUERY_EVERY", "16")) - 1
-if (_POLL_QUERY_MASK + 1) & _POLL_QUERY_MASK or _POLL_QUERY_MASK < 0:
-    raise ValueError("TRIFORCE_POLL_QUERY_EVERY must be a power of two (it is used as a mask)")
-_sched_yield = getattr(__import__("os"), "sched_yield", lambda: None)
-
-
-# TRIFORCE_HOP_TRACE=1: (ns from "record seen" to "replay called", ns inside the replay call) per inner hop, for tools
-_HOP_TRACE = [] if __import__("os").environ.get("TRIFORCE_HOP_TRACE", "0") == "1" else None
-
-
 class _Record:
     """A small int64 decision record written by a kernel and read by the host once per (inner / outer) step.
     mailbox=True: the record lives in PINNED HOST memory that the kernel writes directly (unified addressing); the host
@@ -121,13 +90,8 @@ class _Record:
         if not self.mailbox:
             return self.tensor[:k].tolist()
         view, s, spins = self._np[:k], self.SENTINEL, 0
-        query = torch.cuda.current_stream().query if _POLL_QUERY else None
         while (view == s).any():
             spins += 1
-            if query is not None and (spins & _POLL_QUERY_MASK) == 0:
-                query()                # lets the HIP runtime retire finished commands NOW (see _POLL_QUERY)
-            if _POLL_YIELD:
-                _sched_yield()         # let the HIP runtime's own threads run if they share this core (see _POLL_YIELD)
             if spins > 50_000_000:
                 raise RuntimeError("decision record never arrived (kernel failed?)")
         return view.tolist()
@@ -141,10 +105,6 @@ class _Record:
 #  accept kernel); it is also unsound without an explicit acquire at the head of every chain — the runtime knows nothing of an
 #  ordering that goes through host memory.  Removed)
 INNER_GRAPH = __import__("os").environ.get("TRIFORCE_INNER_GRAPH", "1") != "0"
-# With the inner graphs: the outer accept kernel also writes the catch-up draft's pass tokens and the next target verify's
-# positions / slot / key count on the device (tf_accept_chain_step), and the target verify reads its tokens from the shared token
-# buffer — no set-up launch behind either record.  TRIFORCE_STEP_ON_DEVICE=0: the host sets them up (tf_set_tokens).
-STEP_ON_DEVICE = __import__("os").environ.get("TRIFORCE_STEP_ON_DEVICE", "1") != "0"
 
 
 _MAILBOX_OK = {}
@@ -210,7 +170,7 @@ class _SpecBuffers:
         n = len(ids)
         self._flip ^= 1
         row = self.dev_tokens[self._flip, :n]
-        if (HOST_FAST_MASK & 16) and row.is_cuda and n <= 32:
+        if row.is_cuda and n <= 32:
             ops.set_tokens(row, ids, PAD_TOKEN)                # ids as kernel arguments: no staging copy, no H2D copy
             return row.unsqueeze(0)
         stage = self.stage[self._flip, :n]
@@ -252,9 +212,9 @@ def Middle_Spec(next_token, graph_engine, gamma, verbose, tokenizer, rng=None, b
     ids = [int(next_token)]
     vt = buffers.verify_tokens
     # [next, PAD...] and the gamma + 1 positions S, S + 1, ... in one launch (the token id travels as a kernel argument)
-    if (HOST_FAST_MASK & 1) and vt.numel() <= 32 and buffers.positions.numel() <= 64:      # (tf_set_tokens' limits)
+    if vt.numel() <= 32 and buffers.positions.numel() <= 64:      # (tf_set_tokens' limits)
         position_ids = buffers.positions
-        if ops.HOST_PLANS and vt.is_cuda:
+        if vt.is_cuda:
             if buffers.start_plan is None:
                 buffers.start_plan = ops.SetTokensPlan(vt.view(-1), position_ids)
             buffers.start_plan(ids, PAD_TOKEN, pos0=S)
@@ -269,7 +229,7 @@ def Middle_Spec(next_token, graph_engine, gamma, verbose, tokenizer, rng=None, b
     noclone = dict(clone=False) if getattr(graph_engine, "static_outputs", False) else {}
     # the draft / verify graphs read vt itself: replay without looking at the inputs (this call sits between the host's
     # read of the previous accept record and the next launch — the one place where host time is GPU idle time)
-    replay_draft = getattr(graph_engine, "replay_draft", None) if ((HOST_FAST_MASK & 2) and noclone and buffers.shared_inputs) else None
+    replay_draft = getattr(graph_engine, "replay_draft", None) if (noclone and buffers.shared_inputs) else None
     flat = vt.view(-1)
     while inner is not None and n < gamma:
         # one launch, one read: [draft step n, draw, retrieval verify, accept test + follow-up draw] is ONE hipGraph whose
@@ -277,14 +237,8 @@ def Middle_Spec(next_token, graph_engine, gamma, verbose, tokenizer, rng=None, b
         rng.cursor_tensor(3)
         rec = buffers.mid_out
         rec.arm(4)
-        if _HOP_TRACE is not None and drafted:
-            _t_before = time.perf_counter_ns()
         p = inner.replay(n)
-        if _HOP_TRACE is not None and drafted:                                # host pieces of the inner hop (tools/hop_trace.py)
-            _HOP_TRACE.append((_t_before - _t_seen, time.perf_counter_ns() - _t_before))
         acc, b, d, at = rec.read(4)                                           # the one host read of this step
-        if _HOP_TRACE is not None:
-            _t_seen = time.perf_counter_ns()
         rng.advanced_on_device(3, at)
         drafted += 1
         if acc:                                                               # decoding.py:193-209
@@ -302,12 +256,8 @@ def Middle_Spec(next_token, graph_engine, gamma, verbose, tokenizer, rng=None, b
         buffers.rows_generation = graph_engine.verify_generation()
         return ids, p[:len(ids) - 1], accepted / drafted
     while n < gamma:
-        if _HOP_TRACE is not None and drafted:
-            _t_before = time.perf_counter_ns()
         if replay_draft is not None:
             q_d = replay_draft(n)
-            if _HOP_TRACE is not None and drafted:            # host pieces of the inner hop (TRIFORCE_HOP_TRACE=1, tools only)
-                _HOP_TRACE.append((_t_before - _t_seen, time.perf_counter_ns() - _t_before))
         else:
             q_d = graph_engine.graph_draft_inference(input_ids=vt[:, :n + 1], gamma_offset=n, **noclone)
         u = rng.take(3)
@@ -326,10 +276,6 @@ def Middle_Spec(next_token, graph_engine, gamma, verbose, tokenizer, rng=None, b
                 else:
                     flat[n + 1:n + 3].copy_(_mid_tokens(rec.tensor, n, gamma, flat))
         acc, b, d = rec.read(3)                                               # the one host read of this step
-        if _HOP_TRACE is not None:
-            _t_seen = time.perf_counter_ns()                # (the drain below counts as part of the hop)
-        if _SYNC_AFTER_RECORD:
-            torch.cuda.current_stream().synchronize()       # the accept kernel is ending: launch from an IDLE stream (see there)
         if health is not None:                # TP: a timed-out exchange NaN-filled p — stop before its tokens are used
             health()
         rng.advance(3)
@@ -450,6 +396,18 @@ class TriForceRunner:
             spec_stream(self.next_token, self.tokenizer, "cyan")
         self.emitted = [self.next_token]
 
+    def _device_sets(self):
+        """The captured verify graphs' device scalars (``ge.verify_sets``) when this runner sets its steps up on the device, else
+        None.  Then the outer accept kernel (tf_accept_chain_step) writes the catch-up draft's pass tokens and the next verify's
+        positions / slot / key count, and the verify reads its tokens from the shared token buffer, where the inner graphs left
+        [next, t_1 .. t_g2]: the chain behind the last inner record is one graph replay, no set-up launch.  An eager or rebuild
+        step still sets its verify up from the host."""
+        ge = self.ge
+        if self.inner is None or self.sync_record is not None or self.inclusive_accept or self.top_k > 0 \
+                or (self.temperature, self.top_p) != (ge.sampling["temperature"], ge.sampling["top_p"]):
+            return None
+        return ge.verify_sets(self.gamma)
+
     @torch.inference_mode()
     def step(self):
         """One outer iteration: Middle_Spec drafting, target verify over the full KV, device-side
@@ -460,7 +418,7 @@ class TriForceRunner:
         n0 = self.n
         # health (TP): a plain load of the pinned mirror of the exchange's error word after EVERY inner record read — after a
         # timed-out exchange the probabilities are NaN-filled, and without the check up to gamma more iterations would draft,
-        # append draft KV and write token ids from them before the outer step noticed (advisor, round 4)
+        # append draft KV and write token ids from them before the outer step noticed
         ids, spec_rows, acc_mid = Middle_Spec(next_token, ge, gamma, False, tokenizer, rng=rng, buffers=bufs,
                                               sync_record=self.sync_record, health=self.health)
         self.acc_rate_middle_list.append(acc_mid)
@@ -473,26 +431,16 @@ class TriForceRunner:
         rebuild = self.rebuild_every > 0 and (len(self.counts) + 1) % self.rebuild_every == 0
         self.rebuilds += int(rebuild)
         eager = self.eager_every > 0 and (len(self.counts) + 1) % self.eager_every == 0
-        fast = None
-        # STEP_ON_DEVICE (round 5): the verify reads its tokens from the shared token buffer (the inner graphs left all of
-        # [next, t_1 .. t_g2] there) and its positions / slot / key count from device scalars the PREVIOUS step's accept kernel
-        # wrote — the chain behind the last inner record is one graph replay, no set-up launch (tf_accept_chain_step)
-        on_device = None
-        if STEP_ON_DEVICE and self.inner is not None and self.sync_record is None and not self.inclusive_accept and self.top_k <= 0 \
-                and not rebuild and not eager and (self.temperature, self.top_p) == (ge.sampling["temperature"], ge.sampling["top_p"]):
-            on_device = ge.verify_sets(gamma)
-        if on_device is not None:
+        sets = self._device_sets()
+        on_device = sets is not None and not rebuild and not eager
+        if on_device:
             if not ge.verify_lengths_current(gamma):
                 ge.sync_verify_lengths(gamma)                          # stale (first step, after an eager / rebuild step): one launch each
             tg = ge.target_graphs[len(ids)]
             probs, verify_tokens = tg.replay_in_place(), tg.ids
-        elif (HOST_FAST_MASK & 4) and self.top_k <= 0 and not rebuild and not eager and hasattr(ge, "verify_probs_ids") \
-                and len(ids) <= 32:
+        elif self.top_k <= 0 and not rebuild and not eager and hasattr(ge, "verify_probs_ids") and len(ids) <= 32 \
+                and (fast := ge.verify_probs_ids(ids, self.temperature, self.top_p)) is not None:
             # captured forward + temperature / top-p: ids, positions and lengths set by ONE launch (ids as kernel arguments)
-            fast = ge.verify_probs_ids(ids, self.temperature, self.top_p)
-        if on_device is not None:
-            pass
-        elif fast is not None:
             probs, verify_tokens = fast
         else:
             verify_tokens = bufs.to_device(ids)
@@ -509,10 +457,11 @@ class TriForceRunner:
         rec = bufs.chain_out
         rec.arm(4)
         on_cursor = self.inner is not None and self.sync_record is None
-        if on_device is not None:
-            # ... and leaves the pass tokens in the token buffer and the NEXT verify's scalars (rolled-back length) on the device
+        if on_device:
+            # the accept kernel also leaves the pass tokens in the token buffer and the NEXT verify's scalars (rolled-back
+            # length) on the device
             ops.accept_chain_step(probs, spec_rows, ge.tok_buf.view(-1), rng.buf, rng.cursor_tensor(g2 + 1), g2, False, self.eos,
-                                  PAD_TOKEN, ge.target_graphs[len(ids)].slot, on_device, rec.tensor)
+                                  PAD_TOKEN, ge.target_graphs[len(ids)].slot, sets, rec.tensor)
         elif on_cursor:
             # the uniform stream's device cursor is live (the inner-iteration graphs advance it): the chain reads its numbers
             # behind it and advances it by what it consumed, so no step ever has to re-synchronise the device copy
@@ -551,31 +500,30 @@ class TriForceRunner:
         # forward (:137-139) goes FIRST — ~120 us of device work behind which the host issues the tail copies, the window
         # shift and the next iteration's first launches; issued last, each of those short launches was a host-bound gap
         # (profiles/r04_gap_analysis_decode_steps.txt).
+        # The pass tokens go straight into the draft graphs' static input when they fit (the next Middle_Spec re-initialises
+        # it): one launch, no copies.
         tok_buf = getattr(ge, "tok_buf", None)
-        if on_device is not None:
+        in_tok_buf = tok_buf is not None and tok_buf.shape[0] == 1 and tok_buf.shape[1] >= len(pass_tokens) and tok_buf.is_cuda \
+            and len(pass_tokens) <= 32
+        if on_device:
             ge.dev_len = eng.kv_cache.seq_len - (g2 - count)            # what the accept kernel wrote: the rolled-back length
             ge.replay_draft(g2 + 1)                                      # the pass tokens are in the token buffer already
-        elif (HOST_FAST_MASK & 8) and tok_buf is not None and tok_buf.shape[0] == 1 and tok_buf.shape[1] >= len(pass_tokens) \
-                and tok_buf.is_cuda and len(pass_tokens) <= 32:
-            # straight into the draft graphs' static input (the next Middle_Spec re-initialises it): one launch, no copies
-            replay = getattr(ge, "replay_draft", None)
-            if ops.HOST_PLANS and replay is not None and getattr(ge, "static_outputs", False) and tok_buf.numel() <= 32:
-                if bufs.pass_plan is None:
-                    bufs.pass_plan = ops.SetTokensPlan(tok_buf.view(-1))
-                bufs.pass_plan(pass_tokens, PAD_TOKEN, n_dst=len(pass_tokens))
-                replay(g2 + 1)                                            # (the graph reads tok_buf itself: no input checks)
-            else:
-                row = tok_buf[:, :len(pass_tokens)]
-                ops.set_tokens(row, pass_tokens, PAD_TOKEN)
-                ge.graph_draft_inference(input_ids=row, gamma_offset=g2 + 1)
+        elif in_tok_buf and hasattr(ge, "replay_draft") and getattr(ge, "static_outputs", False) and tok_buf.numel() <= 32:
+            if bufs.pass_plan is None:
+                bufs.pass_plan = ops.SetTokensPlan(tok_buf.view(-1))
+            bufs.pass_plan(pass_tokens, PAD_TOKEN, n_dst=len(pass_tokens))
+            ge.replay_draft(g2 + 1)                                       # (the graph reads tok_buf itself: no input checks)
+        elif in_tok_buf:
+            row = tok_buf[:, :len(pass_tokens)]
+            ops.set_tokens(row, pass_tokens, PAD_TOKEN)
+            ge.graph_draft_inference(input_ids=row, gamma_offset=g2 + 1)
         else:
             ge.graph_draft_inference(input_ids=bufs.to_device(pass_tokens), gamma_offset=g2 + 1)
 
         eng.kv_cache.seq_len -= (g2 - count)                              # rollback (:124)
-        if on_device is None and STEP_ON_DEVICE and self.inner is not None and self.sync_record is None and self.top_k <= 0 \
-                and hasattr(ge, "verify_sets") and ge.verify_sets(gamma) is not None:
-            # this step set its verify up from the host (eager / rebuild step, first step): bring the device scalars to the
-            # rolled-back length HERE, behind the catch-up draft forward, not at the head of the next step's verify chain
+        if sets is not None and not on_device:
+            # this step set its verify up from the host (eager / rebuild step): bring the device scalars to the rolled-back
+            # length HERE, behind the catch-up draft forward, not at the head of the next step's verify chain
             ge.sync_verify_lengths(gamma)
         ge.update_graph_cache()                                           # refresh the retrieval tail (:125)
 
@@ -809,8 +757,7 @@ class _DistEngine:
     def static_outputs(self):
         """The captured draft / retrieval-verify forwards can hand out their static output buffers (valid until the same graph
         replays again — what the decode loops need: no 0.9 MB clone and no per-position row copies per inner iteration)."""
-        return getattr(self.llm, "_verify_cap", None) is not None and bool(getattr(self.llm, "_draft_graphs", None)) \
-            and __import__("os").environ.get("TRIFORCE_TP_STATIC_OUTPUTS", "1") != "0"
+        return getattr(self.llm, "_verify_cap", None) is not None and bool(getattr(self.llm, "_draft_graphs", None))
 
     def graph_draft_inference(self, input_ids, gamma_offset=0, clone=True):
         return self.llm.draft_run(input_ids=input_ids, gamma_offset=gamma_offset, clone=clone)   # 0.6/0.9 hard-wired (SURVEY §7)
