@@ -11,7 +11,7 @@ from triforce_amd.models.cache import FlashSimpleCache, RetrievalCache, Streamin
 from triforce_amd.models.modeling_llama import LlamaForCausalLM  # noqa: E402
 from triforce_amd.models.modeling_llama_68m import LlamaForCausalLM as LlamaForCausalLM_68M  # noqa: E402
 from triforce_amd.utils import cli  # noqa: E402
-from triforce_amd.utils.decoding import Autoregressive, TriForce  # noqa: E402
+from triforce_amd.utils.decoding import Autoregressive, TriForce, TriForceSession  # noqa: E402
 from triforce_amd.utils.graph_infer import GraphInferenceEngine  # noqa: E402
 from triforce_amd.utils.misc import colored, print_config  # noqa: E402
 
@@ -20,7 +20,8 @@ DEVICE = "cuda:0"
 
 def build_engine(args, target, draft):
     """Caches sized as on_chip.py:76-80 (16 sink tokens, recent = draft budget - 16 - gamma) and the captured graphs."""
-    full = FlashSimpleCache(target, args.prefill + args.gen_len + 16)
+    # (--followups: a question's rows sit between the document and its answer; 0 by default)
+    full = FlashSimpleCache(target, args.prefill + args.gen_len + 16 + (args.followup_len if args.followups > 0 else 0))
     retrieval = RetrievalCache(target, max_budget=args.budget, prefill=args.prefill, gamma=args.gamma,
                                chunk_size=args.chunk_size)
     streaming = StreamingLLMEvictionCache(draft, start_size=16, recent_size=args.draft_cache_budget - 16 - args.gamma,
@@ -30,6 +31,25 @@ def build_engine(args, target, draft):
     for c in (full, retrieval, streaming):
         c.print_status()
     return engine
+
+
+def followups(args, tokenizer, engine, prompt, vocab_size, sampling):
+    """--followups N: prefill the document once, answer it, then ask N synthetic questions of --followup_len tokens against
+    the same prefilled document (keep = prefill) and print each one's time to first token and decode speed."""
+    import torch
+    if args.followup_len < 1:
+        raise SystemExit("--followups needs --followup_len >= 1")
+    session = TriForceSession(tokenizer, engine, args.gamma, verbose=args.verbose, rebuild_every=args.rebuild_every, **sampling)
+    session.prefill(prompt)
+    first = session.generate(args.gen_len)
+    print(colored(f"[Session] prefill {prompt.shape[1]} tokens: time to first token {first['ttft']:.3f} s, "
+                  f"{first['tokens_per_s']:.2f} tokens/s", "red"))
+    gen = torch.Generator().manual_seed(0)
+    for i in range(args.followups):
+        question = torch.randint(3, vocab_size, (1, args.followup_len), generator=gen).to(prompt.device)
+        st = session.ask(question, args.gen_len, keep=args.prefill)
+        print(colored(f"[Session] follow-up {i + 1}/{args.followups} ({args.followup_len} tokens, keep {args.prefill}): "
+                      f"time to first token {st['ttft']:.3f} s, {st['tokens_per_s']:.2f} tokens/s", "red"))
 
 
 def main():
@@ -66,6 +86,10 @@ def main():
     print(colored(f"average acceptance rate (NOT per token): {cli.mean([acc for acc, _ in results])}", "red"))
     print(colored(f"[TriForce] average latency: {method_latency} ms", "red"))
     print(colored(f"[E2E Speedup]: {baseline_latency / method_latency}", "red"))
+
+    if args.followups > 0:
+        for p in prompts:
+            followups(args, tokenizer, engine, clip(p), target.config.vocab_size, sampling)
 
 
 if __name__ == "__main__":

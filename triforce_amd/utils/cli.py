@@ -58,11 +58,19 @@ SCRIPTS = {
         ("--tree_size", str, "512", "node count, or a grow map file (tree/<n>.pt / .json)"),
     ],
 }
+# ---- flags one script adds beyond its reference command line (SCRIPTS stays the table compared with the reference's) ----
+SCRIPT_OWN = {
+    "on_chip": [
+        ("--followups", int, 0, "after each prompt's generation, ask N synthetic follow-up questions against the same "
+                                "prefilled document (TriForceSession.ask, keep = prefill); 0 = none"),
+        ("--followup_len", int, 0, "tokens per follow-up question"),
+    ],
+}
 
 
 def parse(script, argv=None):
     ap = argparse.ArgumentParser(description=f"args for {script}.py")
-    for name, typ, default, help_ in SCRIPTS[script]:
+    for name, typ, default, help_ in SCRIPTS[script] + SCRIPT_OWN.get(script, []):
         if typ == "flag":
             ap.add_argument(name, action="store_true", help=help_)
         else:

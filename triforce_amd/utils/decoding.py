@@ -362,6 +362,10 @@ class TriForceRunner:
         self.inner_iters = 0          # Middle_Spec iterations = 68M draft calls = retrieval-verify replays
         self.emitted, self.counts, self.acc_rate_middle_list = [], [], []
         self.next_token, self.last_reason = None, None
+        # extend(): the ids of the full cache's rows — ``history`` (1, n) as of the last prefill() / extend(), ``_fed`` the rows
+        # the steps appended since — and, with ``time_extend``, the split of the last extend() in seconds
+        self.history, self._fed = None, []
+        self.time_extend, self.extend_seconds = False, None
 
     @torch.inference_mode()
     def prefill(self, input_ids):
@@ -378,6 +382,101 @@ class TriForceRunner:
             eng.draft_cache.print_status()
         self.calibrate_aligned()
         self.start(logits)
+        self.history, self._fed = input_ids, []
+
+    def _extend_refusal(self):
+        """Why extend() cannot run over this engine (None: it can)."""
+        from ..models.cache import FlashSimpleCache, RetrievalCache
+        from .graph_infer import GraphInferenceEngine
+        if not isinstance(self.ge, GraphInferenceEngine) or self.sync_record is not None or self.inclusive_accept:
+            return (f"extend() is implemented for the single-GPU resident GraphInferenceEngine only, not for "
+                    f"{type(self.ge).__name__} (tensor-parallel loop)")
+        if type(self.eng.kv_cache) is not FlashSimpleCache or type(self.eng.graph_cache) is not RetrievalCache:
+            return (f"extend() is implemented for the resident FlashSimpleCache + RetrievalCache only, not for "
+                    f"{type(self.eng.kv_cache).__name__} + {type(self.eng.graph_cache).__name__}")
+        return None
+
+    @torch.inference_mode()
+    def extend(self, input_ids, keep=None):
+        """Continue from a prefilled runner without touching rows [0, keep) of the full cache.
+
+        keep=None: a chat turn — everything generated so far stays and the rows fed are [pending next_token] + input_ids (the
+        pending token was emitted, its K/V is not in the cache yet).  keep=k: a new question on the same document — the full
+        cache is rolled back to k rows (retrieval.prefill <= k <= seq_len), then input_ids are fed.  All rows but the last go
+        through the engine's prefill (> 64 rows) or verify (2..64 rows) route, one row through the autoregressive step; the
+        last row is fed alone and re-selects the retrieval cache for its query; the draft's StreamingLLM cache is refilled
+        over the whole token history.  Every bound is checked before any state changes (ValueError names the limit)."""
+        eng, ge, gamma = self.eng, self.ge, self.gamma
+        refusal = self._extend_refusal()
+        if refusal is not None:
+            raise NotImplementedError(refusal)
+        kv, rc, dc = eng.kv_cache, eng.graph_cache, eng.draft_cache
+        if self.history is None or self.next_token is None:
+            raise ValueError("extend() continues a prefilled runner: call prefill() first")
+        ids = torch.as_tensor(input_ids, dtype=torch.long, device=self.device).reshape(1, -1)
+        if ids.shape[1] == 0:
+            raise ValueError("extend() needs at least one input token")
+        S, P = kv.seq_len, rc.prefill
+        known = self.history.shape[1] + len(self._fed)
+        if keep is None:
+            k, rows = S, ids.shape[1] + 1
+        else:
+            k, rows = int(keep), ids.shape[1]
+            if not P <= k <= S:
+                raise ValueError(f"keep={k} is outside [{P}, {S}]: the retrieval cache covers rows [0, {P}) and the full "
+                                 f"cache holds {S} rows")
+        if known < k:
+            raise ValueError(f"the runner knows the ids of {known} cache rows, keep needs {k} (the cache length was changed "
+                             "behind the runner)")
+        room = gamma + 2                                   # one decode step's verify block
+        if k + rows - P + room > rc.max_budget:
+            raise ValueError(f"retrieval tail {k} + {rows} - {P} rows + {room} rows for one decode step exceeds the retrieval "
+                             f"budget max_budget={rc.max_budget}: the covered region [0, {P}) is fixed when the engine is built")
+        if k + rows + room > kv.max_budget:
+            raise ValueError(f"{k} + {rows} rows + {room} rows for one decode step exceeds the full cache's capacity "
+                             f"max_budget={kv.max_budget}")
+        if k + rows <= 64:
+            raise ValueError(f"a token history of {k + rows} rows is too short for the draft's prefill route (> 64 rows)")
+
+        # ---- state changes from here ----
+        t = [self._extend_mark()]
+        hist = self.history
+        if self._fed:
+            hist = torch.cat([hist, torch.tensor(self._fed, dtype=torch.long, device=self.device).unsqueeze(0)], dim=1)
+        new = ids if keep is not None else torch.cat([torch.tensor([[self.next_token]], dtype=torch.long, device=self.device),
+                                                      ids], dim=1)
+        hist = torch.cat([hist[:, :k], new], dim=1)
+        kv.seq_len = k                                     # rows [0, k) stay as they are, the rest is overwritten
+        body = new[:, :-1]
+        if body.shape[1] == 1:                             # (q_len == 1 through inference() would build the retrieval cache)
+            ge.decode_step(body)
+        elif body.shape[1] > 1:
+            ge.inference(input_ids=body)
+        t.append(self._extend_mark())
+        logits = ge.inference(input_ids=new[:, -1:], rebuild_retrieval=True)   # selection for THIS query over [0, P) + tail
+        ge.update_graph_cache()                            # (the last layer's tail copy ran before seq_len advanced)
+        t.append(self._extend_mark())
+        dc.reset()
+        dc.seq_len = 0                                     # a clean refill: the window a first prompt of these ids leaves
+        ge.graph_draft_prefill(input_ids=hist)
+        t.append(self._extend_mark())
+        assert kv.seq_len == k + rows == hist.shape[1]
+        self.history, self._fed = hist, []
+        ge.dev_len = None                                  # the verify graphs' device scalars: re-synchronised by the next step
+        self.bufs.rows_generation = None
+        self.resample_count = self.accepted_count = self.target_sample_count = self.draft_count = 0
+        self.n = self.inner_iters = self.rebuilds = 0
+        self.counts, self.acc_rate_middle_list, self.last_reason = [], [], None
+        self.start(logits)                                 # (take + advance: the uniform stream's device cursor is re-written
+        if self.time_extend:                               #  before its next reader)
+            self.extend_seconds = dict(target_feed=t[1] - t[0], retrieval_rebuild=t[2] - t[1], draft_refill=t[3] - t[2],
+                                       rows=rows, keep=k)
+
+    def _extend_mark(self):
+        if not self.time_extend:
+            return 0.0
+        _sync(self.device)
+        return time.time()
 
     def calibrate_aligned(self):
         """Aligned synthetic weights (models/aligned.py) need one calibration of the lm_head's attention read-out once
@@ -493,6 +592,7 @@ class TriForceRunner:
         self.last_reason = reason          # 0 rejection + resample, 1 everything accepted (bonus token), 2 accepted eos
 
         pass_tokens = [next_token] + generated[:count] + [PAD_TOKEN] * (g2 + 1 - count)
+        self._fed += pass_tokens[:count + 1]          # the rows this step leaves in the full cache (extend)
         if reason != 2:
             pass_tokens[count + 1] = pred             # the resampled (:111-118) or the bonus (:127-134) token
 
@@ -595,6 +695,56 @@ def TriForce(tokenizer, graph_engine, input_ids, gamma=4, max_len=256, top_k=-1,
     if return_details:
         return st
     return acceptance_rate, n / (time2 - time1)
+
+
+class TriForceSession:
+    """One long document, several answers: prefill once, then ``ask`` follow-up questions against the same document or
+    take chat ``turn``s, each starting from the KV already on the device (TriForceRunner.extend).
+    Every answer returns the runner's stats plus ``ttft`` — the seconds from the call to the first token of the answer."""
+
+    def __init__(self, tokenizer, graph_engine, gamma=4, top_k=-1, top_p=0.9, temperature=0.6, verbose=False, rng=None,
+                 rebuild_every=0):
+        self.run = TriForceRunner(tokenizer, graph_engine, gamma, top_k, top_p, temperature, verbose, rng,
+                                  rebuild_every=rebuild_every)
+        self.ttft = None
+
+    @property
+    def document(self):
+        """Rows of the full cache that a follow-up question keeps by default: the region the retrieval cache covers."""
+        return self.run.eng.graph_cache.prefill
+
+    def _first_token(self, fn, *a, **kw):
+        device = self.run.device
+        _sync(device)
+        t0 = time.time()
+        fn(*a, **kw)
+        _sync(device)
+        self.ttft = time.time() - t0
+
+    def prefill(self, input_ids):
+        self._first_token(self.run.prefill, input_ids)
+
+    @torch.inference_mode()
+    def generate(self, max_len=256):
+        run = self.run
+        _sync(run.device)
+        t0 = time.time()
+        while run.n < max_len:
+            run.step()
+        _sync(run.device)
+        st = run.stats(time.time() - t0)
+        st["ttft"] = self.ttft
+        return st
+
+    def ask(self, input_ids, max_len=256, keep=None):
+        """A new question on the same document: the cache is rolled back to ``keep`` rows (default: the document)."""
+        self._first_token(self.run.extend, input_ids, keep=self.document if keep is None else keep)
+        return self.generate(max_len)
+
+    def turn(self, input_ids, max_len=256):
+        """A chat turn: everything generated so far stays in the context."""
+        self._first_token(self.run.extend, input_ids, keep=None)
+        return self.generate(max_len)
 
 
 ################### Dist Spec (TP + offloading) ####################
