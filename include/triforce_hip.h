@@ -443,6 +443,21 @@ int tf_sg_workspace(void* ws, int64_t bytes);
  * utils/sampling.py:43-60 (norm_logits with top_k = -1) without the vocabulary sort: threshold search on the
  * fp32 bit pattern + index-ordered tie scan (== a stable descending sort; ties -> lowest token id). */
 int tf_topp_probs(const float* logits, float* probs, int rows, int V, float temperature, float top_p, void* stream);
+/* tf_topk_topp_probs: tf_topp_probs behind the reference's top-k filter (utils/sampling.py:16-19) — the target tier's sampling
+ * with top_k > 0 (first token, target verify, autoregressive baseline), one launch, no vocabulary sort.  Per row:
+ *   x_i = l_i / temperature (IEEE fp32 division, as in tf_topp_probs);
+ *   kth = the min(top_k, V)-th largest x, counted with multiplicity;
+ *   survivors S = { i : x_i >= kth } — EVERY entry tied with the k-th value survives (the reference masks `logits < kth`, it
+ *   does not keep "exactly k"); -0.0 and +0.0 compare equal; a -inf logit is legal (mass 0; it survives only if kth is -inf);
+ *   NaN is outside the contract.
+ * Entries outside S get probability 0 and contribute to no sum.  Over S the result is exactly what tf_topp_probs defines:
+ * e_i = expf(x_i - max), masses as 2^-40 fixed-point integers, tau = floor(top_p * Z) with Z summed over S only, the boundary
+ * by radix select on mass, ties at the boundary kept in index order, outputs e_i / Zk.  top_k >= V filters nothing: the output
+ * is then BIT-IDENTICAL to tf_topp_probs.  kth comes from a radix select on integer COUNT histograms, so nothing depends on the
+ * order in which atomics land.  One workgroup of 1 024 threads per row.
+ * TF_EINVAL: NULL pointer, rows < 1, V < 1, !(temperature > 0), !(top_p > 0), top_k < 1.  TF_ERANGE: V > 32768. */
+int tf_topk_topp_probs(const float* logits, float* probs, int rows, int V, float temperature, int top_k, float top_p,
+                       void* stream);
 int tf_sample_inverse_cdf(const float* probs, const float* u, int64_t* token_out, int V, void* stream);
 int tf_accept_chain(const float* p, const float* q, const int64_t* tokens, const float* uniforms,
                     int g2, int V, int inclusive, int64_t eos_token_id, int64_t* out, void* stream);

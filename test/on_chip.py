@@ -27,7 +27,7 @@ def build_engine(args, target, draft):
     streaming = StreamingLLMEvictionCache(draft, start_size=16, recent_size=args.draft_cache_budget - 16 - args.gamma,
                                           gamma=args.gamma)
     engine = GraphInferenceEngine(target, full, retrieval, draft, streaming)
-    engine.initialize_cuda_graph(args.gamma, probs=True, temperature=args.temp, top_p=args.top_p)
+    engine.initialize_cuda_graph(args.gamma, probs=True, temperature=args.temp, top_p=args.top_p, top_k=args.top_k)
     for c in (full, retrieval, streaming):
         c.print_status()
     return engine
@@ -58,7 +58,7 @@ def main():
     target = cli.load_causal_lm(LlamaForCausalLM, args.weights, args.target, DEVICE)
     draft = cli.load_causal_lm(LlamaForCausalLM_68M, cli.draft_weights(args), "llama-68M", DEVICE)
     tokenizer, prompts = cli.load_prompts(args, target.config.vocab_size)
-    sampling = dict(top_k=-1, top_p=args.top_p, temperature=args.temp)
+    sampling = dict(top_k=args.top_k, top_p=args.top_p, temperature=args.temp)
     print_config(draft, target, args.prefill, args.gen_len, args.gamma, file_path=args.file, method="TriForce",
                  spec_args={"budget": args.budget, "chunk_size": args.chunk_size}, dataset=args.dataset, **sampling)
     engine = build_engine(args, target, draft)

@@ -667,6 +667,8 @@ struct ToppShared {
     unsigned long long zpart[TOPP_THREADS / 64];   // per-wave sums of all masses: Z does not come from the histogram
     unsigned ties;
     int digit;                                     // >= 0 boundary bin, -1 keep everything, -2 boundary below the candidate cut
+    unsigned krem;                                 // top-k select: rank still looked for inside the current prefix
+    int kdigit;                                    //               the bin the last count scan named
 };
 
 __device__ __forceinline__ float block_max_1024(float v, float* sm, int tid) {
@@ -792,12 +794,81 @@ __device__ __forceinline__ void topp_scan(ToppShared* sh, int lane, bool first_r
     }
 }
 
-__global__ __launch_bounds__(TOPP_THREADS) void topp_probs_kernel(const float* __restrict__ logits,
-                                                                  float* __restrict__ probs, int V,
-                                                                  float temperature, float top_p) {
-    // dynamic LDS only (a static block in front would push the 16-byte row accesses off their alignment):
-    // [ row: nslab * 4096 floats | ToppShared ]
-    extern __shared__ __attribute__((aligned(16))) unsigned char topp_smem[];
+// ------------------------------------------------------------------------------------------------
+// Top-k in front of the top-p select (tf_topk_topp_probs; reference utils/sampling.py:16-19: kth = topk(x, min(k, V))[-1],
+// every x < kth masked to -inf — every entry TIED with the k-th value survives).  kth is found by a 3-round radix select
+// (11 + 11 + 10 bits) over an order-preserving 32-bit key of x = l / T, on COUNT histograms in LDS: integers, so the
+// result does not depend on the order in which the atomics land.  The 2 048 count bins live in ToppShared::hist viewed as
+// 32-bit words (the mass histogram is not in use yet, and is left all-zero for it); lane l of the scanning wave owns bins
+// [32 l, 32 l + 32), one pad word per 32 bins keeps the lanes' reads on different banks.
+// ------------------------------------------------------------------------------------------------
+#define TOPK_BINS 2048
+#define TOPK_HB(b) ((b) + ((b) >> 5))
+#define TOPK_WORDS (TOPK_BINS + TOPK_BINS / 32)
+static_assert(TOPK_WORDS <= 2 * (TOPP_BINS + TOPP_BINS / 16), "the count histogram must fit in ToppShared::hist");
+
+// bigger float -> bigger key; -0.0 and +0.0 share one key (they compare equal)
+__device__ __forceinline__ unsigned topk_key(float x) {
+    unsigned b = __float_as_uint(x);
+    if (b == 0x80000000u) b = 0u;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// cnt[digit] += 1 for the active lanes of a wave (wave-uniform call); a wave whose active lanes all name one bin (tie groups,
+// the narrow exponent range of a row of logits) adds its lane count once
+__device__ __forceinline__ void topk_cnt_add(unsigned* cnt, bool active, int digit) {
+    const unsigned long long act = __ballot(active);
+    if (!act) return;
+    const int first = __ffsll((long long)act) - 1;
+    const int dref = __shfl(digit, first, 64);
+    if (__popcll(act) > 8 && __all(!active || digit == dref)) {
+        if ((int)(threadIdx.x & 63) == first) atomicAdd(&cnt[TOPK_HB(dref)], (unsigned)__popcll(act));
+    } else if (active) {
+        atomicAdd(&cnt[TOPK_HB(digit)], 1u);
+    }
+}
+
+// One wavefront scans the count histogram from the top and names the bin d that holds the krem-th largest entry:
+//   above(d) < krem <= above(d) + cnt(d),   above(d) = entries in the bins above d
+// (sh->kdigit = d, sh->krem = krem - above(d): the rank inside the bin).  Clears the bins it read.
+__device__ __forceinline__ void topk_scan(ToppShared* sh, unsigned* cnt, int lane) {
+    unsigned h[32];
+    unsigned tot = 0u;
+#pragma unroll
+    for (int k = 0; k < 32; ++k) {
+        h[k] = cnt[TOPK_HB(32 * lane + k)];
+        cnt[TOPK_HB(32 * lane + k)] = 0u;
+        tot += h[k];
+    }
+    unsigned inc = tot;                                             // inclusive suffix sum over the lanes
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned n = (unsigned)__shfl_down((int)inc, o, 64);
+        if (lane + o < 64) inc += n;
+    }
+    const unsigned krem = sh->krem;
+    unsigned above = inc - tot;
+    int found = -1;
+    unsigned af = 0u;
+#pragma unroll
+    for (int k = 31; k >= 0; --k) {
+        if (found < 0 && above < krem && krem - above <= h[k]) {
+            found = k;
+            af = above;
+        }
+        above += h[k];
+    }
+    if (found >= 0) {                                               // exactly one lane: 1 <= krem <= entries counted
+        sh->kdigit = 32 * lane + found;
+        sh->krem = krem - af;
+    }
+}
+
+// TOPK = false: tf_topp_probs.  TOPK = true: tf_topk_topp_probs — the same select over the survivors of the top-k filter.
+template <bool TOPK>
+__device__ __forceinline__ void topp_probs_body(unsigned char* topp_smem, const float* __restrict__ logits,
+                                                float* __restrict__ probs, int V, float temperature, int top_k,
+                                                float top_p) {
     const int nslab = (V + 4095) >> 12;
     float* rowe = reinterpret_cast<float*>(topp_smem);
     ToppShared* sh = reinterpret_cast<ToppShared*>(topp_smem + (size_t)nslab * 4096 * sizeof(float));
@@ -839,9 +910,43 @@ __global__ __launch_bounds__(TOPP_THREADS) void topp_probs_kernel(const float* _
         }
         __builtin_amdgcn_sched_barrier(0);                                // interleaving 32 IEEE divisions spills
     }
-    sh->hist[TOPP_HB(tid)] = 0ull;
+    if (TOPK) {
+        unsigned* w = reinterpret_cast<unsigned*>(sh->hist);           // every word: the count histogram uses the pad slots too
+        for (int i = tid; i < 2 * (TOPP_BINS + TOPP_BINS / 16); i += TOPP_THREADS) w[i] = 0u;
+        if (tid == 0) sh->krem = (unsigned)top_k;                       // 1 <= top_k < V (the host routes top_k >= V to TOPK = false)
+    } else {
+        sh->hist[TOPP_HB(tid)] = 0ull;
+    }
     sh->cnt[TOPP_HB(tid)] = 0u;
     mx = block_max_1024(mx, sh->red, tid);
+
+    // ---- top-k: the key of the top_k-th largest x (with multiplicity); survivors are the entries with key >= kthkey ----
+    unsigned kthkey = 0u;
+    if (TOPK) {
+        unsigned* kc = reinterpret_cast<unsigned*>(sh->hist);
+        unsigned pre = 0u;
+#pragma unroll 1
+        for (int r = 0; r < 3; ++r) {
+            const int shift = r == 0 ? 21 : (r == 1 ? 10 : 0);          // digits: bits 31..21, 20..10, 9..0
+            const unsigned dmask = r == 2 ? 1023u : 2047u;
+#pragma unroll 1
+            for (int s = 0; s < nslab; ++s) {
+                const f32x4 x = mine[1024 * s];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const unsigned key = topk_key(x[j]);
+                    // entries past V count nowhere (their -inf would otherwise compete with a real -inf logit)
+                    const bool in = 4096 * s + 4 * tid + j < V && (r == 0 || (key >> (shift + (r == 1 ? 11 : 10))) == pre);
+                    topk_cnt_add(kc, in, (int)((key >> shift) & dmask));
+                }
+            }
+            __syncthreads();
+            if (wave == 0) topk_scan(sh, kc, lane);
+            __syncthreads();
+            pre = (pre << (r == 2 ? 10 : 11)) | (unsigned)sh->kdigit;
+        }
+        kthkey = pre;
+    }
 
     // ---- round 1: e = exp(x - max) back to LDS; mass histogram over bits 29..20 of the CANDIDATES ----
     // Z is summed in registers from every entry; the histogram (LDS atomics) only takes entries >= cut, with
@@ -857,7 +962,10 @@ __global__ __launch_bounds__(TOPP_THREADS) void topp_probs_kernel(const float* _
     for (int s = 0; s < nslab; ++s) {
         f32x4 x = mine[1024 * s];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) x[j] = expf(x[j] - mx);
+        for (int j = 0; j < 4; ++j) {
+            const bool out = TOPK && topk_key(x[j]) < kthkey;          // below the k-th value: zero mass from here on
+            x[j] = out ? 0.f : expf(x[j] - mx);
+        }
         mine[1024 * s] = x;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -1013,6 +1121,22 @@ __global__ __launch_bounds__(TOPP_THREADS) void topp_probs_kernel(const float* _
     }
 }
 
+__global__ __launch_bounds__(TOPP_THREADS) void topp_probs_kernel(const float* __restrict__ logits,
+                                                                  float* __restrict__ probs, int V,
+                                                                  float temperature, float top_p) {
+    // dynamic LDS only (a static block in front would push the 16-byte row accesses off their alignment):
+    // [ row: nslab * 4096 floats | ToppShared ]
+    extern __shared__ __attribute__((aligned(16))) unsigned char topp_smem[];
+    topp_probs_body<false>(topp_smem, logits, probs, V, temperature, 0, top_p);
+}
+
+__global__ __launch_bounds__(TOPP_THREADS) void topk_topp_probs_kernel(const float* __restrict__ logits,
+                                                                       float* __restrict__ probs, int V,
+                                                                       float temperature, int top_k, float top_p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char topp_smem[];
+    topp_probs_body<true>(topp_smem, logits, probs, V, temperature, top_k, top_p);
+}
+
 static size_t topp_lds_bytes(int V) { return (size_t)((V + 4095) >> 12) * 4096 * sizeof(float) + sizeof(ToppShared); }
 
 extern "C" int tf_topp_probs(const float* logits, float* probs, int rows, int V, float temperature, float top_p,
@@ -1028,6 +1152,28 @@ extern "C" int tf_topp_probs(const float* logits, float* probs, int rows, int V,
     }
     hipLaunchKernelGGL(topp_probs_kernel, dim3(rows), dim3(TOPP_THREADS), topp_lds_bytes(V), (hipStream_t)stream, logits,
                        probs, V, temperature, top_p);
+    TF_LAUNCH_CHECK();
+    return TF_OK;
+}
+
+// Temperature + top-k + top-p + softmax (include/triforce_hip.h has the contract).  top_k >= V filters nothing: that call IS
+// tf_topp_probs, so its output is bit-identical by construction.
+extern "C" int tf_topk_topp_probs(const float* logits, float* probs, int rows, int V, float temperature, int top_k,
+                                  float top_p, void* stream) {
+    if (!logits || !probs || rows < 1 || V < 1 || !(temperature > 0.f) || !(top_p > 0.f) || top_k < 1) return TF_EINVAL;
+    if (V > TOPP_THREADS * TOPP_EPT) return TF_ERANGE;
+    if (top_k >= V) return tf_topp_probs(logits, probs, rows, V, temperature, top_p, stream);
+    static bool attr_set[64] = {};                    // the dynamic-LDS opt-in, once per device
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return TF_EINVAL;
+    if (!attr_set[dev]) {
+        hipError_t e = hipFuncSetAttribute((const void*)topk_topp_probs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)topp_lds_bytes(TOPP_THREADS * TOPP_EPT));
+        if (e != hipSuccess) return (int)e;
+        attr_set[dev] = true;
+    }
+    hipLaunchKernelGGL(topk_topp_probs_kernel, dim3(rows), dim3(TOPP_THREADS), topp_lds_bytes(V), (hipStream_t)stream, logits,
+                       probs, V, temperature, top_k, top_p);
     TF_LAUNCH_CHECK();
     return TF_OK;
 }

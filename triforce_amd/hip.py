@@ -75,6 +75,7 @@ SIGNATURES = {
     "tf_kv_dequant_rows_pair": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i32, _i32,
                                        _i32, _i32, _i32, _i32, _vp]),
     "tf_topp_probs": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _vp]),
+    "tf_topk_topp_probs": (_i32, [_vp, _vp, _i32, _i32, _f32, _i32, _f32, _vp]),
     "tf_sample_inverse_cdf": (_i32, [_vp, _vp, _vp, _i32, _vp]),
     "tf_accept_chain": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp]),
     "tf_middle_accept": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),

@@ -1255,6 +1255,18 @@ def topp_probs(logits, temperature, top_p, panel_max=None):
     return probs
 
 
+def topk_topp_probs(logits, temperature, top_k, top_p):
+    """softmax(top_p_filter(top_k_filter(logits / temperature))) for (rows, V) fp32 logits, V <= 32768, top_k >= 1 — one fused
+    kernel, one workgroup per row (tf_topk_topp_probs): every entry tied with the k-th value survives the top-k filter, the
+    rest is tf_topp_probs over the survivors; top_k >= V is tf_topp_probs bit for bit."""
+    _dev(logits)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()
+    probs = torch.empty_like(logits)
+    hip.check(hip.lib().tf_topk_topp_probs(_ptr(logits), _ptr(probs), logits.shape[0], logits.shape[1], float(temperature),
+                                           int(top_k), float(top_p), _stream()), "tf_topk_topp_probs")
+    return probs
+
+
 def sample_inverse_cdf(probs, u, token_out):
     """token_out[0] <- first index with inclusive cumsum(probs) > u[0]*sum(probs).  All device tensors."""
     _dev(probs, u)

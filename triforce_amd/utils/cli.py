@@ -64,6 +64,8 @@ SCRIPT_OWN = {
         ("--followups", int, 0, "after each prompt's generation, ask N synthetic follow-up questions against the same "
                                 "prefilled document (TriForceSession.ask, keep = prefill); 0 = none"),
         ("--followup_len", int, 0, "tokens per follow-up question"),
+        ("--top_k", int, -1, "top-k of the TARGET's sampling (first token, target verify, autoregressive baseline), as in the "
+                             "reference; the two draft tiers never filter by top-k; -1 = off"),
     ],
 }
 

@@ -502,10 +502,22 @@ class TriForceRunner:
         [next, t_1 .. t_g2]: the chain behind the last inner record is one graph replay, no set-up launch.  An eager or rebuild
         step still sets its verify up from the host."""
         ge = self.ge
-        if self.inner is None or self.sync_record is not None or self.inclusive_accept or self.top_k > 0 \
+        if self.inner is None or self.sync_record is not None or self.inclusive_accept or not self._captured_top_k() \
                 or (self.temperature, self.top_p) != (ge.sampling["temperature"], ge.sampling["top_p"]):
             return None
         return ge.verify_sets(self.gamma)
+
+    def _captured_top_k(self):
+        """The engine's captured target verify applies THIS runner's top-k, so its probabilities may be used.  An engine that
+        has no ``top_k`` (tensor-parallel, Sequoia) captured without one: only a runner without top-k takes its fast routes."""
+        captured = getattr(self.ge, "top_k", None)
+        if captured is None:
+            return self.top_k <= 0
+        return (captured if captured > 0 else -1) == (self.top_k if self.top_k > 0 else -1)
+
+    def _top_k_kw(self):
+        """``top_k`` for the verify entry points of an engine that takes one."""
+        return {} if getattr(self.ge, "top_k", None) is None else dict(top_k=self.top_k)
 
     @torch.inference_mode()
     def step(self):
@@ -537,14 +549,15 @@ class TriForceRunner:
                 ge.sync_verify_lengths(gamma)                          # stale (first step, after an eager / rebuild step): one launch each
             tg = ge.target_graphs[len(ids)]
             probs, verify_tokens = tg.replay_in_place(), tg.ids
-        elif self.top_k <= 0 and not rebuild and not eager and hasattr(ge, "verify_probs_ids") and len(ids) <= 32 \
-                and (fast := ge.verify_probs_ids(ids, self.temperature, self.top_p)) is not None:
+        elif self._captured_top_k() and not rebuild and not eager and hasattr(ge, "verify_probs_ids") and len(ids) <= 32 \
+                and (fast := ge.verify_probs_ids(ids, self.temperature, self.top_p, **self._top_k_kw())) is not None:
             # captured forward + temperature / top-p: ids, positions and lengths set by ONE launch (ids as kernel arguments)
             probs, verify_tokens = fast
         else:
             verify_tokens = bufs.to_device(ids)
-            if self.top_k <= 0 and hasattr(ge, "verify_probs"):      # one hipGraph: forward + temperature / top-p
-                probs = ge.verify_probs(verify_tokens, self.temperature, self.top_p, rebuild_retrieval=rebuild, eager=eager)
+            if self._captured_top_k() and hasattr(ge, "verify_probs"):      # one hipGraph: forward + temperature / top-k / top-p
+                probs = ge.verify_probs(verify_tokens, self.temperature, self.top_p, rebuild_retrieval=rebuild, eager=eager,
+                                        **self._top_k_kw())
             else:
                 logits = ge.inference(input_ids=verify_tokens, rebuild_retrieval=True) if rebuild \
                     else (ge.inference(input_ids=verify_tokens, eager=True) if eager else ge.inference(input_ids=verify_tokens))

@@ -34,6 +34,9 @@ def norm_logits(logits: torch.Tensor, temperature=0.6, top_k=-1, top_p=0.9) -> t
     if logits.is_cuda and top_k <= 0 and 0.0 < top_p and logits.shape[-1] <= ops.TOPP_MAX_VOCAB \
             and logits.dtype == torch.float32:
         return ops.topp_probs(logits.contiguous(), temperature, top_p)      # fused HIP kernel, no vocabulary sort
+    if logits.is_cuda and top_k > 0 and 0.0 < top_p and logits.shape[-1] <= ops.TOPP_MAX_VOCAB \
+            and logits.dtype == torch.float32:
+        return ops.topk_topp_probs(logits.contiguous(), temperature, top_k, top_p)   # the same kernel behind a top-k select
     logits = logits / temperature
     logits = top_k_top_p_filter(logits, top_k=top_k, top_p=top_p)
     return F.softmax(logits, dim=-1)
