@@ -210,6 +210,25 @@ int tf_retrieval_gather(const void* k_src, const void* v_src, int64_t src_stride
                         int64_t dst_stride_h, int sets, int chunk, int H, int D, void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * Chunk-mean index (opt-in: RetrievalCache(index=True) / TRIFORCE_RETRIEVAL_INDEX=1).  One layer of
+ * the index is [H][Cmax][D] fp16, head h at index_layer + h * index_stride_h (elements, a multiple
+ * of 8, >= the chunks addressed * D).
+ * tf_chunk_mean              : for every head and chunk c in [c0, c1):
+ *                              index[h][c][d] = fp16( (sum_r float(K[c*chunk + r][h][d])) * (1.0f / chunk) ),
+ *                              the sum in fp32 in row order - the mean tf_retrieval_score forms.
+ *                              Chunks outside [c0, c1) are not written; c1 == c0 launches nothing.
+ * tf_retrieval_score_indexed : scores[h][c] = fp16( q[h] . index[h][c] ), c < C, with the dot product
+ *                              formed as tf_retrieval_score forms it behind its mean: BIT-IDENTICAL to
+ *                              tf_retrieval_score over the K the index was built from.
+ * D is 64 or 128.  TF_EINVAL (before anything launches) for NULL pointers, c0 < 0, c1 < c0,
+ * chunk < 1, C < 1, H < 1, another D, or a stride that breaks the rule above.
+ * ------------------------------------------------------------------------------------------- */
+int tf_chunk_mean(const void* k, int64_t stride_t, int64_t stride_h, void* index_layer, int64_t index_stride_h,
+                  int c0, int c1, int chunk, int H, int D, void* stream);
+int tf_retrieval_score_indexed(const void* index_layer, int64_t index_stride_h, const void* q, void* scores,
+                               int C, int H, int D, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * KV row movement.
  * tf_kv_copy_rows : dst[l][h][dst_t0+i] = src[l][h][src_t0+i], i<n, for L layers x H heads of
  *                   D elements — RetrievalCache.update_graph_cache (cache.py:180-182, :566-575).

@@ -20,7 +20,8 @@ DEVICE = "cuda:0"
 
 def build_engine(args, target, draft):
     """Caches sized as on_chip.py:76-80 (16 sink tokens, recent = draft budget - 16 - gamma) and the captured graphs."""
-    # (--followups: a question's rows sit between the document and its answer; 0 by default)
+    # (--followups: a question's rows sit between the document and its answer; 0 by default.  --reanchor_at: the answer may
+    #  be longer than the retrieval budget, its rows are the gen_len rows the full cache has room for either way)
     full = FlashSimpleCache(target, args.prefill + args.gen_len + 16 + (args.followup_len if args.followups > 0 else 0))
     retrieval = RetrievalCache(target, max_budget=args.budget, prefill=args.prefill, gamma=args.gamma,
                                chunk_size=args.chunk_size)
@@ -39,7 +40,8 @@ def followups(args, tokenizer, engine, prompt, vocab_size, sampling):
     import torch
     if args.followup_len < 1:
         raise SystemExit("--followups needs --followup_len >= 1")
-    session = TriForceSession(tokenizer, engine, args.gamma, verbose=args.verbose, rebuild_every=args.rebuild_every, **sampling)
+    session = TriForceSession(tokenizer, engine, args.gamma, verbose=args.verbose, rebuild_every=args.rebuild_every,
+                              reanchor_at=args.reanchor_at, **sampling)
     session.prefill(prompt)
     first = session.generate(args.gen_len)
     print(colored(f"[Session] prefill {prompt.shape[1]} tokens: time to first token {first['ttft']:.3f} s, "
@@ -78,7 +80,7 @@ def main():
     spec_args = {"budget": args.budget, "draft": args.draft, "chunk_size": args.chunk_size, "gamma": args.gamma,
                  "temperature": args.temp, "top_p": args.top_p, "baseline": baseline_latency / 1000}
     run = dict(gamma=args.gamma, max_len=args.gen_len, verbose=args.verbose, dataset=args.dataset, spec_args=spec_args,
-               rebuild_every=args.rebuild_every, **sampling)
+               rebuild_every=args.rebuild_every, reanchor_at=args.reanchor_at, **sampling)
     for _ in range(3):
         TriForce(tokenizer, engine, clip(prompts[0]), **run)
     results = [TriForce(tokenizer, engine, clip(p), file_path=args.file, **run) for p in prompts]

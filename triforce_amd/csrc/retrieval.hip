@@ -56,6 +56,80 @@ __global__ __launch_bounds__(256) void retrieval_score_kernel(const h16* __restr
     }
 }
 
+// ---- chunk-mean index (opt-in: RetrievalCache(index=True)) ----------------
+// The scorer above spends its time re-reading K for means that never change.  The index keeps them: index[h][c][d] =
+// fp16(mean of chunk c), written once per chunk by chunk_mean_kernel and extended as the covered region grows, so a
+// rebuild scores from chunk-size times fewer bytes.  Both kernels keep retrieval_score_kernel's lane ownership (lane li
+// of a group owns d = 8 li .. 8 li + 7), its row-order fp32 sum, its fmaf element order and its xor-shuffle reduction:
+// index + indexed score is bit-identical to the one-pass scorer over the same K.
+template <int D>
+__global__ __launch_bounds__(256) void chunk_mean_kernel(const h16* __restrict__ k, int64_t stride_t, int64_t stride_h,
+                                                         h16* __restrict__ index, int64_t index_stride_h, int c0, int c1,
+                                                         int chunk) {
+    static_assert(D == 128 || D == 64, "head_dim");
+    constexpr int LPR = D / 8;
+    constexpr int GPB = 256 / LPR;
+    const int h = blockIdx.y;
+    const int grp = threadIdx.x / LPR, li = threadIdx.x % LPR;
+    const h16* kb = k + (int64_t)h * stride_h + 8 * li;
+    h16* ib = index + (int64_t)h * index_stride_h + 8 * li;
+    const float inv = 1.0f / (float)chunk;
+    for (int c = c0 + blockIdx.x * GPB + grp; c < c1; c += gridDim.x * GPB) {
+        float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        const h16* kp = kb + (int64_t)c * chunk * stride_t;
+        for (int r = 0; r < chunk; ++r) {          // sequential fp32 accumulation over the chunk rows
+            const half8 kv = load_half8_stream(kp + (int64_t)r * stride_t);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] += (float)kv[e];
+        }
+        half8 mean;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) mean[e] = (h16)(acc[e] * inv);
+        store_half8(ib + (int64_t)c * D, mean);
+    }
+}
+
+// Four chunks per group and trip: their loads are issued together (one 16-byte load per lane and chunk is all the memory
+// work there is, so the loop is latency-bound otherwise); each chunk's arithmetic is the scorer's.
+template <int D>
+__global__ __launch_bounds__(256) void retrieval_score_indexed_kernel(const h16* __restrict__ index,
+                                                                      int64_t index_stride_h, const h16* __restrict__ q,
+                                                                      h16* __restrict__ scores, int C) {
+    static_assert(D == 128 || D == 64, "head_dim");
+    constexpr int LPR = D / 8;
+    constexpr int GPB = 256 / LPR;
+    constexpr int U = 4;
+    const int h = blockIdx.y;
+    const int grp = threadIdx.x / LPR, li = threadIdx.x % LPR;
+    const h16* ib = index + (int64_t)h * index_stride_h + 8 * li;
+    float qf[8];
+    {
+        const half8 qv = load_half8(q + (int64_t)h * D + 8 * li);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) qf[e] = (float)qv[e];
+    }
+    const int step = gridDim.x * GPB;
+    for (int c = blockIdx.x * GPB + grp; c < C; c += U * step) {
+        half8 m[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int cu = c + u * step;
+            if (cu < C) m[u] = load_half8_stream(ib + (int64_t)cu * D);
+            else m[u] = half8{0, 0, 0, 0, 0, 0, 0, 0};
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            float dot = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) dot = fmaf(qf[e], (float)m[u][e], dot);
+#pragma unroll
+            for (int o = LPR / 2; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
+            const int cu = c + u * step;
+            if (li == 0 && cu < C) scores[(int64_t)h * C + cu] = (h16)dot;
+        }
+    }
+}
+
 // ---- per-head top-k: full bitonic sort of (score, chunk) keys in LDS ------------------------
 __device__ __forceinline__ uint32_t sortable_fp16(uint32_t b) {
     return (b & 0x8000u) ? ((~b) & 0xFFFFu) : (b | 0x8000u);
@@ -259,6 +333,48 @@ extern "C" int tf_retrieval_score(const void* k, int64_t stride_t, int64_t strid
                            stride_h, (const h16*)q, (h16*)scores, C, chunk);
     else
         return TF_EINVAL;
+    TF_LAUNCH_CHECK();
+    return TF_OK;
+}
+
+// workgroups along x for n chunk groups of work at H heads: the scorer's rule, 8 resident workgroups per CU and not one more
+static int chunk_grid_x(int n, int H, int D) {
+    const int gpb = 256 / (D / 8);
+    int gx = (n + gpb - 1) / gpb;
+    const int cap = H <= 2048 ? 2048 / H : 1;
+    if (gx > cap) gx = cap;
+    return gx < 1 ? 1 : gx;
+}
+
+extern "C" int tf_chunk_mean(const void* k, int64_t stride_t, int64_t stride_h, void* index_layer, int64_t index_stride_h,
+                             int c0, int c1, int chunk, int H, int D, void* stream) {
+    if (!k || !index_layer || c0 < 0 || c1 < c0 || chunk < 1 || H < 1 || (D != 128 && D != 64)) return TF_EINVAL;
+    if ((stride_t % 8) || (stride_h % 8) || (index_stride_h % 8) || index_stride_h < (int64_t)c1 * D) return TF_EINVAL;
+    if (c1 == c0) return TF_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(chunk_grid_x(c1 - c0, H, D), H);
+    if (D == 128)
+        hipLaunchKernelGGL((chunk_mean_kernel<128>), grid, dim3(256), 0, st, (const h16*)k, stride_t, stride_h,
+                           (h16*)index_layer, index_stride_h, c0, c1, chunk);
+    else
+        hipLaunchKernelGGL((chunk_mean_kernel<64>), grid, dim3(256), 0, st, (const h16*)k, stride_t, stride_h,
+                           (h16*)index_layer, index_stride_h, c0, c1, chunk);
+    TF_LAUNCH_CHECK();
+    return TF_OK;
+}
+
+extern "C" int tf_retrieval_score_indexed(const void* index_layer, int64_t index_stride_h, const void* q, void* scores,
+                                          int C, int H, int D, void* stream) {
+    if (!index_layer || !q || !scores || C < 1 || H < 1 || (D != 128 && D != 64)) return TF_EINVAL;
+    if ((index_stride_h % 8) || index_stride_h < (int64_t)C * D) return TF_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(chunk_grid_x(C, H, D), H);
+    if (D == 128)
+        hipLaunchKernelGGL((retrieval_score_indexed_kernel<128>), grid, dim3(256), 0, st, (const h16*)index_layer,
+                           index_stride_h, (const h16*)q, (h16*)scores, C);
+    else
+        hipLaunchKernelGGL((retrieval_score_indexed_kernel<64>), grid, dim3(256), 0, st, (const h16*)index_layer,
+                           index_stride_h, (const h16*)q, (h16*)scores, C);
     TF_LAUNCH_CHECK();
     return TF_OK;
 }

@@ -36,6 +36,22 @@ def kv_cache_dtype(override=None):
     return v
 
 
+# TRIFORCE_RETRIEVAL_INDEX=1: RetrievalCache keeps the fp16 chunk means of the covered region (csrc/retrieval.hip "chunk-mean
+# index"): a rebuild scores from them instead of re-reading K.  Off by default: nothing is allocated.
+RETRIEVAL_INDEX_ENV = "TRIFORCE_RETRIEVAL_INDEX"
+TOPK_MAX_CHUNKS = 32768                               # tf_retrieval_topk's limit on the chunk count
+
+
+def retrieval_index(override=None):
+    """Whether RetrievalCache keeps a chunk-mean index: ``override`` if given, else TRIFORCE_RETRIEVAL_INDEX."""
+    if override is not None:
+        return bool(override)
+    v = os.environ.get(RETRIEVAL_INDEX_ENV, "0").strip().lower() or "0"
+    if v not in ("0", "1"):
+        raise ValueError(f"{RETRIEVAL_INDEX_ENV}={v!r}: expected 0 or 1")
+    return v == "1"
+
+
 def _refuse_fp8(what):
     if kv_cache_dtype() == "fp8":
         raise NotImplementedError(f"{KV_CACHE_ENV}=fp8 is implemented for the single-GPU resident cache (FlashSimpleCache) "
@@ -291,11 +307,16 @@ class OffloadingFlashSimpleCache(Cache):
 
 
 class RetrievalCache(Cache):
-    """Per-head retrieval cache (reference cache.py:117-198): chunk-mean scoring, top-k, gather."""
+    """Per-head retrieval cache (reference cache.py:117-198): chunk-mean scoring, top-k, gather.
 
-    def __init__(self, model, max_budget=1024, prefill=1024, chunk_size=8, gamma=6) -> None:
+    ``prefill`` — the rows [0, prefill) the selection covers — can be moved after construction with ``reanchor``
+    (``prefill0`` keeps the constructor's value).  ``index`` (None: TRIFORCE_RETRIEVAL_INDEX) keeps the chunk means of the
+    covered region in ``index`` [L][H][Cmax][D] fp16, Cmax = the full cache's capacity // chunk_size, allocated at the first
+    build; ``indexed_chunks[layer]`` chunks of it are valid, and a build computes only the missing ones."""
+
+    def __init__(self, model, max_budget=1024, prefill=1024, chunk_size=8, gamma=6, index=None) -> None:
         self.chunk_size = chunk_size
-        self.prefill = prefill
+        self.prefill = self.prefill0 = prefill
         self.chunks = prefill // self.chunk_size
         self.select_sets = max_budget // self.chunk_size
         self.gamma = gamma
@@ -311,6 +332,33 @@ class RetrievalCache(Cache):
         self.init_graph = False
         self.last_scores = [None] * self.layers      # (H,C) fp16 / (H,sets) int32 of the last build, for parity checks
         self.last_idx = [None] * self.layers
+        self.use_index = retrieval_index(index)
+        self.index, self.indexed_chunks = None, [0] * self.layers
+
+    def reanchor(self, new_prefill):
+        """Move the covered region to rows [0, new_prefill): the tail then starts there.  Moves no data — the caller follows
+        it with a rebuild (a forward with ``rebuild_retrieval=True``) and the tail copy.  Growing and shrinking are both
+        legal; shrinking forgets the chunk means above the new bound (those rows are about to be rewritten)."""
+        new_prefill, c = int(new_prefill), self.chunk_size
+        if new_prefill % c:
+            raise ValueError(f"new_prefill={new_prefill} is not a multiple of chunk_size={c}")
+        if new_prefill < self.prefill0:
+            raise ValueError(f"new_prefill={new_prefill} is below prefill0={self.prefill0}, the region the cache was built over")
+        if new_prefill // c > TOPK_MAX_CHUNKS:
+            raise ValueError(f"new_prefill={new_prefill} is {new_prefill // c} chunks of {c} rows, more than the top-k's limit "
+                             f"of {TOPK_MAX_CHUNKS} chunks")
+        self.prefill, self.chunks = new_prefill, new_prefill // c
+        self._tail_plan = None                       # (it holds the tail's first row)
+        self.indexed_chunks = [min(n, self.chunks) for n in self.indexed_chunks]
+
+    def _index_layer(self, kv_cache, layer_idx):
+        """This layer's (H, Cmax, D) view of the chunk-mean index over ``kv_cache``, allocated at the first use."""
+        cmax = kv_cache.max_budget // self.chunk_size
+        key = (id(kv_cache), cmax)
+        if self.index is None or self._index_key != key:
+            self.index = torch.zeros(self.layers, self.num_heads, cmax, self.head_dim, dtype=torch.float16, device=self.device)
+            self._index_key, self.indexed_chunks = key, [0] * self.layers
+        return self.index[layer_idx]
 
     def print_status(self):
         print("[Retrieval Cache] Budget:", self.max_budget, " | PreFill:", self.prefill, " | Chunk Size:", self.chunk_size,
@@ -330,7 +378,15 @@ class RetrievalCache(Cache):
             src_k, src_v = kv_cache.scratch_layer(layer_idx, self.prefill)
         else:
             src_k, src_v = kv_cache.layer_kv(layer_idx)
-        scores = ops.retrieval_score(src_k, q[0].contiguous(), self.chunks, self.chunk_size)
+        if self.use_index:                            # means of the chunks not yet indexed, then the scores from the index
+            index = self._index_layer(kv_cache, layer_idx)
+            done = self.indexed_chunks[layer_idx]
+            if done < self.chunks:
+                ops.chunk_mean(src_k, index, done, self.chunks, self.chunk_size)
+                self.indexed_chunks[layer_idx] = self.chunks
+            scores = ops.retrieval_score_indexed(index, q[0].contiguous(), self.chunks)
+        else:
+            scores = ops.retrieval_score(src_k, q[0].contiguous(), self.chunks, self.chunk_size)
         idx = ops.retrieval_topk(scores, self.select_sets)
         ops.retrieval_gather(src_k, src_v, idx, self.k[layer_idx], self.v[layer_idx], self.chunk_size)
         self.last_scores[layer_idx], self.last_idx[layer_idx] = scores, idx
@@ -375,6 +431,9 @@ class RetrievalCache(Cache):
     def reset(self):
         self.k.zero_()
         self.v.zero_()
+        if self.prefill != self.prefill0:            # a new prompt: the region the cache was built over, no chunk mean valid
+            self.reanchor(self.prefill0)
+        self.indexed_chunks = [0] * self.layers
 
 
 class StreamingLLMEvictionCache(Cache):

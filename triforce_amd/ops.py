@@ -989,6 +989,40 @@ def retrieval_score(k_layer, q, chunks, chunk):
     return scores
 
 
+def _index_layer(index_layer, H, D):
+    assert index_layer.dim() == 3 and index_layer.shape[0] == H and index_layer.shape[2] == D and index_layer.dtype == _HALF \
+        and index_layer.stride(2) == 1 and index_layer.stride(1) == D, "(H, Cmax, D) fp16 index layer expected"
+    return index_layer.stride(0)
+
+
+def chunk_mean(k_layer, index_layer, c0, c1, chunk):
+    """index_layer[h, c] = fp16 mean of rows [c * chunk, (c + 1) * chunk) of k_layer[h] for c in [c0, c1): the chunk means
+    retrieval_score forms, kept (the chunk-mean index).  Other chunks are not written."""
+    _dev(k_layer, index_layer)
+    H, T, D = k_layer.shape
+    st, sh = _kv(k_layer)
+    ish = _index_layer(index_layer, H, D)
+    if not 0 <= c0 <= c1 or c1 > index_layer.shape[1] or c1 * chunk > T:
+        raise IndexError(f"chunk_mean: chunks [{c0}, {c1}) of {chunk} rows leave the {index_layer.shape[1]}-chunk index or "
+                         f"the {T}-row cache (the kernel does not bounds-check)")
+    hip.check(hip.lib().tf_chunk_mean(_ptr(k_layer), st, sh, _ptr(index_layer), ish, int(c0), int(c1), int(chunk), H, D,
+                                      _stream()), "tf_chunk_mean")
+
+
+def retrieval_score_indexed(index_layer, q, chunks):
+    """(H, chunks) fp16 scores from the chunk-mean index: bit-identical to retrieval_score over the K it was built from."""
+    _dev(index_layer, q)
+    H, Cmax, D = index_layer.shape
+    ish = _index_layer(index_layer, H, D)
+    assert q.shape == (H, D) and q.dtype == _HALF and q.is_contiguous()
+    if not 1 <= chunks <= Cmax:
+        raise IndexError(f"retrieval_score_indexed: {chunks} chunks of a {Cmax}-chunk index")
+    scores = torch.empty(H, chunks, dtype=_HALF, device=q.device)
+    hip.check(hip.lib().tf_retrieval_score_indexed(_ptr(index_layer), ish, _ptr(q), _ptr(scores), int(chunks), H, D,
+                                                   _stream()), "tf_retrieval_score_indexed")
+    return scores
+
+
 def retrieval_topk(scores, sets):
     """(H, sets) int32: chunk 0 first, then the sets-1 best of [1,C), descending, ties -> lowest chunk."""
     _dev(scores)

@@ -330,10 +330,15 @@ class TriForceRunner:
     ``max_len`` tokens, bench.py drives it for an exact number of steps."""
 
     def __init__(self, tokenizer, graph_engine, gamma, top_k=-1, top_p=0.9, temperature=0.6, verbose=False, rng=None,
-                 inclusive_accept=False, sync_record=None, rebuild_every=0):
+                 inclusive_accept=False, sync_record=None, rebuild_every=0, reanchor_at=0):
         # rebuild_every: N > 0 re-selects the retrieval cache's prefill chunks during every N-th target verify
         #                (SURVEY 8f row 4); 0 = the reference's behaviour, one build per prompt
         self.rebuild_every, self.rebuilds = int(rebuild_every), 0
+        # reanchor_at: N > 0 re-anchors the retrieval cache (DESIGN section 20) at the top of a step whose verify block would
+        #                take the generated tail past N rows: the confirmed rows are folded into the covered region
+        #                (RetrievalCache.reanchor), this step's verify re-selects over it and the tail starts again, so
+        #                generation and extend() may pass the retrieval budget; 0 = the covered region is fixed
+        self.reanchor_at, self.reanchors = int(reanchor_at), 0
         # eager_every: N > 0 runs every N-th target verify eagerly instead of replaying its hipGraph, so that
         #              bench.py can bracket individual attention launches with HIP events inside the timed region
         self.eager_every = 0
@@ -347,6 +352,14 @@ class TriForceRunner:
         self.health = None
         self.tokenizer, self.ge, self.eng = tokenizer, graph_engine, graph_engine.engine
         self.gamma, self.top_k, self.top_p, self.temperature, self.verbose = gamma, top_k, top_p, temperature, verbose
+        if self.reanchor_at != 0:                      # (refused before anything is captured or allocated)
+            refusal = self._extend_refusal("reanchor_at")
+            if refusal is not None:
+                raise NotImplementedError(refusal)
+            if not gamma + 2 <= self.reanchor_at <= self.eng.graph_cache.max_budget:
+                raise ValueError(f"reanchor_at={self.reanchor_at} is outside [gamma + 2, max_budget] = [{gamma + 2}, "
+                                 f"{self.eng.graph_cache.max_budget}]: one verify block must fit below it, and it below the "
+                                 "retrieval budget")
         self.device = self.eng.model.device
         self.rng = rng or UniformSource(self.device)
         self.eos = _eos(tokenizer)
@@ -384,15 +397,15 @@ class TriForceRunner:
         self.start(logits)
         self.history, self._fed = input_ids, []
 
-    def _extend_refusal(self):
-        """Why extend() cannot run over this engine (None: it can)."""
+    def _extend_refusal(self, what="extend()"):
+        """Why extend() — or re-anchoring, the same gate — cannot run over this engine (None: it can)."""
         from ..models.cache import FlashSimpleCache, RetrievalCache
         from .graph_infer import GraphInferenceEngine
         if not isinstance(self.ge, GraphInferenceEngine) or self.sync_record is not None or self.inclusive_accept:
-            return (f"extend() is implemented for the single-GPU resident GraphInferenceEngine only, not for "
+            return (f"{what} is implemented for the single-GPU resident GraphInferenceEngine only, not for "
                     f"{type(self.ge).__name__} (tensor-parallel loop)")
         if type(self.eng.kv_cache) is not FlashSimpleCache or type(self.eng.graph_cache) is not RetrievalCache:
-            return (f"extend() is implemented for the resident FlashSimpleCache + RetrievalCache only, not for "
+            return (f"{what} is implemented for the resident FlashSimpleCache + RetrievalCache only, not for "
                     f"{type(self.eng.kv_cache).__name__} + {type(self.eng.graph_cache).__name__}")
         return None
 
@@ -405,7 +418,13 @@ class TriForceRunner:
         cache is rolled back to k rows (retrieval.prefill <= k <= seq_len), then input_ids are fed.  All rows but the last go
         through the engine's prefill (> 64 rows) or verify (2..64 rows) route, one row through the autoregressive step; the
         last row is fed alone and re-selects the retrieval cache for its query; the draft's StreamingLLM cache is refilled
-        over the whole token history.  Every bound is checked before any state changes (ValueError names the limit)."""
+        over the whole token history.  Every bound is checked before any state changes (ValueError names the limit).
+
+        On a runner with ``reanchor_at`` > 0 the retrieval tail is no bound: a turn that would cross it
+        re-anchors the retrieval cache to the chunk boundary below the last row fed, between the body rows and the last
+        row's forward; and keep=k may lie below the covered region once that has grown (prefill0 <= k): the cache is
+        re-anchored down to the chunk boundary below k first."""
+        from ..models.cache import TOPK_MAX_CHUNKS
         eng, ge, gamma = self.eng, self.ge, self.gamma
         refusal = self._extend_refusal()
         if refusal is not None:
@@ -417,21 +436,34 @@ class TriForceRunner:
         if ids.shape[1] == 0:
             raise ValueError("extend() needs at least one input token")
         S, P = kv.seq_len, rc.prefill
+        moving, chunk = self.reanchor_at > 0, rc.chunk_size
         known = self.history.shape[1] + len(self._fed)
         if keep is None:
             k, rows = S, ids.shape[1] + 1
         else:
             k, rows = int(keep), ids.shape[1]
-            if not P <= k <= S:
+            if moving and not rc.prefill0 <= k <= S:
+                raise ValueError(f"keep={k} is outside [{rc.prefill0}, {S}]: the retrieval cache covers rows [0, "
+                                 f"{rc.prefill0}) at the least and the full cache holds {S} rows")
+            if not moving and not P <= k <= S:
                 raise ValueError(f"keep={k} is outside [{P}, {S}]: the retrieval cache covers rows [0, {P}) and the full "
                                  f"cache holds {S} rows")
+        # the covered region while the body rows are fed (below P: rows of it are about to be rewritten) and for the last row
+        P_feed = P if k >= P else (k // chunk) * chunk
+        P_last = P_feed
         if known < k:
             raise ValueError(f"the runner knows the ids of {known} cache rows, keep needs {k} (the cache length was changed "
                              "behind the runner)")
         room = gamma + 2                                   # one decode step's verify block
-        if k + rows - P + room > rc.max_budget:
-            raise ValueError(f"retrieval tail {k} + {rows} - {P} rows + {room} rows for one decode step exceeds the retrieval "
-                             f"budget max_budget={rc.max_budget}: the covered region [0, {P}) is fixed when the engine is built")
+        if k + rows - P_feed + room > rc.max_budget:
+            if not moving:
+                raise ValueError(f"retrieval tail {k} + {rows} - {P} rows + {room} rows for one decode step exceeds the "
+                                 f"retrieval budget max_budget={rc.max_budget}: the covered region [0, {P}) is fixed when the "
+                                 "engine is built")
+            P_last = ((k + rows - 1) // chunk) * chunk
+            if P_last // chunk > TOPK_MAX_CHUNKS:
+                raise ValueError(f"{k} + {rows} rows need the retrieval cache to cover {P_last // chunk} chunks of {chunk} rows, "
+                                 f"more than the top-k's limit of {TOPK_MAX_CHUNKS} chunks")
         if k + rows + room > kv.max_budget:
             raise ValueError(f"{k} + {rows} rows + {room} rows for one decode step exceeds the full cache's capacity "
                              f"max_budget={kv.max_budget}")
@@ -447,12 +479,19 @@ class TriForceRunner:
                                                       ids], dim=1)
         hist = torch.cat([hist[:, :k], new], dim=1)
         kv.seq_len = k                                     # rows [0, k) stay as they are, the rest is overwritten
+        moved = 0
+        if P_feed != P:
+            rc.reanchor(P_feed)
+            moved += 1
         body = new[:, :-1]
         if body.shape[1] == 1:                             # (q_len == 1 through inference() would build the retrieval cache)
             ge.decode_step(body)
         elif body.shape[1] > 1:
             ge.inference(input_ids=body)
         t.append(self._extend_mark())
+        if P_last != P_feed:                               # every row below P_last is in the full cache now
+            rc.reanchor(P_last)
+            moved += 1
         logits = ge.inference(input_ids=new[:, -1:], rebuild_retrieval=True)   # selection for THIS query over [0, P) + tail
         ge.update_graph_cache()                            # (the last layer's tail copy ran before seq_len advanced)
         t.append(self._extend_mark())
@@ -466,6 +505,7 @@ class TriForceRunner:
         self.bufs.rows_generation = None
         self.resample_count = self.accepted_count = self.target_sample_count = self.draft_count = 0
         self.n = self.inner_iters = self.rebuilds = 0
+        self.reanchors = moved
         self.counts, self.acc_rate_middle_list, self.last_reason = [], [], None
         self.start(logits)                                 # (take + advance: the uniform stream's device cursor is re-written
         if self.time_extend:                               #  before its next reader)
@@ -527,6 +567,16 @@ class TriForceRunner:
         tokenizer, verbose = self.tokenizer, self.verbose
         next_token = self.next_token
         n0 = self.n
+        # re-anchor: between steps seq_len is the rolled-back length, so rows [0, seq_len) are confirmed.
+        # Only the bound moves here (nothing the drafting below reads); this step's verify re-selects over the new region and
+        # the tail copy behind it starts at the new bound
+        reanchor = False
+        if self.reanchor_at > 0:
+            kv, rc = eng.kv_cache, eng.graph_cache
+            if kv.seq_len - rc.prefill + gamma + 2 > self.reanchor_at:
+                rc.reanchor((kv.seq_len // rc.chunk_size) * rc.chunk_size)
+                self.reanchors += 1
+                reanchor = True
         # health (TP): a plain load of the pinned mirror of the exchange's error word after EVERY inner record read — after a
         # timed-out exchange the probabilities are NaN-filled, and without the check up to gamma more iterations would draft,
         # append draft KV and write token ids from them before the outer step noticed
@@ -541,6 +591,7 @@ class TriForceRunner:
         # target model verifies [next, t1..t_g2] against the full KV cache
         rebuild = self.rebuild_every > 0 and (len(self.counts) + 1) % self.rebuild_every == 0
         self.rebuilds += int(rebuild)
+        rebuild = rebuild or reanchor                                  # (one rebuild serves both)
         eager = self.eager_every > 0 and (len(self.counts) + 1) % self.eager_every == 0
         sets = self._device_sets()
         on_device = sets is not None and not rebuild and not eager
@@ -679,9 +730,9 @@ class TriForceRunner:
 
 @torch.inference_mode()
 def TriForce(tokenizer, graph_engine, input_ids, gamma=4, max_len=256, top_k=-1, top_p=0.9, temperature=0.6, verbose=False,
-             file_path=None, dataset=None, spec_args=None, rng=None, return_details=False, rebuild_every=0):
+             file_path=None, dataset=None, spec_args=None, rng=None, return_details=False, rebuild_every=0, reanchor_at=0):
     run = TriForceRunner(tokenizer, graph_engine, gamma, top_k, top_p, temperature, verbose, rng,
-                         rebuild_every=rebuild_every)
+                         rebuild_every=rebuild_every, reanchor_at=reanchor_at)
     run.prefill(input_ids)
     eng, device = run.eng, run.device
     _sync(device)
@@ -716,15 +767,17 @@ class TriForceSession:
     Every answer returns the runner's stats plus ``ttft`` — the seconds from the call to the first token of the answer."""
 
     def __init__(self, tokenizer, graph_engine, gamma=4, top_k=-1, top_p=0.9, temperature=0.6, verbose=False, rng=None,
-                 rebuild_every=0):
+                 rebuild_every=0, reanchor_at=0):
         self.run = TriForceRunner(tokenizer, graph_engine, gamma, top_k, top_p, temperature, verbose, rng,
-                                  rebuild_every=rebuild_every)
+                                  rebuild_every=rebuild_every, reanchor_at=reanchor_at)
         self.ttft = None
 
     @property
     def document(self):
-        """Rows of the full cache that a follow-up question keeps by default: the region the retrieval cache covers."""
-        return self.run.eng.graph_cache.prefill
+        """Rows of the full cache that a follow-up question keeps by default: the region the retrieval cache was built over
+        (re-anchoring moves ``prefill``, not this)."""
+        rc = self.run.eng.graph_cache
+        return getattr(rc, "prefill0", rc.prefill)
 
     def _first_token(self, fn, *a, **kw):
         device = self.run.device
