@@ -297,7 +297,7 @@ def test_device_is_as_close_to_fp64_truth_as_the_cpu_oracle():
     than the CPU oracle is (max within one fp16 spacing more, mean within 15 %).
     Measured (profiles/r03*_parity_notes.txt): with P rounded once to fp16 before the PV MFMA (round 2) the device's mean
     distance to the fp64 result was 7.9e-4 against the oracle's 5.7e-4 — 37 % of the attention outputs were one ulp
-    off; with P fed as hi + lo (csrc/attn.hip TF_ATTN_P_SPLIT) it is 5.5e-4 / max one fp16 spacing: level with the oracle.
+    off; with P fed as hi + lo (csrc/attn.hip, attn_tile) it is 5.5e-4 / max one fp16 spacing: level with the oracle.
     Both differ from the exactly accumulated logits at ~2/3 of the positions — a one-ulp flip in a hidden state moves
     every logit of the row by a fraction of a spacing — which is what the resolution-aware bar of _logit_check rests on."""
     from triforce_amd.models.cache import FlashSimpleCache, RetrievalCache

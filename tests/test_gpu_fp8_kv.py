@@ -310,7 +310,7 @@ def test_target_forward_with_an_fp8_cache_matches_fp64_over_the_stored_rows():
     torch.cuda.synchronize()
     captured = out[0].cpu()
     assert torch.equal(captured, eager), "captured and eager FP8-cache forwards differ"
-    # (the prefill chunk's block attention rounds P once to fp16, TF_BLOCK_P_SPLIT: a wider bar for its row)
+    # (the prefill chunk's block attention rounds P once to fp16, see pair_softmax_pv / lds_softmax_* in csrc/attn.hip: a wider bar for its row)
     for what, got, want, ulps, mean in (("prefill last row", pre, truth_pre, 4, 2e-3), ("decode rows", eager, truth, 2, 1e-3)):
         d = (got - want).abs()
         mag = float(want.abs().max())

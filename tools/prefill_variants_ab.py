@@ -1,7 +1,7 @@
 """A/B of prefill-attention (tf_attn_prefill) library variants at 7B shapes: 32 heads x 128, one 1024-row chunk at the end
 of 32 768 / 124 928 cached keys.  TF/s = causal QK^T + PV flops / time.  Also the largest deviation from attention
 accumulated in fp64 on the device (a 64-row slice), so a variant that changes the arithmetic shows by how much.
-    python tools/prefill_variants_ab.py <variant> [<variant> ...]      (variants: tools/ab_variants.py; "default" = shipped)
+    python tools/prefill_variants_ab.py <variant> [<variant> ...]      ("default" = shipped; others: libraries built by tools/ab_variants.py)
 """
 import json
 import os

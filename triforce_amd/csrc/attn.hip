@@ -23,21 +23,13 @@
 #include "tree_mask.h"
 
 #define NEG_BIG (-1.0e30f)
-// The LDS block kernel reads a tree row's 8 visibility bits (8 consecutive keys per lane) with one 64-bit funnel shift
-// (tree_mask.h) instead of 8 address computations and loads: 512-node Sequoia verify over a 125K prefix 3 140 -> 2 900 us
-// (profiles/r02_gemm_pipeline_ab.jsonl, tune.py "attn_tree_verify_512"); 0 keeps the per-key form for bisecting.
-#ifndef TF_TREE_MASK_FUNNEL
-#define TF_TREE_MASK_FUNNEL 1
-#endif
 #define ATTN_SPLIT_BOUNDS __launch_bounds__(256)
 // Waves per SIMD the two-q-tile form of the split-KV kernel (17..32 query rows: the gamma = 16 verifies) is compiled
 // for.  Left to itself the compiler takes 298 registers for it (1 wave per SIMD, 4 KV tiles in flight per CU); held to
 // 2 waves it fits 236 without scratch and streams 8-15 % faster at every shape of profiles/r02_nsplit_sweep.json
 // (16 heads x 130 066 keys x 17 rows: 225 -> 206 us).  Measured and dropped in the same sweep: transposing each V
 // fragment right before its PV MFMA to run the one-q-tile form at 3 waves per SIMD — no gain beyond run-to-run noise.
-#ifndef TF_ATTN_QT2_OCC
-#define TF_ATTN_QT2_OCC 2
-#endif
+constexpr int ATTN_QT2_OCC = 2;
 // The LDS block kernel is VALU-issue-bound (≈270 non-MFMA instructions per 32 MFMAs with libm's exp2f): its softmax uses
 // the bare v_exp_f32 (exp2f wraps it in a denormal-range fix-up: compare, 2 selects, ldexp) with the score scale folded
 // into one fma: 580 -> 628 TF/s on a 1024-row chunk.  Results below 2^-126 flush to zero — probabilities of keys 2^126
@@ -66,26 +58,10 @@
 #define TF_ATTN_EAGER_TILES 16 // splits of up to this many 16-key tiles per wave use the unconditional-prefetch loop
 #endif
 
-// Two deeper load pipelines, MEASURED AND REJECTED in round 3 (profiles/r03_attn_pipeline_ab.jsonl; cold-cache hipGraph
-// chains, tools/attn_variants_ab.py) — both compile-time off, kept buildable (tools/ab_variants.py "deep8" / "ring4"):
-//   TF_ATTN_DEEP_TILES = N   short streams (a wave owns <= 2 N tiles): attn_split_deep_kernel issues the loads of N
-//       tiles (8 KiB each; one wave per SIMD = 512 registers) before the first MFMA and consumes them in order.  The
-//       hypothesis — the 4 103-key retrieval verify is latency-bound in the two-deep loop, 4 dependent round trips per
-//       wave — is wrong: N = 8 takes it from 20.8 to 25.4 us per launch, the draft-sized stream from 6.5 to 7.5.
-//   TF_ATTN_RING_Q1 / _Q2 = N   long streams: a ring of N tiles in flight per wave, every load unconditional (so the
-//       waitcnt pass keeps vmcnt(8 (N - 1)) in front of each tile — the two-q-tile form's conditional prefetch runs one
-//       tile deep).  N = 4: 32 heads x 125K keys 346.9 -> 347.6 us, 16 heads x 17 rows x 130K keys 195.2 -> 204.3 us,
-//       32 heads x 18 rows 370.0 -> 376.2 us.  More bytes in flight than the shipped loops keep buys nothing here.
-// Both forms walk the same tiles in the same order per wave: bit-identical partials.
-#ifndef TF_ATTN_DEEP_TILES
-#define TF_ATTN_DEEP_TILES 0
-#endif
-#ifndef TF_ATTN_RING_Q1
-#define TF_ATTN_RING_Q1 0
-#endif
-#ifndef TF_ATTN_RING_Q2
-#define TF_ATTN_RING_Q2 0
-#endif
+// The fp16 stream keeps two tiles in flight per wave.  Deeper pipelines were measured and rejected in round 3
+// (profiles/r03_attn_pipeline_ab.jsonl): 8 tiles loaded before the first MFMA took the 4 103-key retrieval verify from 20.8
+// to 25.4 us per launch, a ring of 4 tiles the 16-head x 17-row x 130K-key stream from 195.2 to 204.3 us — more bytes in
+// flight than the shipped loops keep buys nothing here.  (Their code: see the parent of this commit.)
 
 // agent-scope relaxed accesses: global_store / global_load ... sc1 (write-through / L2-coherent across XCDs)
 __device__ __forceinline__ void st_agent(float* p, float v) {
@@ -124,26 +100,16 @@ __device__ __forceinline__ float group_max4(float v) {
     return vmax_raw(__uint_as_float(b[0]), __uint_as_float(b[1]));
 }
 
-// P = exp(S - m) goes to the PV MFMA as fp16.  Rounded ONCE (flash-attn's choice; TF_ATTN_P_SPLIT 0) that costs the
-// attention output ~1 fp16 ulp on average: 36 % of the outputs of a 7 x 4 103-key retrieval verify differ from the
-// exactly accumulated result, and a 7B-width layer's logits end up 1.4x further from it than the CPU oracle's (fp32 P)
-// are (tests/test_gpu_configs.py, fp64 truth; profiles/r03_attn_pipeline_ab.jsonl).  With TF_ATTN_P_SPLIT 1 (default) P
-// is fed as hi + lo — lo = fp16(p - hi), a possibly subnormal fp16 the matrix core takes at full precision — into the
-// same accumulator: 8 more MFMAs per tile and q-tile on a matrix core that is ~9 % busy.  0.16 % of the outputs then
-// differ from exact (mean error 0.25 ulp = the final rounding alone) for +0.9 % on the 125K-key stream.
-#ifndef TF_ATTN_P_SPLIT
-#define TF_ATTN_P_SPLIT 1
-#endif
-// The same hi + lo feed in the block / prefill / tree kernels (pair_softmax_pv, lds_softmax_*) and in the 68M draft's
-// rope-on-read kernel: TF_BLOCK_P_SPLIT / TF_DRAFT_P_SPLIT.  Measured in round 4 (tools/prefill_psplit_ab.py,
-// profiles/r04_psplit_block_ab.jsonl) — see the note there for what ships and why.
-#ifndef TF_BLOCK_P_SPLIT
-#define TF_BLOCK_P_SPLIT 0
-#endif
-#ifndef TF_DRAFT_P_SPLIT
-#define TF_DRAFT_P_SPLIT 1
-#endif
-
+// P = exp(S - m) goes to the PV MFMA as fp16.  Rounded ONCE (flash-attn's choice) that costs the attention output ~1 fp16
+// ulp on average: 36 % of the outputs of a 7 x 4 103-key retrieval verify differ from the exactly accumulated result, and
+// a 7B-width layer's logits end up 1.4x further from it than the CPU oracle's (fp32 P) are (tests/test_gpu_configs.py,
+// fp64 truth; profiles/r03_attn_pipeline_ab.jsonl).  The split-KV kernels feed P as hi + lo — lo = fp16(p - hi), a
+// possibly subnormal fp16 the matrix core takes at full precision — into the same accumulator: 8 more MFMAs per tile and
+// q-tile on a matrix core that is ~9 % busy.  0.16 % of the outputs then differ from exact (mean error 0.25 ulp = the
+// final rounding alone) for +0.9 % on the 125K-key stream.
+// The 68M draft's rope-on-read kernel feeds hi + lo too; the block / prefill / tree kernels (pair_softmax_pv,
+// lds_softmax_*) round P once.  Measured in round 4 (tools/prefill_variants_ab.py, profiles/r04_psplit_block_ab.jsonl) —
+// see the note there for what ships and why.
 
 template <int D, int QT>
 struct AttnState {
@@ -169,16 +135,13 @@ __device__ __forceinline__ void load_kv_tile(const h16* __restrict__ kbase, cons
     }
 }
 
-// Round 6: the same tile fetched as FULL ROWS.  load_kv_tile above issues MFMA A-operand fragments straight from memory: every
-// load instruction touches sixteen rows x 64 bytes (lane (li, g): key li, dims 32 c + 8 g), and a kernel that only reads with that
-// pattern reaches 5.1 TB/s where 256-byte rows, four per instruction, reach 7.0 (tools/probes/hbm_read_probe.hip,
-// profiles/r06_hbm_read_probe.jsonl).  Here lane l of instruction j reads 16 bytes of row RPI j + l / LPR at piece l % LPR
-// (LPR = D / 8 lanes per row, RPI = 64 / LPR rows per instruction; as many instructions as before), and the consumer turns the
-// rows into the fragments load_kv_tile would have produced through a wave-private LDS tile (rows padded by 16 bytes: the
-// fragment reads of a 16-lane group then cover all banks).  Same values in the same registers: the kernel's output bits do not change.
-#ifndef TF_ATTN_ROW_LOADS
-#define TF_ATTN_ROW_LOADS 1
-#endif
+// Round 6: the same tile fetched as FULL ROWS — what the split-KV kernels use.  load_kv_tile above (attn_block_kernel) issues
+// MFMA A-operand fragments straight from memory: every load instruction touches sixteen rows x 64 bytes (lane (li, g): key li,
+// dims 32 c + 8 g), and a kernel that only reads with that pattern reaches 5.1 TB/s where 256-byte rows, four per instruction,
+// reach 7.0 (tools/probes/hbm_read_probe.hip, profiles/r06_hbm_read_probe.jsonl).  Here lane l of instruction j reads 16 bytes
+// of row RPI j + l / LPR at piece l % LPR (LPR = D / 8 lanes per row, RPI = 64 / LPR rows per instruction; as many instructions
+// as before), and the consumer turns the rows into the fragments load_kv_tile would have produced through a wave-private LDS
+// tile (rows padded by 16 bytes: the fragment reads of a 16-lane group then cover all banks).  Same values in the same registers.
 template <int D>
 __device__ __forceinline__ void load_kv_rows(const h16* __restrict__ kbase, const h16* __restrict__ vbase, int64_t stride_t, int tile,
                                              int sk, int lane, half8 (&kr)[D / 32], half8 (&vr)[D / 32]) {
@@ -311,10 +274,7 @@ __device__ __forceinline__ void attn_tile(AttnState<D, QT>& st, const half8 (&kf
         f32x4 r = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf[t >> 1], (t & 1) ? sel1 : sel0, z, 0, 0, 0);
         va[t] = half4{(h16)r[0], (h16)r[1], (h16)r[2], (h16)r[3]};
     }
-    half4 pb[QT];
-#if TF_ATTN_P_SPLIT > 0
-    half4 pl[QT];
-#endif
+    half4 pb[QT], pl[QT];             // P as hi + lo (see the note above AttnState)
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
         f32x4 s = {0.f, 0.f, 0.f, 0.f};
@@ -352,9 +312,7 @@ __device__ __forceinline__ void attn_tile(AttnState<D, QT>& st, const half8 (&kf
             const float p = ok[r] ? __expf(x[r] - mnew) : 0.f;
             psum += p;
             pb[qt][r] = (h16)p;
-#if TF_ATTN_P_SPLIT > 0
             pl[qt][r] = (h16)(p - (float)pb[qt][r]);
-#endif
         }
         // The running maximum settles after the first tiles of a stream; rescaling the 32 accumulator registers
         // (alpha == 1 exactly when no query column of the wave raised its maximum) is skipped wave-uniformly then.
@@ -376,22 +334,21 @@ __device__ __forceinline__ void attn_tile(AttnState<D, QT>& st, const half8 (&kf
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
             st.acc[qt][t] = __builtin_amdgcn_mfma_f32_16x16x16f16(va[t], pb[qt], st.acc[qt][t], 0, 0, 0);
-#if TF_ATTN_P_SPLIT > 0
             st.acc[qt][t] = __builtin_amdgcn_mfma_f32_16x16x16f16(va[t], pl[qt], st.acc[qt][t], 0, 0, 0);
-#endif
         }
 }
 
 
 // ws layout: o[H][nsplit][QR][D] | m[H][nsplit][QR] | l[H][nsplit][QR],  QR = QT*16
 // F8: k / v are e4m3fn codes (strides in bytes) with exponent bytes ke / ve ([H][e_sh] per head, one per key)
-template <int D, int QT, int DEEP = 0, int NW = 4, bool F8 = false>
+template <int D, int QT, bool F8 = false>
 __device__ __forceinline__ void attn_split_body(
     const h16* __restrict__ q, const h16* __restrict__ k, const h16* __restrict__ v, int64_t stride_t,
     int64_t stride_h, int sq, int sk_host, const int32_t* __restrict__ sk_dev, int H, float scale, int nsplit,
     float* __restrict__ ws, unsigned* __restrict__ tickets, h16* __restrict__ out, int64_t osm, int64_t osk,
     const uint8_t* __restrict__ ke = nullptr, const uint8_t* __restrict__ ve = nullptr, int64_t e_sh = 0) {
     constexpr int NC = D / 32, NT = D / 16, QR = QT * 16;
+    constexpr int NW = 4;                              // waves per workgroup
     const int split = blockIdx.x, h = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, g = lane >> 4;
@@ -428,46 +385,28 @@ __device__ __forceinline__ void attn_split_body(
     const h16* kbase = k + (int64_t)h * stride_h;
     const h16* vbase = v + (int64_t)h * stride_h;
 
-    // One block of LDS: the row -> fragment staging tiles of the stream loop (TF_ATTN_ROW_LOADS, 4-wave forms), then — behind a
-    // barrier — the merge of the waves' partial results
-    constexpr int HALVES = NW > 4 ? 2 : 1, DH = D / HALVES, NTH = NT / HALVES;
-    constexpr bool ROWS = TF_ATTN_ROW_LOADS > 0 && NW == 4;
-    constexpr size_t MERGE_BYTES = sizeof(float) * ((size_t)NW * 16 * (DH + 1) + 2 * NW * 16);
-    static_assert(!F8 || (D == 128 && NW == 4 && DEEP == 0), "FP8 stream: D = 128, 4 waves");
-    constexpr size_t STAGE_BYTES = (ROWS || F8) ? (size_t)NW * 2 * 16 * (D + 8) * sizeof(h16) : 0;
+    // One block of LDS: the row -> fragment staging tiles of the stream loop, then — behind a barrier — the merge of the
+    // waves' partial results
+    constexpr size_t MERGE_BYTES = sizeof(float) * ((size_t)NW * 16 * (D + 1) + 2 * NW * 16);
+    static_assert(!F8 || D == 128, "FP8 stream: D = 128");
+    constexpr size_t STAGE_BYTES = (size_t)NW * 2 * 16 * (D + 8) * sizeof(h16);
     __shared__ __attribute__((aligned(16))) unsigned char sm_raw[MERGE_BYTES > STAGE_BYTES ? MERGE_BYTES : STAGE_BYTES];
     h16* stage = reinterpret_cast<h16*>(sm_raw) + (size_t)wave * 2 * 16 * (D + 8);
 
     // tiles whose 16 keys are all <= sk - sq are visible to every row: no mask arithmetic
+    // (macros on purpose: as lambdas the same two helpers changed the register allocation of every split kernel)
 #define ATTN_TILE_FRAGS(KF, VF, T)                                                                    \
     do {                                                                                                \
         if ((T) * 16 + 15 <= sk - sq) attn_tile<D, QT, false, false>(st, KF, VF, sel0, sel1, (T), sk, sq, scale, li, g); \
         else attn_tile<D, QT, false, true>(st, KF, VF, sel0, sel1, (T), sk, sq, scale, li, g);        \
     } while (0)
-    // (ROWS: what was loaded are rows; the fragments are made here, right before their use)
-#define ATTN_TILE_AUTO(KX, VX, T)                                                                     \
+    // what was loaded are rows; the fragments are made here, right before their use
+#define ATTN_TILE_ROWS(KR, VR, T)                                                                     \
     do {                                                                                                \
-        if constexpr (ROWS) {                                                                           \
-            half8 kf_[NC], vf_[NC];                                                                     \
-            rows_to_frags<D>(KX, VX, stage, lane, li, g, kf_, vf_);                                     \
-            ATTN_TILE_FRAGS(kf_, vf_, T);                                                               \
-        } else {                                                                                        \
-            ATTN_TILE_FRAGS(KX, VX, T);                                                                 \
-        }                                                                                               \
+        half8 kf_[NC], vf_[NC];                                                                         \
+        rows_to_frags<D>(KR, VR, stage, lane, li, g, kf_, vf_);                                         \
+        ATTN_TILE_FRAGS(kf_, vf_, T);                                                                   \
     } while (0)
-#define ATTN_LOAD_TILE(T, KX, VX)                                                                     \
-    do {                                                                                                \
-        if constexpr (ROWS) load_kv_rows<D>(kbase, vbase, stride_t, (T), sk, lane, KX, VX);             \
-        else load_kv_tile<D>(kbase, vbase, stride_t, (T), sk, li, g, KX, VX);                           \
-    } while (0)
-    // Two forms of the same two-tiles-deep loop.  A load under `if (t1 < t_end)` makes the compiler assume the worst
-    // case at the use of the OLDER tile — "no younger load was issued" — so it waits vmcnt(7..0) there, i.e. for the
-    // prefetch it has just issued: the wave runs one tile deep.  Issuing the run-ahead loads unconditionally (past the
-    // last tile they re-read it) gives the intended vmcnt(15..8).  Measured (tools/attn_merge_ab.py): short streams gain
-    // (7B retrieval verify 21.0 -> 20.2 us, 4-head TP shard 14.3 -> 13.6, draft-sized 6.9 -> 6.5) but the 125K-key
-    // streams, already bandwidth-bound with 8 MB in flight chip-wide, LOSE 0.7 % (32 heads) to 4 % (16 heads x 17 rows)
-    // with twice as much in flight — so the form is chosen by the length of the wave's stream.
-    static_assert(NW == 4 || (DEEP == 0 && (QT == 1 ? TF_ATTN_RING_Q1 : TF_ATTN_RING_Q2) == 0), "deep / ring forms: 4 waves");
     int t = t_begin + wave;
     if constexpr (F8) {
         // a ring of TF_ATTN_F8_RING tiles, every load unconditional (past the last tile it re-reads it: the waitcnt pass then
@@ -481,98 +420,64 @@ __device__ __forceinline__ void attn_split_body(
             F8Tile ring[RING];
             const int tl = t_end - 1;
 #pragma unroll
-            for (int s = 0; s < RING; ++s) load_kv_rows_f8(kb8, vb8, keb, veb, stride_t, min(t + 4 * s, tl), sk, lane, ring[s]);
+            for (int s = 0; s < RING; ++s) load_kv_rows_f8(kb8, vb8, keb, veb, stride_t, min(t + NW * s, tl), sk, lane, ring[s]);
             while (t < t_end) {
 #pragma unroll
                 for (int s = 0; s < RING; ++s) {
-                    const int ti = t + 4 * s;
+                    const int ti = t + NW * s;
                     if (ti < t_end) {
                         half8 kf_[NC], vf_[NC];
                         f8_rows_to_frags(ring[s], stage, lane, li, g, kf_, vf_);
                         ATTN_TILE_FRAGS(kf_, vf_, ti);
                     }
-                    load_kv_rows_f8(kb8, vb8, keb, veb, stride_t, min(ti + 4 * RING, tl), sk, lane, ring[s]);
+                    load_kv_rows_f8(kb8, vb8, keb, veb, stride_t, min(ti + NW * RING, tl), sk, lane, ring[s]);
                 }
-                t += 4 * RING;
-            }
-        }
-    } else if constexpr (DEEP > 0) {
-        // rounds of N tiles: all N loads issued (tiles past the end re-read the last one: no conditional load, so the
-        // waitcnt pass keeps vmcnt(8 (N - 1 - i)) in front of tile i), then consumed in order
-#define ATTN_DEEP_ROUND(N)                                                                                   \
-    do {                                                                                                       \
-        half8 kd[N][NC], vd[N][NC];                                                                            \
-        const int tl = t_end - 1;                                                                              \
-        _Pragma("unroll") for (int i = 0; i < (N); ++i)                                                        \
-            ATTN_LOAD_TILE(min(t + 4 * i, tl), kd[i], vd[i]);                        \
-        _Pragma("unroll") for (int i = 0; i < (N); ++i) {                                                      \
-            const int ti = t + 4 * i;                                                                          \
-            if (ti < t_end) ATTN_TILE_AUTO(kd[i], vd[i], ti);                                                  \
-        }                                                                                                      \
-        t += 4 * (N);                                                                                          \
-    } while (0)
-        while (t < t_end) {
-            const int left = (t_end - t + 3) >> 2;               // tiles this wave still owns (wave-uniform)
-            if (left > DEEP / 2) ATTN_DEEP_ROUND(DEEP);
-            else if (left > 1) ATTN_DEEP_ROUND(DEEP / 2);
-            else ATTN_DEEP_ROUND(1);
-        }
-#undef ATTN_DEEP_ROUND
-    } else if constexpr ((QT == 1 ? TF_ATTN_RING_Q1 : TF_ATTN_RING_Q2) > 0) {
-        constexpr int RING = QT == 1 ? TF_ATTN_RING_Q1 : TF_ATTN_RING_Q2;
-        if (t < t_end) {
-            half8 kr[RING][NC], vr[RING][NC];
-            const int tl = t_end - 1;
-#pragma unroll
-            for (int s = 0; s < RING; ++s) ATTN_LOAD_TILE(min(t + 4 * s, tl), kr[s], vr[s]);
-            while (t < t_end) {
-#pragma unroll
-                for (int s = 0; s < RING; ++s) {
-                    const int ti = t + 4 * s;
-                    if (ti < t_end) ATTN_TILE_AUTO(kr[s], vr[s], ti);
-                    ATTN_LOAD_TILE(min(ti + 4 * RING, tl), kr[s], vr[s]);
-                }
-                t += 4 * RING;
+                t += NW * RING;
             }
         }
     } else if (t < t_end) {
+        // Two forms of the same two-tiles-deep loop.  A load under `if (t1 < t_end)` makes the compiler assume the worst
+        // case at the use of the OLDER tile — "no younger load was issued" — so it waits vmcnt(7..0) there, i.e. for the
+        // prefetch it has just issued: the wave runs one tile deep.  Issuing the run-ahead loads unconditionally (past the
+        // last tile they re-read it) gives the intended vmcnt(15..8).  Measured (tools/attn_merge_ab.py): short streams gain
+        // (7B retrieval verify 21.0 -> 20.2 us, 4-head TP shard 14.3 -> 13.6, draft-sized 6.9 -> 6.5) but the 125K-key
+        // streams, already bandwidth-bound with 8 MB in flight chip-wide, LOSE 0.7 % (32 heads) to 4 % (16 heads x 17 rows)
+        // with twice as much in flight — so the form is chosen by the length of the wave's stream.
         half8 ka[NC], va_[NC], kb[NC], vb[NC];
-        ATTN_LOAD_TILE(t, ka, va_);
+        load_kv_rows<D>(kbase, vbase, stride_t, t, sk, lane, ka, va_);
         // (one-q-tile form only: with both loops the two-q-tile form no longer fits its 2-waves-per-SIMD register budget)
         if (TF_ATTN_EAGER_TILES > 0 && QT == 1 && t_end - t_begin <= NW * TF_ATTN_EAGER_TILES) {
             const int tl = t_end - 1;
             while (true) {
-                ATTN_LOAD_TILE(min(t + NW, tl), kb, vb);
-                ATTN_TILE_AUTO(ka, va_, t);
+                load_kv_rows<D>(kbase, vbase, stride_t, min(t + NW, tl), sk, lane, kb, vb);
+                ATTN_TILE_ROWS(ka, va_, t);
                 if (t + NW >= t_end) break;
-                ATTN_LOAD_TILE(min(t + 2 * NW, tl), ka, va_);
-                ATTN_TILE_AUTO(kb, vb, t + NW);
+                load_kv_rows<D>(kbase, vbase, stride_t, min(t + 2 * NW, tl), sk, lane, ka, va_);
+                ATTN_TILE_ROWS(kb, vb, t + NW);
                 if (t + 2 * NW >= t_end) break;
                 t += 2 * NW;
             }
         } else {
             while (t < t_end) {
                 const int t1 = t + NW;
-                if (t1 < t_end) ATTN_LOAD_TILE(t1, kb, vb);
-                ATTN_TILE_AUTO(ka, va_, t);
+                if (t1 < t_end) load_kv_rows<D>(kbase, vbase, stride_t, t1, sk, lane, kb, vb);
+                ATTN_TILE_ROWS(ka, va_, t);
                 if (t1 >= t_end) break;
                 const int t2 = t1 + NW;
-                if (t2 < t_end) ATTN_LOAD_TILE(t2, ka, va_);
-                ATTN_TILE_AUTO(kb, vb, t1);
+                if (t2 < t_end) load_kv_rows<D>(kbase, vbase, stride_t, t2, sk, lane, ka, va_);
+                ATTN_TILE_ROWS(kb, vb, t1);
                 t = t2;
             }
         }
     }
 
-#undef ATTN_TILE_AUTO
+#undef ATTN_TILE_ROWS
 #undef ATTN_TILE_FRAGS
-#undef ATTN_LOAD_TILE
-    // ---- merge the NW waves of this split through LDS, one q-tile at a time (8 waves: one half of D at a time, so the
-    // staging stays under the 64 KiB static limit) ----
-    float (*sm_o)[16][DH + 1] = reinterpret_cast<float (*)[16][DH + 1]>(sm_raw);
-    float (*sm_m)[16] = reinterpret_cast<float (*)[16]>(sm_raw + sizeof(float) * (size_t)NW * 16 * (DH + 1));
+    // ---- merge the NW waves of this split through LDS, one q-tile at a time ----
+    float (*sm_o)[16][D + 1] = reinterpret_cast<float (*)[16][D + 1]>(sm_raw);
+    float (*sm_m)[16] = reinterpret_cast<float (*)[16]>(sm_raw + sizeof(float) * (size_t)NW * 16 * (D + 1));
     float (*sm_l)[16] = sm_m + NW;
-    if constexpr (ROWS || F8) __syncthreads();        // another wave may still be reading its staging tile where this one is about to write
+    __syncthreads();                                   // another wave may still be reading its staging tile where this one is about to write
     float* ws_o = ws;
     float* ws_m = ws + (int64_t)H * nsplit * QR * D;
     float* ws_l = ws_m + (int64_t)H * nsplit * QR;
@@ -583,45 +488,42 @@ __device__ __forceinline__ void attn_split_body(
         lsum += __shfl_xor(lsum, 16, 64);
         lsum += __shfl_xor(lsum, 32, 64);
 #pragma unroll
-        for (int hv = 0; hv < HALVES; ++hv) {
+        for (int tt = 0; tt < NT; ++tt)
 #pragma unroll
-            for (int tt = 0; tt < NTH; ++tt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) sm_o[wave][li][16 * tt + 4 * g + r] = st.acc[qt][hv * NTH + tt][r];
-            if (g == 0) {
-                sm_m[wave][li] = st.m[qt];
-                sm_l[wave][li] = lsum;
-            }
-            __syncthreads();
-            for (int e = tid; e < 16 * DH; e += 64 * NW) {
-                const int qq = e / DH, dl = e - qq * DH, d = hv * DH + dl;
-                float mm = sm_m[0][qq];
-#pragma unroll
-                for (int w = 1; w < NW; ++w) mm = fmaxf(mm, sm_m[w][qq]);
-                // sum over the waves in wave order (for NW = 4 the very expression of round 2: ((a0 w0 + a1 w1) + a2 w2) + a3 w3)
-                float o = 0.f, lw = 0.f;
-#pragma unroll
-                for (int w = 0; w < NW; ++w) {
-                    const float ww = __expf(sm_m[w][qq] - mm);
-                    o = (w == 0) ? sm_o[w][qq][dl] * ww : o + sm_o[w][qq][dl] * ww;
-                    lw = (w == 0) ? sm_l[w][qq] * ww : lw + sm_l[w][qq] * ww;
-                }
-                if (tickets == nullptr) {
-                    ws_o[(pbase + qt * 16 + qq) * D + d] = o;
-                    if (d == 0) {
-                        ws_m[pbase + qt * 16 + qq] = mm;
-                        ws_l[pbase + qt * 16 + qq] = lw;
-                    }
-                } else {                                   // one-launch form: write-through (sc1) stores, see below
-                    st_agent(&ws_o[(pbase + qt * 16 + qq) * D + d], o);
-                    if (d == 0) {
-                        st_agent(&ws_m[pbase + qt * 16 + qq], mm);
-                        st_agent(&ws_l[pbase + qt * 16 + qq], lw);
-                    }
-                }
-            }
-            __syncthreads();
+            for (int r = 0; r < 4; ++r) sm_o[wave][li][16 * tt + 4 * g + r] = st.acc[qt][tt][r];
+        if (g == 0) {
+            sm_m[wave][li] = st.m[qt];
+            sm_l[wave][li] = lsum;
         }
+        __syncthreads();
+        for (int e = tid; e < 16 * D; e += 64 * NW) {
+            const int qq = e / D, d = e - qq * D;
+            float mm = sm_m[0][qq];
+#pragma unroll
+            for (int w = 1; w < NW; ++w) mm = fmaxf(mm, sm_m[w][qq]);
+            // sum over the waves in wave order: ((a0 w0 + a1 w1) + a2 w2) + a3 w3
+            float o = 0.f, lw = 0.f;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) {
+                const float ww = __expf(sm_m[w][qq] - mm);
+                o = (w == 0) ? sm_o[w][qq][d] * ww : o + sm_o[w][qq][d] * ww;
+                lw = (w == 0) ? sm_l[w][qq] * ww : lw + sm_l[w][qq] * ww;
+            }
+            if (tickets == nullptr) {
+                ws_o[(pbase + qt * 16 + qq) * D + d] = o;
+                if (d == 0) {
+                    ws_m[pbase + qt * 16 + qq] = mm;
+                    ws_l[pbase + qt * 16 + qq] = lw;
+                }
+            } else {                                   // one-launch form: write-through (sc1) stores, see below
+                st_agent(&ws_o[(pbase + qt * 16 + qq) * D + d], o);
+                if (d == 0) {
+                    st_agent(&ws_m[pbase + qt * 16 + qq], mm);
+                    st_agent(&ws_l[pbase + qt * 16 + qq], lw);
+                }
+            }
+        }
+        __syncthreads();
     }
     if (tickets == nullptr) return;                    // two-launch form: attn_combine_kernel merges the splits
 
@@ -786,46 +688,27 @@ __global__ ATTN_SPLIT_BOUNDS void attn_split_kernel(
                            osm, osk);
 }
 
-// The deep-prefetch form for short streams (one q-tile; see TF_ATTN_DEEP_TILES): one wave per SIMD, 512 registers.
-#if TF_ATTN_DEEP_TILES > 0
+// The two-q-tile form compiled for ATTN_QT2_OCC waves per SIMD (see the note at the top of the file).
 template <int D>
-__global__ __launch_bounds__(256, 1) void attn_split_deep_kernel(
+__global__ __launch_bounds__(256, ATTN_QT2_OCC) void attn_split_q2_kernel(
     const h16* __restrict__ q, const h16* __restrict__ k, const h16* __restrict__ v, const int32_t* __restrict__ sk_dev,
     int sq, int sk_host, int H, int nsplit, int stride_t, int stride_h, float scale,      // <- 14 dwords preloaded into SGPRs
     float* __restrict__ ws, unsigned* __restrict__ tickets, h16* __restrict__ out, int64_t osm, int64_t osk) {
-    attn_split_body<D, 1, TF_ATTN_DEEP_TILES>(q, k, v, (int64_t)stride_t, (int64_t)stride_h, sq, sk_host, sk_dev, H, scale, nsplit,
-                                              ws, tickets, out, osm, osk);
+    attn_split_body<D, 2>(q, k, v, (int64_t)stride_t, (int64_t)stride_h, sq, sk_host, sk_dev, H, scale, nsplit, ws, tickets, out,
+                          osm, osk);
 }
-#endif
-
-// The two-q-tile form compiled for TF_ATTN_QT2_OCC waves per SIMD (see the note at the top of the file).
-// TF_ATTN_Q2_WAVES: waves per workgroup of the two-q-tile form (4 = round 2; 8 = two waves per SIMD at the one-workgroup-
-// per-CU grid, so one wave's softmax / MFMA work runs under the other's loads)
-#ifndef TF_ATTN_Q2_WAVES
-#define TF_ATTN_Q2_WAVES 4
-#endif
-#if TF_ATTN_QT2_OCC > 0
-template <int D>
-__global__ __launch_bounds__(64 * TF_ATTN_Q2_WAVES, TF_ATTN_Q2_WAVES == 8 ? 2 : TF_ATTN_QT2_OCC) void attn_split_q2_kernel(
-    const h16* __restrict__ q, const h16* __restrict__ k, const h16* __restrict__ v, const int32_t* __restrict__ sk_dev,
-    int sq, int sk_host, int H, int nsplit, int stride_t, int stride_h, float scale,      // <- 14 dwords preloaded into SGPRs
-    float* __restrict__ ws, unsigned* __restrict__ tickets, h16* __restrict__ out, int64_t osm, int64_t osk) {
-    attn_split_body<D, 2, 0, TF_ATTN_Q2_WAVES>(q, k, v, (int64_t)stride_t, (int64_t)stride_h, sq, sk_host, sk_dev, H, scale, nsplit, ws,
-                                               tickets, out, osm, osk);
-}
-#endif
 
 // The FP8-KV form (tf_attn_decode_fp8_act): k / v are code pointers, ke / ve the exponent bytes.  The one-q-tile form keeps the
-// fp16 kernel's bounds, the two-q-tile form its TF_ATTN_QT2_OCC waves per SIMD.
+// fp16 kernel's bounds, the two-q-tile form its ATTN_QT2_OCC waves per SIMD.
 template <int QT>
-__global__ __launch_bounds__(256, QT == 2 && TF_ATTN_QT2_OCC > 0 ? TF_ATTN_QT2_OCC : 1) void attn_split_f8_kernel(
+__global__ __launch_bounds__(256, QT == 2 ? ATTN_QT2_OCC : 1) void attn_split_f8_kernel(
     const h16* __restrict__ q, const uint8_t* __restrict__ k, const uint8_t* __restrict__ v, const int32_t* __restrict__ sk_dev,
     int sq, int sk_host, int H, int nsplit, int stride_t, int stride_h, float scale,      // <- 14 dwords preloaded into SGPRs
     float* __restrict__ ws, unsigned* __restrict__ tickets, h16* __restrict__ out, int64_t osm, int64_t osk,
     const uint8_t* __restrict__ ke, const uint8_t* __restrict__ ve, int64_t e_sh) {
-    attn_split_body<128, QT, 0, 4, true>(q, reinterpret_cast<const h16*>(k), reinterpret_cast<const h16*>(v), (int64_t)stride_t,
-                                         (int64_t)stride_h, sq, sk_host, sk_dev, H, scale, nsplit, ws, tickets, out, osm, osk,
-                                         ke, ve, e_sh);
+    attn_split_body<128, QT, true>(q, reinterpret_cast<const h16*>(k), reinterpret_cast<const h16*>(v), (int64_t)stride_t,
+                                   (int64_t)stride_h, sq, sk_host, sk_dev, H, scale, nsplit, ws, tickets, out, osm, osk, ke, ve,
+                                   e_sh);
 }
 
 // ---- 32-key step of the block kernel: two 16-key tiles A, B per softmax update ----------------------------
@@ -900,13 +783,12 @@ __device__ __forceinline__ void pair_softmax_pv(AttnState<D, QT>& st, const Pair
         tmax = group_max4(tmax);
         const float mnew = fmaxf(st.m[qt], tmax);
         float psum = 0.f;
-        half8 pb, pl;
+        half8 pb;
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             const float p = ok[r] ? exp2f(x[r] - mnew) : 0.f;
             psum += p;
             pb[r] = (h16)p;
-            pl[r] = (h16)(p - (float)pb[r]);
         }
         if (__builtin_amdgcn_ballot_w64(mnew != st.m[qt])) {
             const float alpha = exp2f(st.m[qt] - mnew);
@@ -920,12 +802,7 @@ __device__ __forceinline__ void pair_softmax_pv(AttnState<D, QT>& st, const Pair
         }
         st.l[qt] += psum;
 #pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            st.acc[qt][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ps.va8[t], pb, st.acc[qt][t], 0, 0, 0);
-#if TF_BLOCK_P_SPLIT > 0
-            st.acc[qt][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ps.va8[t], pl, st.acc[qt][t], 0, 0, 0);
-#endif
-        }
+        for (int t = 0; t < NT; ++t) st.acc[qt][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ps.va8[t], pb, st.acc[qt][t], 0, 0, 0);
     }
 }
 
@@ -941,14 +818,10 @@ __device__ __forceinline__ void pair_softmax_pv(AttnState<D, QT>& st, const Pair
 // TREE = false: bottom-right causal mask.  TREE = true: keys [0, tree_start) are visible to every row, key
 // tree_start + j is visible to row i iff bit j of mask row (mask_row0 + i) is set (the reference's additive mask
 // is 0 / fp16-min over the tree columns: SpecTree_TP.py:65-67,83-87,170; a 0/1 bit loses nothing).
-#ifndef TF_BLOCK_NO_LDS
-#define TF_BLOCK_NO_LDS 0       // 1: 65..128-row blocks use the register-only kernel instead of the LDS-shared one
-#endif
-#ifndef TF_BLOCK_OCC
-#define TF_BLOCK_OCC 1          // waves per SIMD the block kernel is compiled for (A/B: 1 lets it use 512 registers)
-#endif
+// Launched for blocks of up to 64 rows (rg <= 2); 65..128-row blocks run the LDS-shared form below.  Compiled for one wave
+// per SIMD: it may use 512 registers.
 template <int D, bool TREE>
-__global__ __launch_bounds__(256, TF_BLOCK_OCC) void attn_block_kernel(
+__global__ __launch_bounds__(256, 1) void attn_block_kernel(
     const h16* __restrict__ q, const h16* __restrict__ k, const h16* __restrict__ v, int64_t stride_t,
     int64_t stride_h, int sq, int sk, int H, float scale, int nsplit, int rg, float* __restrict__ ws,
     const uint32_t* __restrict__ mask, int mask_words, int mask_row0, int tree_start) {
@@ -1092,7 +965,7 @@ __device__ __forceinline__ void lds_softmax_pv(AttnState<D, QT>& st, const f32x4
                                                const h16* __restrict__ svt, int g0, int key0, int sk, int sq,
                                                float scale_log2, int li, int g, int qbase, TreeMask tm) {
     constexpr int NT = D / 16, VS = BLK_SLAB + 8;
-    half8 pb[QT], pl[QT];
+    half8 pb[QT];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
         const int qrow = qbase + qt * 16 + li;
@@ -1100,33 +973,22 @@ __device__ __forceinline__ void lds_softmax_pv(AttnState<D, QT>& st, const f32x4
         float x[8];
         bool ok[8];
         float tmax = NEG_BIG;
-#if TF_TREE_MASK_FUNNEL
-        uint32_t vis8 = 0xFFu;                 // the lane's 8 keys are consecutive: 8 consecutive bits of the mask row
+        // The lane's 8 keys are consecutive = 8 consecutive bits of the mask row, read with one 64-bit funnel shift
+        // (tree_mask.h) instead of 8 address computations and loads: 512-node Sequoia verify over a 125K prefix
+        // 3 140 -> 2 900 us (profiles/r02_gemm_pipeline_ab.jsonl, tune.py "attn_tree_verify_512").
+        uint32_t vis8 = 0xFFu;
         if (MASKED && TREE) {
             const int kidx0 = key0 + 8 * g;
             vis8 = tf_tree_vis8(tm.rows + (int64_t)(tm.row0 + min(qrow, sq - 1)) * tm.words, tm.words,
                                 kidx0 - tm.start, sk - kidx0);
         }
-#endif
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             const int kidx = key0 + 8 * g + r;
             bool v = true;
             if (MASKED) {
-                if (TREE) {
-#if TF_TREE_MASK_FUNNEL
-                    v = (vis8 >> r) & 1u;
-#else
-                    const int j = kidx - tm.start;
-                    v = kidx < sk;
-                    if (j >= 0 && v) {
-                        const int mrow = tm.row0 + min(qrow, sq - 1);
-                        v = (tm.rows[(int64_t)mrow * tm.words + (j >> 5)] >> (j & 31)) & 1u;
-                    }
-#endif
-                } else {
-                    v = kidx <= kmax;
-                }
+                if (TREE) v = (vis8 >> r) & 1u;
+                else v = kidx <= kmax;
             }
             ok[r] = v;
             x[r] = (r < 4 ? sa[qt][r] : sb[qt][r - 4]);                 // raw score: the scale rides in the fma below
@@ -1144,7 +1006,6 @@ __device__ __forceinline__ void lds_softmax_pv(AttnState<D, QT>& st, const f32x4
             const float p = ok[r] ? __builtin_amdgcn_exp2f(fmaf(x[r], scale_log2, -mnew)) : 0.f;
             psum += p;
             pb[qt][r] = (h16)p;
-            pl[qt][r] = (h16)(p - (float)pb[qt][r]);
         }
         if (__builtin_amdgcn_ballot_w64(mnew != st.m[qt])) {
             const float alpha = __builtin_amdgcn_exp2f(st.m[qt] - mnew);
@@ -1168,12 +1029,7 @@ __device__ __forceinline__ void lds_softmax_pv(AttnState<D, QT>& st, const f32x4
             const half4 lo = lds_read_tr4(vrow + pos), hi = lds_read_tr4(vrow + 4 * D + pos);
             const half8 vt = half8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 #pragma unroll
-            for (int qt = 0; qt < QT; ++qt) {
-                st.acc[qt][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vt, pb[qt], st.acc[qt][t], 0, 0, 0);
-#if TF_BLOCK_P_SPLIT > 0
-                st.acc[qt][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vt, pl[qt], st.acc[qt][t], 0, 0, 0);
-#endif
-            }
+            for (int qt = 0; qt < QT; ++qt) st.acc[qt][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vt, pb[qt], st.acc[qt][t], 0, 0, 0);
         }
     } else {
 #pragma unroll
@@ -1181,69 +1037,25 @@ __device__ __forceinline__ void lds_softmax_pv(AttnState<D, QT>& st, const f32x4
             const int d = 16 * t + li;                                              // V^T[d][keys 8(g0+g) .. +7]
             const half8 vt = load_half8(svt + d * VS + 8 * ((g0 + g) ^ BLK_VSWZ(d)));
 #pragma unroll
-            for (int qt = 0; qt < QT; ++qt) {
-                st.acc[qt][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vt, pb[qt], st.acc[qt][t], 0, 0, 0);
-#if TF_BLOCK_P_SPLIT > 0
-                st.acc[qt][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vt, pl[qt], st.acc[qt][t], 0, 0, 0);
-#endif
-            }
+            for (int qt = 0; qt < QT; ++qt) st.acc[qt][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vt, pb[qt], st.acc[qt][t], 0, 0, 0);
         }
     }
 }
 
-// ---- the fully visible slab (TF_BLOCK_PIPE) --------------------------------------------------------------------------
+// ---- the fully visible slab ---------------------------------------------------------------------------------------------
 // A 64-key slab all of whose keys every row of the wave may see — every slab of a long prefix but the last one or two — is
-// walked as ONE softmax step instead of two:  QK(0) QK(1) | max, exps | PV(0) PV(1).
-//   1  both QK^T runs first, then the two sub-steps' softmax / PV as before (bit-identical to the alternating form):
-//      1024-row chunk over 124 928 keys 722 -> 754 TF/s;
-//   2  (default) ONE running-max update — and at most one accumulator rescale — per slab: both sub-steps' probabilities are
-//      taken against max(m, slab max).  The same softmax (m only ever has to dominate the scores seen so far), half the
-//      max / ballot / rescale bookkeeping, two long MFMA runs instead of four short ones: 722 -> 799 TF/s
-//      (profiles/r03_prefill_slab_ab.jsonl; error against attention accumulated in fp64 unchanged: max 1.64e-5, mean
-//      2.03e-6 on outputs of magnitude ~0.01).  Its max chain is plain fmaxf — measured equal to the asm v_max3 chain, and
-//      the compiler's hazard recogniser then sees every reader of the MFMA results (see mfma_settle8).
-//   0  the alternating form (also what masked slabs, the TREE form and D = 64 use).
-#ifndef TF_BLOCK_PIPE
-#define TF_BLOCK_PIPE 2
-#endif
-template <int D, int QT>
-__device__ __forceinline__ void lds_softmax_clear(AttnState<D, QT>& st, const f32x4 (&sa)[QT], const f32x4 (&sb)[QT],
-                                                  float scale_log2, half8 (&pb)[QT], half8 (&pl)[QT]) {
-    constexpr int NT = D / 16;
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt) {
-        float x[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) x[r] = (r < 4 ? sa[qt][r] : sb[qt][r - 4]);
-        mfma_settle8(x);
-        float tmax = vmax3_raw(vmax3_raw(x[0], x[1], x[2]), vmax3_raw(x[3], x[4], x[5]), vmax_raw(x[6], x[7]));
-        tmax = group_max4(tmax);
-        const float mnew = fmaxf(st.m[qt], tmax * scale_log2);
-        float psum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const float p = __builtin_amdgcn_exp2f(fmaf(x[r], scale_log2, -mnew));
-            psum += p;
-            pb[qt][r] = (h16)p;
-            pl[qt][r] = (h16)(p - (float)pb[qt][r]);
-        }
-        if (__builtin_amdgcn_ballot_w64(mnew != st.m[qt])) {
-            const float alpha = __builtin_amdgcn_exp2f(st.m[qt] - mnew);
-            st.l[qt] *= alpha;
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                st.acc[qt][t][0] *= alpha; st.acc[qt][t][1] *= alpha;
-                st.acc[qt][t][2] *= alpha; st.acc[qt][t][3] *= alpha;
-            }
-            st.m[qt] = mnew;
-        }
-        st.l[qt] += psum;
-    }
-}
+// walked as ONE softmax step instead of two:  QK(0) QK(1) | max, exps | PV(0) PV(1).  ONE running-max update — and at most
+// one accumulator rescale — per slab: both sub-steps' probabilities are taken against max(m, slab max).  The same softmax
+// (m only ever has to dominate the scores seen so far), half the max / ballot / rescale bookkeeping, two long MFMA runs
+// instead of four short ones: 1024-row chunk over 124 928 keys 722 -> 799 TF/s (profiles/r03_prefill_slab_ab.jsonl; error
+// against attention accumulated in fp64 unchanged: max 1.64e-5, mean 2.03e-6 on outputs of magnitude ~0.01; running both
+// QK^T first but keeping two softmax steps reached 754).  Its max chain is plain fmaxf — measured equal to the asm v_max3
+// chain, and the compiler's hazard recogniser then sees every reader of the MFMA results (see mfma_settle8).
+// Masked slabs, the TREE form and D = 64 walk the alternating form (lds_softmax_pv per 32-key sub-step).
 template <int D, int QT>
 __device__ __forceinline__ void lds_softmax_clear2(AttnState<D, QT>& st, const f32x4 (&s0a)[QT], const f32x4 (&s0b)[QT],
                                                    const f32x4 (&s1a)[QT], const f32x4 (&s1b)[QT], float scale_log2,
-                                                   half8 (&p0)[QT], half8 (&p1)[QT], half8 (&l0)[QT], half8 (&l1)[QT]) {
+                                                   half8 (&p0)[QT], half8 (&p1)[QT]) {
     constexpr int NT = D / 16;
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
@@ -1262,9 +1074,8 @@ __device__ __forceinline__ void lds_softmax_clear2(AttnState<D, QT>& st, const f
         for (int r = 0; r < 16; ++r) {
             const float p = __builtin_amdgcn_exp2f(fmaf(x[r], scale_log2, -mnew));
             psum += p;
-            const h16 ph = (h16)p, pw = (h16)(p - (float)ph);
-            if (r < 8) { p0[qt][r] = ph; l0[qt][r] = pw; }
-            else { p1[qt][r - 8] = ph; l1[qt][r - 8] = pw; }
+            if (r < 8) p0[qt][r] = (h16)p;
+            else p1[qt][r - 8] = (h16)p;
         }
         if (__builtin_amdgcn_ballot_w64(mnew != st.m[qt])) {
             const float alpha = __builtin_amdgcn_exp2f(st.m[qt] - mnew);
@@ -1280,8 +1091,8 @@ __device__ __forceinline__ void lds_softmax_clear2(AttnState<D, QT>& st, const f
     }
 }
 template <int D, int QT>
-__device__ __forceinline__ void lds_pv_tr(AttnState<D, QT>& st, const half8 (&pb)[QT], const half8 (&pl)[QT],
-                                          const h16* __restrict__ svt, int g0, int li, int g) {
+__device__ __forceinline__ void lds_pv_tr(AttnState<D, QT>& st, const half8 (&pb)[QT], const h16* __restrict__ svt, int g0,
+                                          int li, int g) {
     constexpr int NT = D / 16;
     const int fv = (li >> 2) | ((g & 1) << 2);
     const h16* vrow = svt + (8 * (g0 + g) + (li >> 2)) * D + 4 * (li & 3);
@@ -1291,26 +1102,17 @@ __device__ __forceinline__ void lds_pv_tr(AttnState<D, QT>& st, const half8 (&pb
         const half4 lo = lds_read_tr4(vrow + pos), hi = lds_read_tr4(vrow + 4 * D + pos);
         const half8 vt = half8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) {
-            st.acc[qt][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vt, pb[qt], st.acc[qt][t], 0, 0, 0);
-#if TF_BLOCK_P_SPLIT > 0
-            st.acc[qt][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vt, pl[qt], st.acc[qt][t], 0, 0, 0);
-#endif
-        }
+        for (int qt = 0; qt < QT; ++qt) st.acc[qt][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vt, pb[qt], st.acc[qt][t], 0, 0, 0);
     }
 }
 
-// K / V slab loads of the LDS block kernel by LDS-DMA instead of through 32 staging registers per lane (swizzled layout,
-// D = 128): 1 = TREE form only, 2 = chain form too (default), 0 = register-staged.  The TREE form spilled 24 registers at
-// its 2 waves per SIMD; without the staging registers it spills 2: 512-node Sequoia verify over a 124 928-token prefix
-// 2 298 -> 1 905 us, 128-row chain block 465 -> 422 us, outputs bit-identical (profiles/r03_block_dma_ab.jsonl).
-#ifndef TF_BLOCK_DMA
-#define TF_BLOCK_DMA 2
-#endif
-#ifndef TF_BLOCK_TREE_OCC
-#define TF_BLOCK_TREE_OCC 2      // waves per SIMD of the TREE form of the LDS block kernel.  At 2 it spills 46 registers; at 1
-                                 // (512 registers, no spill) the 512-node Sequoia verify is 25 % SLOWER (2 890 -> 3 630 us): kept at 2
-#endif
+// K / V slab loads of the LDS block kernel go by LDS-DMA instead of through 32 staging registers per lane wherever the
+// layout is the swizzled one (D = 128, TREE and chain form alike).  The TREE form spilled 24 registers at its 2 waves per
+// SIMD; without the staging registers it spills 2: 512-node Sequoia verify over a 124 928-token prefix 2 298 -> 1 905 us,
+// 128-row chain block 465 -> 422 us, outputs bit-identical (profiles/r03_block_dma_ab.jsonl).
+// Both forms are compiled for 2 waves per SIMD.  The TREE form at 1 (512 registers, no spill) ran the 512-node Sequoia
+// verify 25 % SLOWER (2 890 -> 3 630 us).
+constexpr int BLOCK_LDS_OCC = 2;
 // One workgroup: the 128-row block ``q`` against slabs [s_begin, s_end) of head h; partial (m, l, O) to slot ``split``.
 template <int D, bool TREE>
 __device__ __forceinline__ void attn_block_lds_body(
@@ -1358,10 +1160,10 @@ __device__ __forceinline__ void attn_block_lds_body(
     const int lr = tid / VPR, lc = tid % VPR;               // this thread's (row, 16-byte column) in a load pass
     const int row_a = 8 * (li >> 2) + (li & 3);             // slab row behind MFMA row li of tile A (tile B: +4)
 
-    // K / V slabs reach LDS either through staging registers (fetch -> stash: 32 registers per lane live across a slab's
-    // MFMAs) or — TF_BLOCK_DMA, swizzled layout only — by LDS-DMA straight into the buffer the NEXT iteration reads (free
-    // since the previous barrier), the XOR swizzle applied on the source side (see attn_prefill_ahead_body).
-    constexpr bool DMA = TF_BLOCK_DMA && TR && (TREE || TF_BLOCK_DMA > 1);
+    // K / V slabs reach LDS either through staging registers (padded layout, D = 64: fetch -> stash, the registers live
+    // across a slab's MFMAs) or — swizzled layout, D = 128 — by LDS-DMA straight into the buffer the NEXT iteration reads
+    // (free since the previous barrier), the XOR swizzle applied on the source side (see attn_prefill_ahead_body).
+    constexpr bool DMA = TR;
     half8 gk[DMA ? 1 : NPASS], gv[DMA ? 1 : NPASS];
     auto fetch = [&](int slab, int buf) {
 #pragma unroll
@@ -1393,16 +1195,10 @@ __device__ __forceinline__ void attn_block_lds_body(
 #pragma unroll
         for (int p = 0; p < (DMA ? 0 : NPASS); ++p) {
             const int r = p * RPP + lr;
-            if constexpr (TR) {
-                const int fk = (r & 3) | (((r >> 3) & 3) << 2), fv = (r & 3) | (((r >> 3) & 1) << 2);
-                store_half8(dk + r * RS + 8 * (lc ^ fk), gk[p]);
-                store_half8(dv + r * D + 8 * ((((lc >> 1) ^ fv) << 1) | (lc & 1)), gv[p]);
-            } else {
-                store_half8(dk + r * RS + 8 * lc, gk[p]);
+            store_half8(dk + r * RS + 8 * lc, gk[p]);
 #pragma unroll
-                for (int e = 0; e < 8; ++e)                // d = 8*lc + e -> swizzle key = lc
-                    dv[(8 * lc + e) * VS + ((((r >> 3) ^ (lc & (SLAB / 8 - 1))) << 3) | (r & 7))] = gv[p][e];
-            }
+            for (int e = 0; e < 8; ++e)                    // d = 8*lc + e -> swizzle key = lc
+                dv[(8 * lc + e) * VS + ((((r >> 3) ^ (lc & (SLAB / 8 - 1))) << 3) | (r & 7))] = gv[p][e];
         }
     };
 
@@ -1422,7 +1218,7 @@ __device__ __forceinline__ void attn_block_lds_body(
         const h16* bk = sK + buf * BlkLayout<D>::K_HALFS;
         const h16* bv = sVt + buf * BlkLayout<D>::V_HALFS;
         bool piped = false;
-        if constexpr (TF_BLOCK_PIPE && TR && !TREE && SLAB == 64) {
+        if constexpr (TR && !TREE && SLAB == 64) {                   // the fully visible slab as one softmax step (see above)
             const int last = sl * SLAB + SLAB - 1;
             if (last < sk && last <= sk - sq + qbase) {              // wave-uniform: both sub-steps fully visible
                 piped = true;
@@ -1454,17 +1250,10 @@ __device__ __forceinline__ void attn_block_lds_body(
                         s1b[qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kb, st.qf[qt][c], s1b[qt], 0, 0, 0);
                     }
                 }
-                half8 p0[QT], p1[QT], l0[QT], l1[QT];
-                if constexpr (TF_BLOCK_PIPE >= 2) {
-                    lds_softmax_clear2<D, QT>(st, s0a, s0b, s1a, s1b, scale_log2, p0, p1, l0, l1);
-                    lds_pv_tr<D, QT>(st, p0, l0, bv, 0, li, g);
-                    lds_pv_tr<D, QT>(st, p1, l1, bv, 4, li, g);
-                } else {
-                    lds_softmax_clear<D, QT>(st, s0a, s0b, scale_log2, p0, l0);
-                    lds_pv_tr<D, QT>(st, p0, l0, bv, 0, li, g);
-                    lds_softmax_clear<D, QT>(st, s1a, s1b, scale_log2, p1, l1);
-                    lds_pv_tr<D, QT>(st, p1, l1, bv, 4, li, g);
-                }
+                half8 p0[QT], p1[QT];
+                lds_softmax_clear2<D, QT>(st, s0a, s0b, s1a, s1b, scale_log2, p0, p1);
+                lds_pv_tr<D, QT>(st, p0, bv, 0, li, g);
+                lds_pv_tr<D, QT>(st, p1, bv, 4, li, g);
             }
         }
 #pragma unroll
@@ -1520,7 +1309,7 @@ __device__ __forceinline__ void attn_block_lds_body(
 }
 
 template <int D, bool TREE>
-__global__ __launch_bounds__(256, TREE ? TF_BLOCK_TREE_OCC : 2) void attn_block_lds_kernel(
+__global__ __launch_bounds__(256, BLOCK_LDS_OCC) void attn_block_lds_kernel(
     const h16* __restrict__ q, const h16* __restrict__ k, const h16* __restrict__ v, int64_t stride_t,
     int64_t stride_h, int sq, int sk, int H, float scale, int nsplit, float* __restrict__ ws,
     const uint32_t* __restrict__ mask, int mask_words, int mask_row0, int tree_start) {
@@ -1532,7 +1321,7 @@ __global__ __launch_bounds__(256, TREE ? TF_BLOCK_TREE_OCC : 2) void attn_block_
                                  tree_start, split, h, s_begin, min(nslabs, s_begin + sps));
 }
 
-// ---- prefill body with the NEXT slab's QK^T issued ahead and K / V brought in by LDS-DMA (TF_PREFILL_AHEAD) -----------------
+// ---- prefill body with the NEXT slab's QK^T issued ahead and K / V brought in by LDS-DMA ------------------------------------
 // The dependency chain of a slab is QK^T -> softmax -> PV: matrix core, VALU, matrix core.  K[s] is dead as soon as
 // QK^T(s) has run, so with the SAME two K and two V buffers the loop can hold K one slab ahead of V: iteration s runs
 // QK^T(s + 1) (from the K buffer this iteration's PV does not touch), then the softmax of slab s on scores computed one
@@ -1545,10 +1334,7 @@ __global__ __launch_bounds__(256, TREE ? TF_BLOCK_TREE_OCC : 2) void attn_block_
 // 1024-row chunk x 124 928 keys x 32 heads, same box (profiles/r03_prefill_slab_ab.jsonl): 792.7 -> 848.4 TF/s (+7 %; +10.5 %
 // on a slower box).  Splitting the softmax so that the compiler interleaves the next slab's QK^T MFMAs with this slab's exps
 // INSIDE one wave measured slower (820.5): what overlaps the matrix core with the VALU here is the other wave of the SIMD.
-// D = 128, chain (non-tree) form only; 0 = the shared body (attn_block_lds_body).
-#ifndef TF_PREFILL_AHEAD
-#define TF_PREFILL_AHEAD 1
-#endif
+// D = 128, chain (non-tree) form only; D = 64 runs the shared body (attn_block_lds_body).
 template <int D>
 __device__ __forceinline__ void attn_prefill_ahead_body(
     const h16* __restrict__ q, const h16* __restrict__ k, const h16* __restrict__ v, int64_t stride_t,
@@ -1653,11 +1439,11 @@ __device__ __forceinline__ void attn_prefill_ahead_body(
             f32x4 n0a[QT], n0b[QT], n1a[QT], n1b[QT];
             const int last = sl * SLAB + SLAB - 1;
             if (last < sk && last <= sk - sq + qbase) {      // wave-uniform: the whole slab is visible to every row of the wave
-                half8 p0[QT], p1[QT], l0[QT], l1[QT];
+                half8 p0[QT], p1[QT];
                 qk_slab(bk_next, n0a, n0b, n1a, n1b);        // next slab's QK^T (past the end: finite garbage, never used)
-                lds_softmax_clear2<D, QT>(st, c0a, c0b, c1a, c1b, scale_log2, p0, p1, l0, l1);
-                lds_pv_tr<D, QT>(st, p0, l0, bv, 0, li, g);
-                lds_pv_tr<D, QT>(st, p1, l1, bv, 4, li, g);
+                lds_softmax_clear2<D, QT>(st, c0a, c0b, c1a, c1b, scale_log2, p0, p1);
+                lds_pv_tr<D, QT>(st, p0, bv, 0, li, g);
+                lds_pv_tr<D, QT>(st, p1, bv, 4, li, g);
             } else {
                 qk_slab(bk_next, n0a, n0b, n1a, n1b);
                 const int key0 = sl * SLAB;
@@ -1720,7 +1506,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(
     const int sps = (nslabs_all + nsplit - 1) / nsplit;
     const int s_begin = split * sps;
     float* ws_rb = ws + (int64_t)rb * H * nsplit * 128 * (D + 2);
-    if constexpr (TF_PREFILL_AHEAD && BlkLayout<D>::TR)
+    if constexpr (BlkLayout<D>::TR)
         attn_prefill_ahead_body<D>(q + (int64_t)r0 * H * D, k, v, stride_t, stride_h, rows, sk_eff, H, scale, nsplit, ws_rb,
                                    split, h, s_begin, min(nslabs, s_begin + sps));
     else
@@ -1952,12 +1738,8 @@ __global__ __launch_bounds__(256) void attn_rope_on_read_mfma_kernel(
     h16* sK = reinterpret_cast<h16*>(smem_raw);       // [kvp][KS]
     h16* sVt = sK + (size_t)kvp * KS;                 // [D][PS]
     h16* sP = sVt + (size_t)D * PS;                   // [16][PS]
-#if TF_DRAFT_P_SPLIT > 0
-    h16* sPl = sP + (size_t)16 * PS;                  // [16][PS]  low-order parts of P
+    h16* sPl = sP + (size_t)16 * PS;                  // [16][PS]  low-order parts of P (hi + lo feed: see the note above AttnState)
     float* sS = reinterpret_cast<float*>(sPl + (size_t)16 * PS);  // [16][kvp]
-#else
-    float* sS = reinterpret_cast<float*>(sP + (size_t)16 * PS);   // [16][kvp]
-#endif
     float* sL = sS + (size_t)16 * kvp;                // [16]
 
     const int h = blockIdx.x, q0 = blockIdx.y * 16;
@@ -2031,9 +1813,7 @@ __global__ __launch_bounds__(256) void attn_rope_on_read_mfma_kernel(
             }
             const h16 ph = (h16)p;
             sP[(size_t)row * PS + j] = ph;
-#if TF_DRAFT_P_SPLIT > 0
             sPl[(size_t)row * PS + j] = (h16)(p - (float)ph);          // low-order part of P: its own A operand below
-#endif
         }
         lsum = wave_sum(lsum);
         if (lane == 0) sL[row] = lsum;
@@ -2046,9 +1826,7 @@ __global__ __launch_bounds__(256) void attn_rope_on_read_mfma_kernel(
         const half8 ap = load_half8(sP + (size_t)li * PS + 32 * c + 8 * g);
         const half8 bv = load_half8(sVt + (size_t)(16 * wave + li) * PS + 32 * c + 8 * g);
         o = __builtin_amdgcn_mfma_f32_16x16x32_f16(ap, bv, o, 0, 0, 0);
-#if TF_DRAFT_P_SPLIT > 0
         o = __builtin_amdgcn_mfma_f32_16x16x32_f16(load_half8(sPl + (size_t)li * PS + 32 * c + 8 * g), bv, o, 0, 0, 0);
-#endif
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -2059,7 +1837,7 @@ __global__ __launch_bounds__(256) void attn_rope_on_read_mfma_kernel(
 
 static size_t draft_mfma_lds_bytes(int kv_len) {
     const size_t kvp = (size_t)((kv_len + 31) & ~31), PS = kvp + DRAFT_KPAD;
-    return kvp * (64 + DRAFT_KPAD) * 2 + 64 * PS * 2 + (TF_DRAFT_P_SPLIT > 0 ? 2 : 1) * 16 * PS * 2 + 16 * kvp * 4 + 16 * 4;
+    return kvp * (64 + DRAFT_KPAD) * 2 + 64 * PS * 2 + 2 * 16 * PS * 2 + 16 * kvp * 4 + 16 * 4;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2111,27 +1889,12 @@ static int launch_attn(const void* q, const void* k, const void* v, void* out, i
     // folds them inside the launch (see FUSED_MERGE_BIG_SPLITS)
     if (tickets && nsplit > FUSED_MERGE_MAX_SPLITS &&
         (D != 128 || H > 64 || nsplit > FUSED_MERGE_BIG_SPLITS || (int64_t)nsplit * H > FUSED_MERGE_BIG_MAX_WGS ||
-         TF_ATTN_Q2_WAVES > 4 || !g_attn_rendezvous))
+         !g_attn_rendezvous))
         tickets = nullptr;
-    bool launched = false;
-#if TF_ATTN_DEEP_TILES > 0
-    if constexpr (QT == 1) {
-        // tiles one wave owns at the HOST key count (a device-side count can only be smaller)
-        const int ntiles = (sk + 15) / 16, tps = (ntiles + nsplit - 1) / nsplit, per_wave = (tps + 3) / 4;
-        if (per_wave <= 2 * TF_ATTN_DEEP_TILES && (int64_t)nsplit * H <= 320) {      // short streams, <= ~1 workgroup per CU
-            hipLaunchKernelGGL((attn_split_deep_kernel<D>), grid, block, 0, st, (const h16*)q, (const h16*)k, (const h16*)v,
-                               sk_dev, sq, sk, H, nsplit, (int)stride_t, (int)stride_h, scale, ws, tickets, (h16*)out, osm, osk);
-            launched = true;
-        }
-    }
-#endif
-#if TF_ATTN_QT2_OCC > 0
     if constexpr (QT == 2)
-        hipLaunchKernelGGL((attn_split_q2_kernel<D>), grid, dim3(64 * TF_ATTN_Q2_WAVES), 0, st, (const h16*)q, (const h16*)k, (const h16*)v,
+        hipLaunchKernelGGL((attn_split_q2_kernel<D>), grid, block, 0, st, (const h16*)q, (const h16*)k, (const h16*)v,
                            sk_dev, sq, sk, H, nsplit, (int)stride_t, (int)stride_h, scale, ws, tickets, (h16*)out, osm, osk);
     else
-#endif
-    if (!launched)
         hipLaunchKernelGGL((attn_split_kernel<D, QT>), grid, block, 0, st, (const h16*)q, (const h16*)k, (const h16*)v,
                            sk_dev, sq, sk, H, nsplit, (int)stride_t, (int)stride_h, scale, ws, tickets, (h16*)out, osm, osk);
     TF_LAUNCH_CHECK();
@@ -2248,7 +2011,7 @@ static int launch_block(const void* q, const void* k, const void* v, void* out, 
                         int sq, int sk, int H, float scale, int nsplit, float* ws, const uint32_t* mask,
                         int mask_words, int mask_row0, int tree_start, hipStream_t st) {
     const int rg = sq <= 32 ? 1 : (sq <= 64 ? 2 : 4);
-    if (rg == 4 && !TF_BLOCK_NO_LDS) {
+    if (rg == 4) {
         static bool attr_set = false;                     // 70 KiB of dynamic LDS: above the 64 KiB default limit
         if (!attr_set) {
             hipError_t e = hipFuncSetAttribute((const void*)attn_block_lds_kernel<D, TREE>,
