@@ -335,9 +335,13 @@ int tf_skinny_qkv_rope(const void* wqkv_packed, const void* x, int64_t ldx, cons
  *     fragments of 64 B.  The decode layer keeps its residual stream, attention output and SwiGLU output in this form
  *     when a block has more than 16 rows (the gamma = 16 verifies of offloading_TP.py: tensor_op.py:276-328,346-360).
  * The fp32 logits of out_f32 != 0 stay row-major (ys_m = row stride, ys_k ignored); q_out of the q|k|v form stays
- * [M][H][D].  tf_sg_tune: A/B knobs of the launch rule (key 0: rows from which a wave multiplies TWO weight panels
- * against one B operand, 33 = never; key 1: waves per workgroup of that form, 4 or 8; key 2: smallest halved grid,
- * panels / 2, that takes it); returns the previous value, -1 for an unknown key. */
+ * [M][H][D].  tf_sg_tune: A/B knobs of the launch rule (csrc/sg_rule.h; key 0: rows from which a wave multiplies TWO
+ * weight panels against one B operand, 33 = never; key 2: smallest halved grid, panels / 2, that takes that form; keys
+ * 3-5: see tf_sg_workspace and sg_rule.h); returns the previous value, -1 for an unknown key.  Keys 1 (8 waves for the
+ * two-panel form), 6 (twice the weights in flight) and 7 (batch of the narrow-panel form) are unknown keys now: those
+ * variants are not buildable any more; code in the history of csrc/gemv.hip at the parent of the commit that retired
+ * them; measurements in profiles/r04_draft_lm_head_launch_forms.jsonl, r04_gemm_layout_ab.jsonl and
+ * r04_gemm_deep_prefetch_ab.jsonl. */
 int tf_skinny_gemm_act(const void* w_packed, const void* x, int64_t xs_m, int64_t xs_k, const void* ln_w, float eps,
                        const float* ss_in, const void* resid, int64_t rs_m, int64_t rs_k, float* ss_out, void* y,
                        int64_t ys_m, int64_t ys_k, int M, int N, int K, int out_f32, void* stream);
@@ -358,8 +362,7 @@ int tf_sg_tune(int key, int value);
  * panel of the q and k sections = rows d0..d0+3 and d0+D/2..d0+D/2+3 of one head).  Same operands, layouts and rounding
  * points as tf_skinny_gemm_swiglu_act / tf_skinny_qkv_rope_act; requires ln_w (norm prologue), M <= 24, K % 64 == 0,
  * K >= 1024 — otherwise -EINVAL and the caller keeps the 16-row form.  Results agree with the 16-row form to fp32
- * summation order (the K sum is taken even | odd chunk first), not bit for bit.  tf_sg_tune key 7: super-chunks per batch
- * (0 = rule, 5, 8). */
+ * summation order (the K sum is taken even | odd chunk first), not bit for bit. */
 int tf_skinny_gemm_swiglu_n8(const void* gate_n8, const void* up_n8, const void* x, int64_t xs_m, int64_t xs_k,
                              const void* ln_w, float eps, const float* ss_in, void* act, int64_t ys_m, int64_t ys_k,
                              int M, int I, int K, void* stream);

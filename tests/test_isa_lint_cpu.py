@@ -61,8 +61,8 @@ _Zk: ; @_Zk
     shapes = isa_lint.prologue_shape(isa_lint.compile_to_asm(os.path.join(CSRC, "gemv.hip"), extra=extra))
     norm = {k: v for k, v in shapes.items() if k.startswith("_Z18skinny_gemm_kernelILi1E") and "ELb1ELi" in k[:40]
             and v.get("loads_before_first_wait") is not None}
-    # one row tile, norm prologue, no K split across workgroups, UX = 1: q|k|v / gate|up / lm_head forms at 4 and 8 waves
-    hot = {k: v for k, v in norm.items() if "ELb0ELb0ELi1EE" in k}
+    # one row tile, norm prologue, no K split across workgroups, no exchange: q|k|v / gate|up / lm_head forms at 4 and 8 waves
+    hot = {k: v for k, v in norm.items() if "ELb0ELb0EEv" in k}
     assert len(hot) >= 8, sorted(norm)[:4]
     for k, v in hot.items():
         assert v.get("preload") == 14, (k, v)

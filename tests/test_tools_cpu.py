@@ -201,10 +201,10 @@ def test_build_variant_command_line(monkeypatch):
     monkeypatch.setattr(tb.subprocess, "run", lambda cmd, check=True: seen.append(list(cmd)))
     monkeypatch.setattr(tb, "hipcc_path", lambda: "hipcc")
     assert "-amdgpu-kernarg-preload-count=14" in tb.FLAGS and tb.FLAGS[tb.FLAGS.index("-amdgpu-kernarg-preload-count=14") - 1] == "-mllvm"
-    out = tb.build_variant("t1", ["SG_LN_PRE=1", "-save-temps"], verbose=False)
+    out = tb.build_variant("t1", ["SG_STAMPS=1", "-save-temps"], verbose=False)
     assert out.endswith("libtriforce_hip_t1.so")
     cmd = seen[-1]
-    assert "-DSG_LN_PRE=1" in cmd and "-save-temps" in cmd and "-amdgpu-kernarg-preload-count=14" in cmd
+    assert "-DSG_STAMPS=1" in cmd and "-save-temps" in cmd and "-amdgpu-kernarg-preload-count=14" in cmd
     assert cmd[-2:] == ["-o", out] and any(c.endswith("gemv.hip") for c in cmd)
     tb.build_variant("t2", ["!kernarg-preload"], verbose=False)
     cmd = seen[-1]

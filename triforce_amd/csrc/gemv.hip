@@ -23,49 +23,11 @@
 //     inside one 16-row panel, so the epilogue rotates q / k in registers (one cross-lane exchange) and writes q
 //     to [M][H][D] and the k / v rows straight into the cache slots.
 #include "common.h"
+#include "sg_rule.h"   // the launch rule: which form a shape gets (host-testable)
 
-#ifdef TF_NO_NT
-#define SG_LOAD(p) (*(p))
-#else
 #define SG_LOAD(p) __builtin_nontemporal_load(p)   // weights are read once per forward: non-temporal
-#endif
 
-// Waves per workgroup = K-splits of one 16-row panel.  A wave keeps SG_U KiB of weights in flight, so a grid of
-// few panels (o_proj / down_proj: N = 4096 -> 256 workgroups, one per CU) needs more waves per panel to cover the
-// HBM latency-bandwidth product (cold-cache graph replay, tools/tune.py): o_proj 9.0 -> 7.6 us, down_proj 20.8 ->
-// 18.3 us with 8 waves per panel; 16 waves measured the same as 8.
-#ifndef SG_WAVES
-#define SG_WAVES 4
-#endif
-#ifndef SG_WAVES_WIDE
-#define SG_WAVES_WIDE 8
-#endif
-#ifndef SG_WIDE_MAX_PANELS
-#define SG_WIDE_MAX_PANELS 512   // <= 2 workgroups per CU -> use the wide (more K-splits) variant
-#endif
-#ifndef SG_U
-#define SG_U 4              // k-chunks (KiB of weights) in flight per wave
-#endif
-#ifndef SG_TAIL_BATCH
-#define SG_TAIL_BATCH 1         // 1: the last 1..U-1 k-chunks of a wave as one batch of loads (round 4); 0: one chunk at a time
-#endif
-#ifndef SG_LN_PRE
-#define SG_LN_PRE 0             // 1: the first batch's norm weights are loaded with the prologue too (+16 registers: the one-tile
-                                // gate|up form drops from 4 to 3 waves per SIMD)
-#endif
-#ifndef SG_EPI_LATE
-#define SG_EPI_LATE 1           // forms without a norm prologue fetch their epilogue operands behind the first weight batch
-#endif
-#ifndef SG_PROLOGUE_ORDER
-#define SG_PROLOGUE_ORDER 2     // 2: norm partials, x rows, norm weights, weights in ONE basic block (unconditional loads,
-                                // pinned in front of the fold); 1: the same order behind branches — which the compiler
-                                // threads into "partials, WAIT, fold, then the rest"; 0: weights first, x after the fold (round 3)
-#endif
-#ifndef TF_SG_RES_EARLY
-#define TF_SG_RES_EARLY 1   // residual epilogue operands fetched before the weight loop (0: at the tail, round 2's form)
-#endif
-
-enum { SG_PLAIN = 0, SG_GATEUP = 1, SG_F32 = 2, SG_QKV = 3 };
+constexpr int SG_U = 4;   // k-chunks (KiB of weights) in flight per wave of the one-panel, one-stream forms
 
 // Activation layout (round 4).  Every activation operand is addressed through two element strides,
 //     element (m, k) at base[m * sm + (k / 8) * sk + (k % 8)],
@@ -78,15 +40,6 @@ struct SgAct {
     int64_t sm, sk;
 };
 
-// P = panels per wave: a wave that multiplies P weight panels against ONE B operand reads x once per P KiB of weights
-// (x traffic through L2 -> L1 is panels * M * K * 2 bytes: as large as the weight stream itself at 17 rows with P = 1).
-// Measured (profiles/r04_gemm_layout_ab.jsonl, k-octet-major x): P = 2 pays when the halved grid still puts two
-// workgroups on most CUs — 13B q|k|v (480 groups) 32.0 -> 27.6 us at 17 rows, 26.9 -> 25.2 at 8; 13B gate|up (432)
-// 49.8 -> 47.5 / 48.4 -> 44.7 — and LOSES below that: 7B q|k|v (384 groups) 20.5 -> 23.4, 7B gate|up (344) 32.2 -> 35.4.
-// With 4 waves per workgroup it is bit-identical to the P = 1 form (same K ranges per wave, same merge order).
-#ifndef SG_P_WIDE_MIN_GROUPS
-#define SG_P_WIDE_MIN_GROUPS 420
-#endif
 // K split ACROSS workgroups (round 4).  A GEMM with few output panels — the q|k|v and gate|up shards of a tensor-parallel
 // rank: 96 / 86 panels at 7B TP 8 — ran one workgroup per panel, i.e. on 86-96 of the 256 CUs: 13.2 / 9.1 us for 22.5 /
 // 12.6 MB (1.7 / 1.4 TB/s, profiles/r04_tp8_7b_kernel_timeline_before.json).  With gridDim.y = KS workgroups per panel
@@ -95,8 +48,6 @@ struct SgAct {
 // reads all KS partials back (agent-scope loads), adds them IN SPLIT ORDER (deterministic whoever arrives last) and runs
 // the epilogue.  Same hand-off as the one-launch attention merge (csrc/attn.hip).  The workspace (tickets first) belongs
 // to the caller: tf_sg_workspace registers one per device; without it KS = 1.
-#define SG_KSPLIT_MAX 4
-#define SG_TICKETS 4096
 struct SgKsplit {
     float* ws;            // [panel][KS][NA][MT][64][4] fp32
     unsigned* tickets;    // [SG_TICKETS], zero between launches
@@ -137,21 +88,13 @@ static int sg_slot_of(int dev, hipStream_t st) {
     g_sg_slot_stream[dev][g_sg_slots_used[dev]] = st;
     return g_sg_slots_used[dev]++;
 }
-// Measured (profiles/r04_tp_shard_structural_ab.jsonl, r04_tp8_7b_kernel_timeline_after_splitk.json): NO gain in situ — the
-// 7B TP-8 gate|up GEMM stays at 13.2 us with 258 workgroups instead of 86, q|k|v goes 9.1 -> 10.9 us: at 12-22 MB these
-// launches are made of fixed costs (dispatch, the norm prologue's dependent loads, merge, epilogue, drain), not of the
-// stream the extra CUs would shorten, and the hand-off adds a round trip.  Default off (0); tf_sg_tune key 3 turns it on.
-// Measured (profiles/r04_gemm_deep_prefetch_ab.jsonl) and OFF: twice the bytes per trip halves the trips but not the time —
-// 7B TP-8 gate|up K loop 7.3 -> 6.4 us with the prologue 0.8 us longer, workgroup lifetime 11.0 us either way; retrieval verify
-// 1 671 -> 1 685 us, 13B TP 8 3 109 -> 3 200.  The K loop of a few-panel GEMM is bound by what ONE CU can pull (~37 GB/s:
-// 256 KiB in 7 us, whatever is in flight), not by the number of round trips.
-static int g_sg_deep_panels = 0;           // grids of up to this many panels (and K >= 2048) keep twice the weights in flight per wave (key 6)
-static int g_sg_few_panels = 200;          // gate|up GEMMs of up to this many panels run 8 waves per panel at two row tiles (tf_sg_tune key 5)
-static int g_sg_ksplit_force = 0;          // tf_sg_tune key 4 (A/B): > 1 that many K-splits across workgroups for EVERY P = 1 GEMM,
-                                           // 1 never split, 0 the rule in sg_pick_ksplit
-static int g_sg_ksplit_max_groups = 0;     // split K across workgroups below this many panel groups (tf_sg_tune key 3; 0 = never)
-static int g_sg_n8_u = 0;                  // narrow-panel form (skinny_gemm_n8_kernel), tf_sg_tune key 7 (A/B): 0 = the rule in
-                                           // launch_sg_n8, 5 / 8 = that many super-chunks per batch for every launch
+// Measured and NOT in the tree any more (profiles/r04_gemm_deep_prefetch_ab.jsonl; code in the history of this file): twice the
+// weights in flight per wave on few-panel grids halves the trips but not the time — 7B TP-8 gate|up K loop 7.3 -> 6.4 us with
+// the prologue 0.8 us longer, workgroup lifetime 11.0 us either way; retrieval verify 1 671 -> 1 685 us, 13B TP 8 3 109 -> 3 200.
+// The K loop of a few-panel GEMM is bound by what ONE CU can pull (~37 GB/s: 256 KiB in 7 us, whatever is in flight), not by
+// the number of round trips.
+
+static SgKnobs g_sg_knobs;                 // the launch rule's knobs (sg_rule.h), set through tf_sg_tune
 
 __device__ __forceinline__ void sg_st_agent(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ float sg_ld_agent(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -209,10 +152,6 @@ __device__ __forceinline__ half4 xc_ld8(const h16* p) {
                                                        __HIP_MEMORY_SCOPE_SYSTEM));
 }
 
-static int g_sg_p2_rows = 1;       // P = 2 from this many rows (tf_sg_tune key 0; 33 = never)
-static int g_sg_p2_waves = 4;      // waves per workgroup of the P = 2 form (key 1)
-static int g_sg_p2_groups = SG_P_WIDE_MIN_GROUPS;   // ... while panels / 2 >= this (key 2)
-
 struct SgRope {                       // arguments of the RoPE + KV-append epilogue (SG_QKV)
     const h16* cosb;                  // [max_pos][D] fp16
     const h16* sinb;
@@ -234,7 +173,7 @@ __device__ __forceinline__ half8 sg_normalise(half8 xv, half8 wv, float inv) {
     return o;
 }
 
-template <int MT, int MODE, bool NORM, int WAVES, int P, bool KSPLIT, bool XCHG = false, int UX = 1>
+template <int MT, int MODE, bool NORM, int WAVES, int P, bool KSPLIT, bool XCHG = false>
 // Argument order: what the PROLOGUE needs comes first, as plain pointers / scalars — weights, x and its two strides, the
 // norm partials and weights, K, M: 14 dwords, the most the hardware preloads into SGPRs with the dispatch (built with
 // -mllvm -amdgpu-kernarg-preload-count=14, triforce_amd/build.py): the first loads are issued without waiting for the
@@ -253,11 +192,8 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const half8* __
     static_assert(!XCHG || (MODE == SG_PLAIN && P == 1 && !KSPLIT), "the exchange form is the plain one-panel GEMM");
     constexpr bool GATEUP = MODE == SG_GATEUP;
     constexpr int NA = GATEUP ? 2 : 1;                       // weight streams (accumulator sets) per panel
-    // k-chunks in flight per wave and weight stream: 8 KiB of weights per wave (4 for P = NA = 1) — times UX.  UX = 2 was
-    // built for the FEW-PANEL grids (a tensor-parallel rank's shards), where a wave's K share looks like a chain of load ->
-    // wait -> MFMA round trips of ~0.9 us — 7.5 of the 11.1 us a 7B TP-8 gate|up workgroup lives (tools/gemm_stamps.py,
-    // profiles/r04_gemm_phase_stamps.json).  Measured: half the trips take as long (see g_sg_deep_panels) — off by default.
-    constexpr int U = ((P * NA >= 2) ? (8 / (P * NA)) : SG_U) * UX;
+    // k-chunks in flight per wave and weight stream: 8 KiB of weights per wave (4 for P = NA = 1)
+    constexpr int U = (P * NA >= 2) ? (8 / (P * NA)) : SG_U;
     static_assert(P <= WAVES && U >= 1, "one epilogue wave per panel");
     const int panel0 = blockIdx.x * P;                       // this workgroup's P consecutive panels
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -301,15 +237,13 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const half8* __
     // first and the x rows only after the fold: the fold then waited for the HBM loads, and the first MFMA for one more
     // round trip of x — ~1.5 us of every norm-prologue GEMM in situ (q|k|v 21.7 us in the layer against 17.8 alone).
     constexpr int SSB = MT == 1 ? 3 : 2;                     // batches of 8 partials per thread loaded up front
-    constexpr bool BPRE = MT == 1 && SG_PROLOGUE_ORDER != 0; // (two row tiles: the x prefetch would cost a wave per SIMD)
+    constexpr bool BPRE = MT == 1;                           // (two row tiles: the x prefetch would cost a wave per SIMD)
     constexpr int G = WAVES * 4;
     const int nparts = K >> 4;
     const int pg = tid >> 4, m16 = tid & 15;
     float ssv[MT][SSB][8], part0[MT];
-    constexpr bool LNPRE = BPRE && SG_PROLOGUE_ORDER == 2 && SG_LN_PRE != 0;   // norm weights of the first batch fetched up front
-    half8 a_pre[U][P][NA], b_pre[BPRE ? U : 1][MT], ln_pre[LNPRE ? U : 1];
+    half8 a_pre[U][P][NA], b_pre[BPRE ? U : 1][MT];
     const bool pre = NORM && (c0 + U <= c1);
-#if SG_PROLOGUE_ORDER == 2
     if constexpr (NORM) {
         // ONE basic block: every load below is unconditional (clamped index + select; a null ss_in reads the head of the
         // weights instead — the values are not used), nothing between them can wait, and the block is pinned in front of
@@ -338,7 +272,6 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const half8* __
                     const half8 v = load_half8(xr[t] + xcs * cu);
                     b_pre[u][t] = xok[t] ? v : zero8;
                 }
-                if constexpr (LNPRE) ln_pre[u] = load_half8(ln_w + 32 * cu + 8 * g);
             }
         }
 #pragma unroll
@@ -368,47 +301,6 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const half8* __
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-#else
-#if SG_PROLOGUE_ORDER == 0
-    if (pre) {                                               // round 3's order (A/B): weights first
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int j = 0; j < P; ++j) {
-                a_pre[u][j][0] = SG_LOAD(wa + j * pstride + (int64_t)(c0 + u) * 64);
-                if (GATEUP) a_pre[u][j][NA - 1] = SG_LOAD(wu + j * pstride + (int64_t)(c0 + u) * 64);
-            }
-    }
-#endif
-    if (NORM && ss_in) {
-#pragma unroll
-        for (int t = 0; t < MT; ++t)
-#pragma unroll
-            for (int bb = 0; bb < SSB; ++bb)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int p = pg + bb * 8 * G + j * G;
-                    ssv[t][bb][j] = (p < nparts) ? ss_in[(int64_t)p * 32 + t * 16 + m16] : 0.f;
-                }
-    }
-#if SG_PROLOGUE_ORDER != 0
-    if (pre) {
-        if constexpr (BPRE) {
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int t = 0; t < MT; ++t) b_pre[u][t] = xok[t] ? load_half8(xr[t] + xcs * (c0 + u)) : zero8;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int j = 0; j < P; ++j) {
-                a_pre[u][j][0] = SG_LOAD(wa + j * pstride + (int64_t)(c0 + u) * 64);
-                if (GATEUP) a_pre[u][j][NA - 1] = SG_LOAD(wu + j * pstride + (int64_t)(c0 + u) * 64);
-            }
-    }
-#endif
-#endif
 
     SG_STAMP(1);
     float inv[MT];
@@ -423,17 +315,7 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const half8* __
             float* red = &sm[0][0][0][0][0];                            // reuse the merge buffer: [MT][G][16] floats
 #pragma unroll
             for (int t = 0; t < MT; ++t) {
-#if SG_PROLOGUE_ORDER == 2
                 float part = part0[t];                                  // summed next to the loads (see there)
-#else
-                float part = 0.f;
-#pragma unroll
-                for (int bb = 0; bb < SSB; ++bb)                        // (same order of additions as the loop below)
-                    if (pg + bb * 8 * G < nparts) {
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) part += ssv[t][bb][j];
-                    }
-#endif
                 for (int p0 = pg + SSB * 8 * G; p0 < nparts; p0 += 8 * G) {
                     float v[8];
 #pragma unroll
@@ -548,7 +430,7 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const half8* __
         // (resid may alias y: every element is read and written by the same lane only.)
         r_off = (int64_t)(2 * panel + (g >> 1)) * ra.sk + 4 * (g & 1);   // this lane's 4 columns, piece form
         y_off = (int64_t)(2 * panel + (g >> 1)) * ya.sk + 4 * (g & 1);
-        res_early = TF_SG_RES_EARLY && MODE == SG_PLAIN && resid != nullptr && epi && (ra.sm % 4) == 0 &&
+        res_early = MODE == SG_PLAIN && resid != nullptr && epi && (ra.sm % 4) == 0 &&
                     (ra.sk % 4) == 0 && (reinterpret_cast<uintptr_t>(resid) % 8) == 0;
         if (res_early) {
 #pragma unroll
@@ -559,7 +441,7 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const half8* __
             }
         }
     };
-    constexpr bool EPI_LATE = !NORM && SG_EPI_LATE != 0;         // prefetch_epi inside the first K batch
+    constexpr bool EPI_LATE = !NORM;                             // prefetch_epi inside the first K batch
     if (!EPI_LATE || !(c0 + U <= c1)) prefetch_epi();
 
     int c = c0;
@@ -582,9 +464,7 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const half8* __
                 if (BPRE && NORM && c == c0 && pre) b[u][t] = b_pre[BPRE ? u : 0][t];
                 else b[u][t] = xok[t] ? load_half8(xr[t] + xcs * (c + u)) : zero8;
                 if (NORM) {
-                    half8 lw;
-                    if (LNPRE && c == c0 && pre) lw = ln_pre[LNPRE ? u : 0];
-                    else lw = load_half8(ln_w + 32 * (c + u) + 8 * g);
+                    const half8 lw = load_half8(ln_w + 32 * (c + u) + 8 * g);
                     b[u][t] = sg_normalise(b[u][t], lw, inv[t]);
                 }
             }
@@ -609,7 +489,7 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const half8* __
 #endif
     }
     SG_STAMP(4);
-    if constexpr (NORM || !SG_TAIL_BATCH) {
+    if constexpr (NORM) {
         // (norm-prologue forms: K = hidden, whose k-chunks divide evenly among the waves in every configuration that
         //  matters; the batch below would only cost them registers — a wave per SIMD on the gate|up form)
         for (; c < c1; ++c) {
@@ -915,7 +795,7 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const half8* __
 // arithmetic); the K sum is taken in another order (even | odd chunks, then the waves), so results agree with the 16-row
 // form to fp32-summation noise, not bit for bit — both are checked against the oracle at the same tolerance.
 // Every wave issues ALL loads of a batch up front; registers are not a constraint here (<= 1 workgroup per CU by design).
-template <int MT, int MODE, bool NORM, int WAVES, int U>
+template <int MT, int MODE, int WAVES, int U>
 __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_n8_kernel(const half8* __restrict__ wp,
                                                                     const half8* __restrict__ wp_up,
                                                                     const h16* __restrict__ x,
@@ -955,7 +835,7 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_n8_kernel(const half8*
         xok[t] = m < M;
         xr[t] = x + (int64_t)(xok[t] ? m : 0) * xa_sm + (int64_t)(4 * par + g) * sk;
     }
-    const h16* lnp = NORM ? (ln_w + 32 * par + 8 * g) : nullptr;
+    const h16* lnp = ln_w + 32 * par + 8 * g;
     const half8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
 
     // ---- prologue: every load of the norm partials and of the first batch in ONE basic block (see skinny_gemm_kernel) ----
@@ -967,19 +847,17 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_n8_kernel(const half8*
     half8 a[U][NA], b[U][MT], lw[U];
     const int last = max(c1 - 1, 0);
     {
-        const float* ssp = (NORM && ss_in) ? ss_in : reinterpret_cast<const float*>(wp);
-        if constexpr (NORM) {
+        const float* ssp = ss_in ? ss_in : reinterpret_cast<const float*>(wp);
 #pragma unroll
-            for (int t = 0; t < MT16; ++t)
+        for (int t = 0; t < MT16; ++t)
 #pragma unroll
-                for (int bb = 0; bb < SSB; ++bb)
+            for (int bb = 0; bb < SSB; ++bb)
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int p = pg + bb * 8 * G + j * G;
-                        const float v = ssp[(int64_t)min(p, nparts - 1) * 32 + t * 16 + m16];
-                        ssv[t][bb][j] = (p < nparts) ? v : 0.f;
-                    }
-        }
+                for (int j = 0; j < 8; ++j) {
+                    const int p = pg + bb * 8 * G + j * G;
+                    const float v = ssp[(int64_t)min(p, nparts - 1) * 32 + t * 16 + m16];
+                    ssv[t][bb][j] = (p < nparts) ? v : 0.f;
+                }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int cu = min(c0 + u, last);
@@ -988,7 +866,7 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_n8_kernel(const half8*
                 const half8 v = load_half8(xr[t] + xcs * cu);
                 b[u][t] = xok[t] ? v : zero8;
             }
-            if constexpr (NORM) lw[u] = load_half8(lnp + 64 * cu);
+            lw[u] = load_half8(lnp + 64 * cu);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -998,92 +876,87 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_n8_kernel(const half8*
         }
         asm volatile("" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (NORM) {
 #pragma unroll
-            for (int t = 0; t < MT16; ++t) {
-                float part = 0.f;
+        for (int t = 0; t < MT16; ++t) {
+            float part = 0.f;
 #pragma unroll
-                for (int bb = 0; bb < SSB; ++bb)
+            for (int bb = 0; bb < SSB; ++bb)
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) part += ssv[t][bb][j];
-                asm volatile("" : "+v"(part));                  // the fold's first additions stay in front of everything else
-                part0[t] = part;
-            }
-            __builtin_amdgcn_sched_barrier(0);
+                for (int j = 0; j < 8; ++j) part += ssv[t][bb][j];
+            asm volatile("" : "+v"(part));                      // the fold's first additions stay in front of everything else
+            part0[t] = part;
         }
+        __builtin_amdgcn_sched_barrier(0);
     }
 
-    float inv[MT];
+    float inv[MT], tot[MT];
 #pragma unroll
-    for (int t = 0; t < MT; ++t) inv[t] = 1.f;
-    if constexpr (NORM) {
-        float tot[MT];
-        if (ss_in) {
-            // per-panel sums of squares left by the producer of x (residual-epilogue GEMM / exchange): fold in a fixed order
+    for (int t = 0; t < MT; ++t) inv[t] = 1.f;    // (dead, and kept: without it the compiler orders the prologue of 8 of the 11 forms differently)
+    if (ss_in) {
+        // per-panel sums of squares left by the producer of x (residual-epilogue GEMM / exchange): fold in a fixed order
 #pragma unroll
-            for (int t = 0; t < MT16; ++t) {
-                float part = part0[t];
-                for (int p0 = pg + SSB * 8 * G; p0 < nparts; p0 += 8 * G) {
-                    float v[8];
+        for (int t = 0; t < MT16; ++t) {
+            float part = part0[t];
+            for (int p0 = pg + SSB * 8 * G; p0 < nparts; p0 += 8 * G) {
+                float v[8];
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int p = p0 + j * G;
-                        v[j] = (p < nparts) ? ss_in[(int64_t)p * 32 + t * 16 + m16] : 0.f;
-                    }
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) part += v[j];
+                for (int j = 0; j < 8; ++j) {
+                    const int p = p0 + j * G;
+                    v[j] = (p < nparts) ? ss_in[(int64_t)p * 32 + t * 16 + m16] : 0.f;
                 }
-                red[t][pg][m16] = part;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) part += v[j];
             }
-            __syncthreads();
+            red[t][pg][m16] = part;
+        }
+        __syncthreads();
 #pragma unroll
-            for (int t = 0; t < MT; ++t) {
-                const int row = t * 8 + lr;
-                tot[t] = 0.f;
-                for (int j = 0; j < G; ++j) tot[t] += red[row >> 4][j][row & 15];
-            }
-        } else {
-            // no hand-off (layer 0): this wave's share of sum(x^2) over ALL of K, then across the waves
-            float ss[MT];
+        for (int t = 0; t < MT; ++t) {
+            const int row = t * 8 + lr;
+            tot[t] = 0.f;
+            for (int j = 0; j < G; ++j) tot[t] += red[row >> 4][j][row & 15];
+        }
+    } else {
+        // no hand-off (layer 0): this wave's share of sum(x^2) over ALL of K, then across the waves
+        float ss[MT];
 #pragma unroll
-            for (int t = 0; t < MT; ++t) ss[t] = 0.f;
-            for (int cc = c0; cc < c1; cc += 4) {
-                half8 v[4][MT];
+        for (int t = 0; t < MT; ++t) ss[t] = 0.f;
+        for (int cc = c0; cc < c1; cc += 4) {
+            half8 v[4][MT];
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
+            for (int j = 0; j < 4; ++j)
 #pragma unroll
-                    for (int t = 0; t < MT; ++t) {
-                        const half8 q = load_half8(xr[t] + xcs * min(cc + j, last));
-                        v[j][t] = (xok[t] && cc + j < c1) ? q : zero8;
+                for (int t = 0; t < MT; ++t) {
+                    const half8 q = load_half8(xr[t] + xcs * min(cc + j, last));
+                    v[j][t] = (xok[t] && cc + j < c1) ? q : zero8;
+                }
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int t = 0; t < MT; ++t)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const float f = (float)v[j][t][e];
+                        ss[t] = fmaf(f, f, ss[t]);
                     }
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int t = 0; t < MT; ++t)
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            const float f = (float)v[j][t][e];
-                            ss[t] = fmaf(f, f, ss[t]);
-                        }
-            }
-#pragma unroll
-            for (int t = 0; t < MT; ++t) {
-                ss[t] += __shfl_xor(ss[t], 8, 64);              // the two stacked chunks
-                ss[t] += __shfl_xor(ss[t], 16, 64);             // the four k-octets
-                ss[t] += __shfl_xor(ss[t], 32, 64);
-                if (lane < 8) sm_ss[wave][t * 8 + lane] = ss[t];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int t = 0; t < MT; ++t) {
-                tot[t] = 0.f;
-#pragma unroll
-                for (int w = 0; w < WAVES; ++w) tot[t] += sm_ss[w][t * 8 + lr];
-            }
         }
 #pragma unroll
-        for (int t = 0; t < MT; ++t) inv[t] = 1.0f / sqrtf(tot[t] / (float)K + eps);
+        for (int t = 0; t < MT; ++t) {
+            ss[t] += __shfl_xor(ss[t], 8, 64);              // the two stacked chunks
+            ss[t] += __shfl_xor(ss[t], 16, 64);             // the four k-octets
+            ss[t] += __shfl_xor(ss[t], 32, 64);
+            if (lane < 8) sm_ss[wave][t * 8 + lane] = ss[t];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < MT; ++t) {
+            tot[t] = 0.f;
+#pragma unroll
+            for (int w = 0; w < WAVES; ++w) tot[t] += sm_ss[w][t * 8 + lr];
+        }
     }
+#pragma unroll
+    for (int t = 0; t < MT; ++t) inv[t] = 1.0f / sqrtf(tot[t] / (float)K + eps);
 
     // RoPE tables of this lane's output columns (positions -> table: two dependent loads, fetched under the K loop)
     const bool epi = wave == 0;
@@ -1111,7 +984,7 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_n8_kernel(const half8*
             if (c + u < c1) {
 #pragma unroll
                 for (int t = 0; t < MT; ++t) {
-                    const half8 bn = NORM ? sg_normalise(b[u][t], lw[u], inv[t]) : b[u][t];
+                    const half8 bn = sg_normalise(b[u][t], lw[u], inv[t]);
 #pragma unroll
                     for (int aa = 0; aa < NA; ++aa)
                         acc[aa][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[u][aa], bn, acc[aa][t], 0, 0, 0);
@@ -1131,7 +1004,7 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_n8_kernel(const half8*
                 const half8 v = load_half8(xr[t] + xcs * cu);
                 b[u][t] = xok[t] ? v : zero8;
             }
-            if constexpr (NORM) lw[u] = load_half8(lnp + 64 * cu);
+            lw[u] = load_half8(lnp + 64 * cu);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -1244,42 +1117,25 @@ struct SgArgs {                       // one GEMM call: operands with their layo
     float* ss_out;
 };
 
-// Workgroups per panel group along K: only few-panel grids (see SgKsplit), only with a registered workspace that holds the
-// partials, and only while every wave of every workgroup still gets >= 2 k-chunks.
-template <int MT, int NA, int WAVES, int P>
-static int sg_pick_ksplit(const SgArgs& a, SgKsplit& kx, hipStream_t st = nullptr) {
-    kx = SgKsplit{nullptr, nullptr, nullptr};
+// Cycle-stamp buffer of the instrumented build (-DSG_STAMPS=1, tools/gemm_stamps.py): behind the first 4 MiB of a
+// registered workspace of >= 6 MiB; null in every other build.
+static unsigned long long* sg_stamps_ptr() {
 #if SG_STAMPS
-    {
-        int d0 = 0;
-        if (hipGetDevice(&d0) == hipSuccess && d0 >= 0 && d0 < 16 && g_sg_ws[d0] && g_sg_ws_bytes[d0] >= (6 << 20))
-            kx.stamps = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(g_sg_ws[d0]) + (4 << 20));
-    }
-#endif
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16 || !g_sg_ws[dev]) return 1;
-    const int panels = a.N / 16, groups = panels / P, nchunks = a.K >> 5;
-    if (panels > SG_TICKETS) return 1;
-    int ks;
-    if (g_sg_ksplit_force > 1) {                       // A/B (tf_sg_tune key 4): this many workgroups per panel, any grid
-        ks = g_sg_ksplit_force;
-    } else if (g_sg_ksplit_force == 1) {               // ... or never
-        return 1;
-    } else if (panels > 256 && panels <= 384 && nchunks >= 256) {
-        // The one regime where the split pays (profiles/r04_gemm_ksplit_force_ab.jsonl): a grid a little larger than the
-        // chip — 13B down_proj: 320 panels on 256 CUs, 64 CUs hold two workgroups and set the pace — with a LONG K
-        // (432 k-chunks, 141.6 MB).  Three K-splits (960 workgroups, even): 41.8 -> 34.8 us at 17 rows, 32.4 -> 28.5 at 8,
-        // 48.4 -> 39.8 at 32.  With a short K (13B o_proj, 160 k-chunks: 16.3 -> 19.2) or a grid that already fits
-        // (7B: 256 panels) it loses.
-        ks = 3;
-    } else {
-        if (groups >= g_sg_ksplit_max_groups) return 1;
-        ks = (256 + groups - 1) / groups;
-    }
-    if (ks > SG_KSPLIT_MAX) ks = SG_KSPLIT_MAX;
-    while (ks > 1 && nchunks / ks < 2 * WAVES) --ks;
-    if (ks <= 1) return 1;
-    const int64_t need = (int64_t)SG_TICKETS * 4 + (int64_t)panels * ks * NA * MT * 256 * 4;
+    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16 && g_sg_ws[dev] && g_sg_ws_bytes[dev] >= (6 << 20))
+        return reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(g_sg_ws[dev]) + (4 << 20));
+#endif
+    return nullptr;
+}
+
+// Workgroups per panel along K: what the rule asks for (sg_pick_ks), if the current device has a registered workspace
+// that holds the partials and a slot of it is free for this launch stream; else 1.
+static int sg_ksplit(const SgArgs& a, const SgForm& f, int mode, SgKsplit& kx, hipStream_t st) {
+    const int panels = a.N / 16, NA = mode == SG_GATEUP ? 2 : 1;
+    const int ks = sg_pick_ks(panels, f.P, a.K >> 5, f.WAVES, mode, g_sg_knobs);
+    int dev = 0;
+    if (ks <= 1 || hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16 || !g_sg_ws[dev]) return 1;
+    const int64_t need = (int64_t)SG_TICKETS * 4 + (int64_t)panels * ks * NA * f.MT * 256 * 4;
     const int64_t slot_bytes = (g_sg_ws_bytes[dev] / SG_WS_SLOTS) & ~(int64_t)255;
     if (need > slot_bytes) return 1;
     const int slot = sg_slot_of(dev, st);
@@ -1290,82 +1146,49 @@ static int sg_pick_ksplit(const SgArgs& a, SgKsplit& kx, hipStream_t st = nullpt
     return ks;
 }
 
-template <int MT, int MODE, bool NORM, int WAVES, int P, int UX = 1>
-static void launch_sg_w(const SgArgs& a, const SgRope& rp, hipStream_t st) {
-    SgKsplit kx = {nullptr, nullptr, nullptr};
-    if constexpr (UX > 1) {
-        sg_pick_ksplit<MT, (MODE == SG_GATEUP ? 2 : 1), WAVES, P>(a, kx);      // (stamps pointer of the instrumented build)
-        kx.ws = nullptr, kx.tickets = nullptr;
-        hipLaunchKernelGGL((skinny_gemm_kernel<MT, MODE, NORM, WAVES, P, false, false, UX>), dim3(a.N / 16 / P), dim3(WAVES * 64),
-                           0, st, (const half8*)a.wp, (const half8*)a.wp_up, (const h16*)a.x, a.ss_in, (const h16*)a.ln_w, a.K, a.M,
-                           (int)a.xa.sm, (int)a.xa.sk, a.eps, a.N, (const h16*)a.resid, a.ra, a.y, a.ya, rp, a.ss_out, kx, SgXchg{});
-        return;
-    }
-    if constexpr (P == 1 && MODE != SG_F32) {                     // few-panel grids only: never the P = 2 form, never lm_head
-        const int ks = sg_pick_ksplit<MT, (MODE == SG_GATEUP ? 2 : 1), WAVES, P>(a, kx, st);
-        if (ks > 1) {
-            hipLaunchKernelGGL((skinny_gemm_kernel<MT, MODE, NORM, WAVES, P, true>), dim3(a.N / 16 / P, ks), dim3(WAVES * 64),
-                               0, st, (const half8*)a.wp, (const half8*)a.wp_up, (const h16*)a.x, a.ss_in, (const h16*)a.ln_w, a.K, a.M,
-                               (int)a.xa.sm, (int)a.xa.sk, a.eps, a.N, (const h16*)a.resid, a.ra, a.y, a.ya, rp, a.ss_out, kx,
-                               SgXchg{});
-            return;
+// One form of launch_sg's list.  What the rule cannot return for this MODE is not instantiated: gate|up takes 8 waves at two
+// row tiles only; two panels per wave and lm_head are never split.
+template <int MT, int MODE, bool NORM, int WAVES, int P>
+static int launch_sg_form(const SgArgs& a, const SgRope& rp, const SgKsplit& kx, int ks, hipStream_t st) {
+    constexpr bool REACHABLE = MODE != SG_GATEUP || WAVES == SG_WAVES || MT == 2;
+    constexpr bool CAN_SPLIT = P == 1 && MODE != SG_F32;
+#define SG_LAUNCH(KSPLIT_)                                                                                                 \
+    hipLaunchKernelGGL((skinny_gemm_kernel<MT, MODE, NORM, WAVES, P, KSPLIT_>), dim3(a.N / 16 / P, ks), dim3(WAVES * 64), 0, \
+                       st, (const half8*)a.wp, (const half8*)a.wp_up, (const h16*)a.x, a.ss_in, (const h16*)a.ln_w, a.K,  \
+                       a.M, (int)a.xa.sm, (int)a.xa.sk, a.eps, a.N, (const h16*)a.resid, a.ra, a.y, a.ya, rp, a.ss_out,  \
+                       kx, SgXchg{})
+    if constexpr (!REACHABLE) {
+        return TF_EINVAL;
+    } else {
+        if (ks == 1) {
+            SG_LAUNCH(false);
+        } else if constexpr (CAN_SPLIT) {
+            SG_LAUNCH(true);
+        } else {
+            return TF_EINVAL;
         }
+        TF_LAUNCH_CHECK();
+        return TF_OK;
     }
-    hipLaunchKernelGGL((skinny_gemm_kernel<MT, MODE, NORM, WAVES, P, false>), dim3(a.N / 16 / P), dim3(WAVES * 64), 0, st,
-                       (const half8*)a.wp, (const half8*)a.wp_up, (const h16*)a.x, a.ss_in, (const h16*)a.ln_w, a.K, a.M,
-                       (int)a.xa.sm, (int)a.xa.sk, a.eps, a.N, (const h16*)a.resid, a.ra, a.y, a.ya, rp, a.ss_out, kx, SgXchg{});
+#undef SG_LAUNCH
 }
 
 template <int MODE, bool NORM>
 static int launch_sg(const SgArgs& a, const SgRope& rp, hipStream_t st) {
-    const int panels = a.N / 16, nchunks = a.K >> 5;
-    // two panels per wave (x read once per 2 KiB of weights): from g_sg_p2_rows activation rows up, while the halved
-    // grid still covers every CU; the 8 waves of such a workgroup split K.
-    const bool p2 = a.M >= g_sg_p2_rows && (panels % 2) == 0 && panels / 2 >= g_sg_p2_groups && nchunks >= 16;
-    if (p2) {
-        if (g_sg_p2_waves == 4) {
-            if (a.M <= 16) launch_sg_w<1, MODE, NORM, 4, 2>(a, rp, st);
-            else launch_sg_w<2, MODE, NORM, 4, 2>(a, rp, st);
-        } else {
-            if (a.M <= 16) launch_sg_w<1, MODE, NORM, 8, 2>(a, rp, st);
-            else launch_sg_w<2, MODE, NORM, 8, 2>(a, rp, st);
-        }
-        TF_LAUNCH_CHECK();
-        return TF_OK;
-    }
-    // Few-panel gate|up GEMMs at two row tiles (a tensor-parallel rank's shard at 17-32 rows: 108 panel pairs at 13B TP 8)
-    // run 8 waves per panel like the other few-panel forms, not 4: 13B TP-8 retrieval verify 3 421 -> 3 215 us, target
-    // verify 5 492 -> 5 278 (profiles/r04_tp_shard_waves_tail_ab.jsonl).  At ONE row tile more waves per panel were
-    // measured and lose (16 waves: 7B TP-8 retrieval verify 1 877 -> 1 925 us; q|k|v 10.0 -> 10.9 us, gate|up 13.8 ->
-    // 13.9): those launches are not bound by the length of a wave's K chain.  tf_sg_tune key 5 = largest panel count that
-    // takes the form (0: never).
-    constexpr bool CAN_DEEP = MODE != SG_F32;
-    const bool deep = CAN_DEEP && panels <= g_sg_deep_panels && nchunks >= 64;    // few panels, long K: UX = 2 (see the kernel)
-    if (MODE == SG_GATEUP && a.M > 16 && panels <= g_sg_few_panels && nchunks >= 32) {
-        launch_sg_w<2, MODE, NORM, 8, 1>(a, rp, st);              // (UX = 2 would spill here: 256 registers + 4)
-        TF_LAUNCH_CHECK();
-        return TF_OK;
-    }
-    if (deep) {
-        constexpr int DW = MODE == SG_GATEUP ? SG_WAVES : SG_WAVES_WIDE;
-        if (a.M <= 16) launch_sg_w<1, MODE, NORM, DW, 1, (CAN_DEEP ? 2 : 1)>(a, rp, st);
-        else launch_sg_w<2, MODE, NORM, SG_WAVES_WIDE, 1, ((CAN_DEEP && MODE != SG_GATEUP) ? 2 : 1)>(a, rp, st);
-        TF_LAUNCH_CHECK();
-        return TF_OK;
-    }
-    // wide variant: few panels and enough k-chunks that every wave still gets >= 2 of them
-    constexpr bool CAN_WIDE = MODE != SG_GATEUP;
-    const bool wide = CAN_WIDE && panels <= SG_WIDE_MAX_PANELS && nchunks >= 2 * SG_WAVES_WIDE;
-    constexpr int WW = CAN_WIDE ? SG_WAVES_WIDE : SG_WAVES;
-    if (a.M <= 16) {
-        if (wide) launch_sg_w<1, MODE, NORM, WW, 1>(a, rp, st);
-        else launch_sg_w<1, MODE, NORM, SG_WAVES, 1>(a, rp, st);
-    } else {
-        if (wide) launch_sg_w<2, MODE, NORM, WW, 1>(a, rp, st);
-        else launch_sg_w<2, MODE, NORM, SG_WAVES, 1>(a, rp, st);
-    }
-    TF_LAUNCH_CHECK();
-    return TF_OK;
+    const SgForm f = sg_pick_form(MODE, NORM, a.M, a.N, a.K, g_sg_knobs);
+    // (the instrumented build stamps the forms that may split, and the exchange GEMM: no others, as before)
+    SgKsplit kx = {nullptr, nullptr, (f.P == 1 && MODE != SG_F32) ? sg_stamps_ptr() : nullptr};
+    const int ks = sg_ksplit(a, f, MODE, kx, st);
+#define SG_FORM(MT_, W_, P_) \
+    if (f.MT == MT_ && f.WAVES == W_ && f.P == P_) return launch_sg_form<MT_, MODE, NORM, W_, P_>(a, rp, kx, ks, st)
+    SG_FORM(1, SG_WAVES, 1);
+    SG_FORM(2, SG_WAVES, 1);
+    SG_FORM(1, SG_WAVES_WIDE, 1);
+    SG_FORM(2, SG_WAVES_WIDE, 1);
+    SG_FORM(1, SG_WAVES, 2);
+    SG_FORM(2, SG_WAVES, 2);
+#undef SG_FORM
+    return TF_EINVAL;                                             // a form this file does not build: the rule and the list above disagree
 }
 
 static bool sg_act_ok(const SgAct& s) { return s.sm > 0 && s.sk > 0 && (s.sm % 8) == 0 && (s.sk % 8) == 0; }
@@ -1375,17 +1198,17 @@ static bool sg_shape_ok(int M, int N, int K, const SgAct& xa) {
            xa.sm <= 0x7fffffff && xa.sk <= 0x7fffffff;     // (the kernel takes x's two strides as 32-bit arguments)
 }
 
-// A/B knobs of the launch rule (tools/gemm_layout_ab.py): key 0 = rows from which two panels per wave are used (33:
-// never), key 1 = waves per workgroup of that form (4 or 8), key 2 = smallest halved grid (panels / 2) that takes it,
-// key 3 = panel-group count below which K is also split ACROSS workgroups (0 = never).  Returns the previous value, -1 for an unknown key.
+// A/B knobs of the launch rule (SgKnobs in sg_rule.h; tools/gemm_layout_ab.py): key 0 = rows from which two panels per wave
+// are used (33: never), key 2 = smallest halved grid (panels / 2) that takes that form, key 3 = panel count below which K is
+// also split ACROSS workgroups (0 = never), key 4 = K-splits forced (1: never), key 5 = largest gate|up grid that runs 8 waves
+// per panel at two row tiles.  Keys 1, 6 and 7 set variants that are not built any more.  Returns the previous value, -1
+// for an unknown key.
 extern "C" int tf_sg_tune(int key, int value) {
-    int* slot = key == 0 ? &g_sg_p2_rows : key == 1 ? &g_sg_p2_waves : key == 2 ? &g_sg_p2_groups
-                : key == 3 ? &g_sg_ksplit_max_groups : key == 4 ? &g_sg_ksplit_force : key == 5 ? &g_sg_few_panels
-                : key == 6 ? &g_sg_deep_panels : key == 7 ? &g_sg_n8_u : nullptr;
+    SgKnobs& k = g_sg_knobs;
+    int* slot = key == 0 ? &k.p2_rows : key == 2 ? &k.p2_groups : key == 3 ? &k.ksplit_max_groups
+                : key == 4 ? &k.ksplit_force : key == 5 ? &k.few_panels : nullptr;
     if (!slot) return -1;
     const int old = *slot;
-    if (key == 1 && value != 4 && value != 8) return old;
-    if (key == 7 && value != 0 && value != 5 && value != 8) return old;
     *slot = value;
     return old;
 }
@@ -1506,10 +1329,6 @@ extern "C" int tf_skinny_qkv_rope(const void* wqkv_packed, const void* x, int64_
 // weight additionally in the 8-row rotary order (ops.rope_row_order_n8: every panel of the q and k sections holds rows
 // d0..d0+3 and their partners d0+D/2..d0+D/2+3 of one head).  Applies to <= 24 rows with a norm prologue (ln_w) and
 // K a multiple of 64 with >= 2 super-chunks per wave; anything else returns TF_EINVAL — the caller keeps the 16-row form.
-#ifndef SG_N8_WAVES
-#define SG_N8_WAVES 8          // waves per 8-row panel (A/B: variant build with SG_N8_WAVES=4)
-#endif
-
 static bool sg_n8_ok(int M, int N, int K, const SgAct& xa) {
     return M >= 1 && M <= 24 && N >= 8 && (N % 8) == 0 && K >= 64 * 2 * SG_N8_WAVES && (K % 64) == 0 && sg_act_ok(xa) &&
            xa.sm <= 0x7fffffff && xa.sk <= 0x7fffffff;
@@ -1517,31 +1336,27 @@ static bool sg_n8_ok(int M, int N, int K, const SgAct& xa) {
 
 template <int MODE>
 static int launch_sg_n8(const SgArgs& a, const SgRope& rp, hipStream_t st) {
-    const int nsc = a.K >> 6, cpw = (nsc + SG_N8_WAVES - 1) / SG_N8_WAVES;
-    // batch = super-chunks a wave keeps in flight (x NA weight streams): its whole share when that is <= 8 (7B: 8 — one
-    // round trip per wave), else the even split of 10 (13B: 5 + 5)
-    const bool u5 = g_sg_n8_u ? (g_sg_n8_u == 5) : (cpw > 8 && (cpw % 5) == 0);
-#define N8_LAUNCH(MT_, U_)                                                                                                   \
-    hipLaunchKernelGGL((skinny_gemm_n8_kernel<MT_, MODE, true, SG_N8_WAVES, U_>), dim3(a.N / 8), dim3(SG_N8_WAVES * 64), 0,  \
-                       st, (const half8*)a.wp, (const half8*)a.wp_up, (const h16*)a.x, a.ss_in, (const h16*)a.ln_w, a.K,    \
-                       a.M, (int)a.xa.sm, (int)a.xa.sk, a.eps, a.y, a.ya, rp)
-    // (the gate|up form holds two weight streams: from two row tiles up a batch of 4 — or 13B's even 5 + 5 — keeps it inside 256 registers)
-    if (a.M <= 8) {
-        if (u5) N8_LAUNCH(1, 5); else N8_LAUNCH(1, 8);
-    } else if constexpr (MODE == SG_GATEUP) {
-        if (a.M <= 16) {
-            if (u5) N8_LAUNCH(2, 5); else N8_LAUNCH(2, 4);
-        } else {
-            if (u5) N8_LAUNCH(3, 5); else N8_LAUNCH(3, 4);
-        }
-    } else if (a.M <= 16) {
-        if (u5) N8_LAUNCH(2, 5); else N8_LAUNCH(2, 8);
-    } else {
-        N8_LAUNCH(3, 5);
+    const SgN8Form f = sg_pick_n8(MODE, a.M, a.K);
+    // (FOR_: the modes whose rule can return the form — the others do not instantiate it)
+#define N8_FORM(MT_, U_, FOR_)                                                                                               \
+    if constexpr (FOR_) {                                                                                                    \
+        if (f.MT == MT_ && f.U == U_) {                                                                                      \
+            hipLaunchKernelGGL((skinny_gemm_n8_kernel<MT_, MODE, SG_N8_WAVES, U_>), dim3(a.N / 8), dim3(SG_N8_WAVES * 64), 0, \
+                               st, (const half8*)a.wp, (const half8*)a.wp_up, (const h16*)a.x, a.ss_in, (const h16*)a.ln_w,   \
+                               a.K, a.M, (int)a.xa.sm, (int)a.xa.sk, a.eps, a.y, a.ya, rp);                                  \
+            TF_LAUNCH_CHECK();                                                                                               \
+            return TF_OK;                                                                                                    \
+        }                                                                                                                    \
     }
-#undef N8_LAUNCH
-    TF_LAUNCH_CHECK();
-    return TF_OK;
+    N8_FORM(1, 5, true)
+    N8_FORM(1, 8, true)
+    N8_FORM(2, 5, true)
+    N8_FORM(3, 5, true)
+    N8_FORM(2, 4, MODE == SG_GATEUP)
+    N8_FORM(3, 4, MODE == SG_GATEUP)
+    N8_FORM(2, 8, MODE != SG_GATEUP)
+#undef N8_FORM
+    return TF_EINVAL;
 }
 
 extern "C" int tf_skinny_gemm_swiglu_n8(const void* gate_n8, const void* up_n8, const void* x, int64_t xs_m, int64_t xs_k,
@@ -1622,19 +1437,10 @@ extern "C" int tf_skinny_gemm_xchg(const void* w_packed, const void* x, int64_t 
     if ((const void*)out == (const void*)xc.stage[rank] || (const void*)resid == (const void*)xc.stage[rank]) return TF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const SgRope rp = {};
-    SgKsplit kx = {nullptr, nullptr, nullptr};
-#if SG_STAMPS
-    {
-        SgKsplit tmp;
-        SgArgs dummy = a;
-        sg_pick_ksplit<1, 1, 8, 1>(dummy, tmp);
-        kx.stamps = tmp.stamps;
-    }
-#endif
-    const int nchunks = K >> 5;
-    const bool wide = nchunks >= 2 * SG_WAVES_WIDE;
+    const SgKsplit kx = {nullptr, nullptr, sg_stamps_ptr()};
+    const bool wide = sg_xchg_waves(K) == SG_WAVES_WIDE;
 #define XCHG_LAUNCH(MT_, W_)                                                                                                  \
-    hipLaunchKernelGGL((skinny_gemm_kernel<MT_, SG_PLAIN, false, W_, 1, false, true, 1>), dim3(N / 16), dim3(W_ * 64), 0, st, \
+    hipLaunchKernelGGL((skinny_gemm_kernel<MT_, SG_PLAIN, false, W_, 1, false, true>), dim3(N / 16), dim3(W_ * 64), 0, st, \
                        (const half8*)a.wp, (const half8*)nullptr, (const h16*)a.x, (const float*)nullptr,              \
                        (const h16*)nullptr, a.K, a.M, (int)a.xa.sm, (int)a.xa.sk, 0.f, a.N, (const h16*)a.resid, a.ra, a.y, a.ya, rp, a.ss_out, \
                        kx, xc)

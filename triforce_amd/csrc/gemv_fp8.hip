@@ -23,26 +23,13 @@
 // them is on the single-GPU spec forward).
 #include "common.h"
 
-#ifdef TF_NO_NT
-#define F8_LOAD(p) (*(p))
-#else
 #define F8_LOAD(p) __builtin_nontemporal_load(p)   // weights are read once per forward: non-temporal
-#endif
 
 // Launch rule: waves per workgroup.  Grids of few panels (o_proj / down_proj at 7B: 256 panels) take the wide form, as in
-// the 16-bit kernel.  A/B through variant builds (triforce_amd.build.build_variant): F8_WIDE_MAX_PANELS, F8_GATEUP_WIDE.
-#ifndef F8_WAVES
-#define F8_WAVES 4
-#endif
-#ifndef F8_WAVES_WIDE
-#define F8_WAVES_WIDE 8
-#endif
-#ifndef F8_WIDE_MAX_PANELS
-#define F8_WIDE_MAX_PANELS 512   // grids of up to this many panels run F8_WAVES_WIDE waves per panel
-#endif
-#ifndef F8_GATEUP_WIDE
-#define F8_GATEUP_WIDE 0         // 1: gate|up GEMMs take the wide form too
-#endif
+// the 16-bit kernel; gate|up GEMMs never do.
+constexpr int F8_WAVES = 4;
+constexpr int F8_WAVES_WIDE = 8;
+constexpr int F8_WIDE_MAX_PANELS = 512;   // grids of up to this many panels run F8_WAVES_WIDE waves per panel
 
 enum { F8_PLAIN = 0, F8_GATEUP = 1, F8_F32 = 2, F8_QKV = 3 };
 
@@ -401,7 +388,7 @@ template <int MODE, bool NORM>
 static int launch_f8(const F8Args& a, const F8Rope& rp, hipStream_t st) {
     const int panels = a.N / 16, nsc = a.K >> 6;
     // few panels (o / down at 7B: 256 on 256 CUs) -> more waves per panel, while every wave keeps >= 2 super-chunks
-    const bool wide = (MODE != F8_GATEUP || F8_GATEUP_WIDE) && panels <= F8_WIDE_MAX_PANELS && nsc >= 2 * F8_WAVES_WIDE;
+    const bool wide = MODE != F8_GATEUP && panels <= F8_WIDE_MAX_PANELS && nsc >= 2 * F8_WAVES_WIDE;
     if (a.M <= 16) {
         if (wide) launch_f8_w<1, MODE, NORM, F8_WAVES_WIDE>(a, rp, st);
         else launch_f8_w<1, MODE, NORM, F8_WAVES>(a, rp, st);
