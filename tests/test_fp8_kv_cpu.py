@@ -111,7 +111,7 @@ def test_knob_parsing(monkeypatch):
 def test_fp8_needs_the_fused_decode_layer(monkeypatch):
     from triforce_amd.models import cache as C
     monkeypatch.setenv(ENV, "fp8")
-    monkeypatch.setattr(C.ops, "FUSE_MODE", "rope")
+    monkeypatch.setattr(C.ops, "FUSE_MODE", "none")
     with pytest.raises(ValueError, match="TRIFORCE_FUSE"):
         C.kv_cache_dtype()
 

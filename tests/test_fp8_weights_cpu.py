@@ -164,14 +164,24 @@ def test_retrieval_weights_knob(monkeypatch):
     monkeypatch.setenv("TRIFORCE_RETRIEVAL_WEIGHTS", "fp8")
     monkeypatch.setattr(ops, "FUSE_MODE", "all")
     assert C.retrieval_weights() == "fp8"
-    for mode in ("all2", "rope", "none"):
-        monkeypatch.setattr(ops, "FUSE_MODE", mode)
-        with pytest.raises(ValueError, match="TRIFORCE_FUSE"):
-            C.retrieval_weights()
+    monkeypatch.setattr(ops, "FUSE_MODE", "none")
+    with pytest.raises(ValueError, match="TRIFORCE_FUSE"):
+        C.retrieval_weights()
     monkeypatch.setattr(ops, "FUSE_MODE", "all")
     monkeypatch.setenv("TRIFORCE_RETRIEVAL_WEIGHTS", "int4")
     with pytest.raises(ValueError):
         C.retrieval_weights()
+
+
+def test_fusion_switch_is_two_valued(monkeypatch):
+    ops = _ops()
+    monkeypatch.delenv("TRIFORCE_FUSE", raising=False)
+    assert ops.fuse_mode() == "all"
+    monkeypatch.setenv("TRIFORCE_FUSE", "none")
+    assert ops.fuse_mode() == "none"
+    monkeypatch.setenv("TRIFORCE_FUSE", "rope")                     # a retired level: refused, not read as "none"
+    with pytest.raises(ValueError, match="all or none"):
+        ops.fuse_mode()
 
 
 def test_tensor_parallel_engine_refuses_fp8(monkeypatch):

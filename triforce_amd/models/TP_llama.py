@@ -26,7 +26,7 @@ from ..utils.sampling import norm_logits
 from .cache import (DistributedKVCacheBuffer, DistributedRetrievalCache, DistributedRetrievalCache_Seqouia,
                     DistributedSimpleCache, _refuse_fp8)
 from .config_yarn import LlamaConfig
-from .llama_core import (RETRIEVAL_WEIGHTS_ENV, LlamaWeights, parse_random_spec, retrieval_weights, rope_tables_for,
+from .llama_core import (RETRIEVAL_WEIGHTS_ENV, DecoderLayers, LlamaWeights, parse_random_spec, retrieval_weights, rope_tables_for,
                          softmax_scale_for)
 from .TP_layers import DistributedOffloadingConfig
 
@@ -141,6 +141,7 @@ class DistributedLlama:
         self.weights = W
         cos, sin = rope_tables_for(cfg)
         self.cos_cache, self.sin_cache = cos.to(self.device), sin.to(self.device)
+        self.layers = DecoderLayers(W, self.cos_cache, self.sin_cache)       # (this rank's shard: W.H_local heads)
         self.embed_tokens, self.lm_head, self.norm_weight = W.embed, W.lm_head, W.norm
         self.norm_variance_epsilon = W.eps
         # TRIFORCE_ALLREDUCE = auto (one-shot after its self-check, else RCCL) | oneshot (fail if unavailable) | rccl;
@@ -405,14 +406,7 @@ class DistributedLlama:
                    sk_dev=None):
         """Attention block of layer i on this rank's shard up to (not including) the all-reduce: returns the partial
         o_proj output.  x: residual stream (updated in place with the pending MLP output d of the previous layer)."""
-        W = self.weights
-        Hl, D = W.H_local, W.D
-        if d is None:
-            h = ops.rmsnorm(x, W.ln1[i], W.eps)
-        else:
-            h = ops.rmsnorm(d, W.ln1[i], W.eps, residual=x, sum_out=x)
-        qkv = ops.linear(h, W.wqkv[i])
-        q = ops.rope_append(qkv, self.cos_cache, self.sin_cache, pos, kl, vl, slot, Hl, D, slot0_dev=slot_dev)
+        q = self.layers.qkv(i, x, d, pos, kl, vl, slot, slot_dev)
         if retrieval_build:                               # tensor_op.py:161-162
             self.retrieval_cache.init_graph_cache((kl, vl), q, i)
         if sk_dev is not None:                            # captured form: slot / key count live in device memory
@@ -422,22 +416,14 @@ class DistributedLlama:
         else:                                             # tensor_op.py:171,265: SDPA, scale 1/sqrt(D) in fp32
             bits, row0, tree_start = tree
             a = ops.attn_tree(q, kl, vl, sk, self.tree_scale, bits, tree_start, mask_row0=row0)
-        return ops.linear(a, W.wo[i]) if out is None else ops.linear(a, W.wo[i], out=out)
-
-    def _mlp_half(self, i, x, o, out=None):
-        """MLP block of layer i up to the all-reduce: x += o (all-reduced attention output), returns the partial
-        down_proj output."""
-        W = self.weights
-        h = ops.rmsnorm(o, W.ln2[i], W.eps, residual=x, sum_out=x)
-        act = ops.mlp_act(h, W.wgu[i])
-        return ops.linear(act, W.wd[i]) if out is None else ops.linear(act, W.wd[i], out=out)
+        return self.layers.o_proj(i, a, out)
 
     def _layer(self, i, x, d, pos, kl, vl, slot, sk, q_len, retrieval_build=False, tree=None):
         """One decoder layer on this rank's shard.  x: residual stream (updated in place), d: pending MLP output
         of the previous layer (None for layer 0).  Returns the (all-reduced) MLP output of this layer."""
         o = self._reduce(self._attn_half(i, x, d, pos, kl, vl, slot, sk, retrieval_build, tree,
                                          out=self._partial_out(q_len)))                                # tensor_op.py:176-179
-        return self._reduce(self._mlp_half(i, x, o, out=self._partial_out(q_len)))                     # tensor_op.py:353-359
+        return self._reduce(self.layers.mlp(i, x, o, self._partial_out(q_len)))                        # tensor_op.py:353-359
 
     # ---- fused decode layer (<= 32 rows): the single-GPU engine's 5-launch layer with an exchange step in it -------
     # q|k|v GEMM with RMSNorm prologue and RoPE + KV-append epilogue, attention, o_proj, [exchange], gate|up GEMM with
@@ -468,32 +454,26 @@ class DistributedLlama:
     def _attn_half_fused(self, i, x, ss, pos, kl, vl, slot, sk, retrieval_build=False, slot_dev=None, sk_dev=None):
         """Attention block of layer i, fused form: returns this rank's partial o_proj output in the exchange's staging
         buffer, or None at world size 1 (x and ss already updated by the GEMM's own epilogue)."""
-        W = self.weights
-        Hl, D = W.H_local, W.D
-        packed = isinstance(x, ops.Act)                   # k-octet-major residual stream (ops.act_packed)
-        q = ops.qkv_rope(x, W.wqkv[i], W.ln1[i], W.eps, self.cos_cache, self.sin_cache, pos, kl, vl, slot, Hl, D,
-                         slot0_dev=slot_dev, ss_in=ss if i > 0 else None)
+        q = self.layers.qkv_fused(i, x, ss, pos, kl, vl, slot, slot_dev)
         if retrieval_build:                               # tensor_op.py:161-162
             self.retrieval_cache.init_graph_cache((kl, vl), q, i)
-        a = ops.attn_decode(q, kl, vl, sk, self.scale, sk_dev=sk_dev, packed=packed)
-        if self.world_size == 1:
-            ops.linear(a, W.wo[i], resid=x, out=x, ss_out=ss)
-            return None
-        if self._xchg is not None:                        # o_proj + exchange + residual + sums of squares: one launch
-            self._xchg.linear_reduce(a, W.wo[i], x, ss)
-            return None
-        return ops.linear(a, W.wo[i], out=self._ar.staging(x.shape[0], self.hidden_size, packed=packed))
+        a = ops.attn_decode(q, kl, vl, sk, self.scale, sk_dev=sk_dev, packed=isinstance(x, ops.Act))
+        return self._partial_fused(self.layers.o_fused, self.weights.wo, i, a, x, ss)
 
     def _mlp_half_fused(self, i, x, ss):
-        W = self.weights
-        act = ops.mlp_act(x, W.wgu[i], ln=W.ln2[i], eps=W.eps, ss_in=ss)
+        return self._partial_fused(self.layers.down_fused, self.weights.wd, i, self.layers.gate_up_fused(i, x, ss), x, ss)
+
+    def _partial_fused(self, gemm, ws, i, a, x, ss):
+        """The o / down GEMM of the fused layer (``gemm`` of self.layers over the weights ``ws``) and where it writes: at
+        world size 1 its own epilogue adds to x and refreshes ss; GemmExchange does the same across the ranks in one launch;
+        else the partial goes to the one-shot all-reduce's staging buffer (k-octet-major like x) and is returned."""
         if self.world_size == 1:
-            ops.linear(act, W.wd[i], resid=x, out=x, ss_out=ss)
+            gemm(i, a, x, ss)
             return None
         if self._xchg is not None:
-            self._xchg.linear_reduce(act, W.wd[i], x, ss)
+            self._xchg.linear_reduce(a, ws[i], x, ss)
             return None
-        return ops.linear(act, W.wd[i], out=self._ar.staging(x.shape[0], self.hidden_size, packed=isinstance(x, ops.Act)))
+        return gemm(i, a, x, ss, out=self._ar.staging(x.shape[0], self.hidden_size, packed=isinstance(x, ops.Act)))
 
     def _exchange_fused(self, part, x, ss):
         """x += sum over ranks of ``part`` (tensor_op.py:179-181,359-360) and ss <- panel sums of squares of the new x."""
@@ -504,20 +484,8 @@ class DistributedLlama:
         self._exchange_fused(self._attn_half_fused(i, x, ss, pos, kl, vl, slot, sk, retrieval_build), x, ss)
         self._exchange_fused(self._mlp_half_fused(i, x, ss), x, ss)
 
-    def _finish_fused(self, x, ss):
-        W = self.weights
-        if W.capture is not None:
-            W.capture.append(x.rows() if isinstance(x, ops.Act) else x.clone())
-        return ops.linear(x, W.lm_head, out_f32=True, ln=W.norm, eps=W.eps, ss_in=ss).unsqueeze(0)
-
     def _finish(self, x, d, last_rows=None):
-        W = self.weights
-        h = ops.rmsnorm(d, W.norm, W.eps, residual=x, sum_out=x)
-        if W.capture is not None:
-            W.capture.append(x.clone())
-        if last_rows is not None and last_rows < h.shape[0]:      # chunked prefill: only the returned rows get logits
-            h = h[-last_rows:]
-        return ops.linear(h, W.lm_head, out_f32=True).unsqueeze(0)
+        return self.layers.head(x, d, last_rows)
 
     @torch.inference_mode()
     def inference(self, input_ids, position_ids=None, attention_mask=None, retrieval_cache=None, eager=False,
@@ -580,7 +548,7 @@ class DistributedLlama:
         if n_on < L:
             torch.cuda.current_stream(self.device).wait_stream(cs)              # write-backs visible before reuse
         kvc.seq_len = S + q_len
-        return self._finish_fused(x, ss) if fused else self._finish(x, d, last_rows)
+        return self.layers.head_fused(x, ss) if fused else self._finish(x, d, last_rows)
 
     def _tree_mask(self, attention_mask, tree_start, q_len):
         """Tree visibility for the block-attention kernel: (bit rows int32, first row, key index of tree column 0).
@@ -665,7 +633,7 @@ class DistributedLlama:
         def mlp(i, cell):
             def run():
                 part = cell["p"] = self._partial_out(q_len, st["d"])
-                return self._mlp_half(i, st["x"], st["o"], out=part)
+                return self.layers.mlp(i, st["x"], st["o"], part)
             return run
 
         def finish():
@@ -709,7 +677,7 @@ class DistributedLlama:
             return run
 
         def finish():
-            logits = self._finish_fused(x, ss)
+            logits = self.layers.head_fused(x, ss)
             if kind == "retrieval":
                 return norm_logits(logits[0], temperature=self.temperature, top_k=-1, top_p=self.top_p)
             return logits
@@ -1004,7 +972,7 @@ class DistributedLlama:
             for idx in range(self.num_layers):
                 kl, vl = rc.layer_kv(idx)
                 self._layer_fused(idx, x, ss, pos, kl, vl, rc.spec_slot, rc.real_budget)
-            return self._finish_fused(x, ss)
+            return self.layers.head_fused(x, ss)
         d = None
         for idx in range(self.num_layers):
             kl, vl = rc.layer_kv(idx)

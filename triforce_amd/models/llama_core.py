@@ -229,6 +229,86 @@ class LlamaWeights:
         return sum(t.numel() * t.element_size() for t in ts)
 
 
+class DecoderLayers:
+    """The decoder layer around its attention, once for the target, the draft and the tensor-parallel engine (whose shard
+    is a LlamaWeights with fewer heads and MLP columns).  Attention stays with the engine, and so does the choice of where
+    the o / down GEMM writes and what follows it (nothing here knows about process groups).
+
+    Fused form (decode-sized blocks, ops.can_fuse): x is the residual stream — a row-major tensor or an ops.Act — and
+    ``ss`` the sums of squares of x that every residual GEMM leaves for the norm prologue of the GEMM after it.
+    ``f8``: stream the FP8 copies of the weights (the retrieval-verify tier).  o_fused / down_fused with ``out`` None add
+    to x in place and refresh ss in the GEMM's own epilogue; with ``out`` they write the bare product there.
+
+    Un-fused form (prefill chunks; the CPU stand-ins of the tests): x is updated by the norm that follows each GEMM, so
+    the MLP output ``d`` of one layer is still pending when the next one starts (None at layer 0)."""
+
+    def __init__(self, W, cos, sin, rotate_k=True):
+        self.W, self.cos, self.sin, self.rotate_k = W, cos, sin, rotate_k
+
+    def _capture(self, x):
+        """W.capture (a list, while aligned weights are calibrated) receives the final residual stream, before the norm."""
+        if self.W.capture is not None:
+            self.W.capture.append(x.rows() if isinstance(x, ops.Act) else x.clone())
+
+    # -- fused ---------------------------------------------------------------------------------
+    def qkv_fused(self, i, x, ss, pos, kl, vl, slot, slot_dev=None, f8=False):
+        """[norm ->] q|k|v GEMM -> RoPE -> K/V rows into kl / vl at ``slot`` (or the device scalar slot_dev); returns q."""
+        W = self.W
+        w = W.wqkv[i]
+        return ops.qkv_rope(x, w.fp8 if f8 else w, W.ln1[i], W.eps, self.cos, self.sin, pos, kl, vl, slot, W.H_local, W.D,
+                            rotate_k=self.rotate_k, slot0_dev=slot_dev, ss_in=ss if i > 0 else None)
+
+    def o_fused(self, i, a, x, ss, f8=False, out=None):
+        w = self.W.wo[i].fp8 if f8 else self.W.wo[i]
+        if out is None:
+            return ops.linear(a, w, resid=x, out=x, ss_out=ss)                  # x += attn_out
+        return ops.linear(a, w, out=out)
+
+    def gate_up_fused(self, i, x, ss, f8=False):
+        W = self.W
+        w = W.wgu[i]
+        return ops.mlp_act(x, w.fp8 if f8 else w, ln=W.ln2[i], eps=W.eps, ss_in=ss)
+
+    def down_fused(self, i, act, x, ss, f8=False, out=None):
+        w = self.W.wd[i].fp8 if f8 else self.W.wd[i]
+        if out is None:
+            return ops.linear(act, w, resid=x, out=x, ss_out=ss)                # x += mlp_out
+        return ops.linear(act, w, out=out)
+
+    def head_fused(self, x, ss, f8=False):
+        W = self.W
+        self._capture(x)
+        return ops.linear(x, W.lm_head.fp8 if f8 else W.lm_head, out_f32=True, ln=W.norm, eps=W.eps, ss_in=ss).unsqueeze(0)
+
+    # -- un-fused ------------------------------------------------------------------------------
+    def qkv(self, i, x, d, pos, kl, vl, slot, slot_dev=None):
+        W = self.W
+        if d is None:
+            h = ops.rmsnorm(x, W.ln1[i], W.eps)
+        else:                                       # x += mlp_out of the previous layer, fused into the norm
+            h = ops.rmsnorm(d, W.ln1[i], W.eps, residual=x, sum_out=x)
+        return ops.rope_append(ops.linear(h, W.wqkv[i]), self.cos, self.sin, pos, kl, vl, slot, W.H_local, W.D,
+                               rotate_k=self.rotate_k, slot0_dev=slot_dev)
+
+    def o_proj(self, i, a, out=None):
+        return ops.linear(a, self.W.wo[i], out=out)
+
+    def mlp(self, i, x, o, out=None):
+        """x += o (the attention output), then the MLP: returns its output, which the next norm adds to x."""
+        W = self.W
+        h = ops.rmsnorm(o, W.ln2[i], W.eps, residual=x, sum_out=x)
+        return ops.linear(ops.mlp_act(h, W.wgu[i]), W.wd[i], out=out)
+
+    def head(self, x, d, last_rows=None):
+        """last_rows = k: logits of the trailing k rows only (chunked prefill)."""
+        W = self.W
+        h = ops.rmsnorm(d, W.norm, W.eps, residual=x, sum_out=x)
+        self._capture(x)
+        if last_rows is not None and last_rows < h.shape[0]:
+            h = h[-last_rows:]
+        return ops.linear(h, W.lm_head, out_f32=True).unsqueeze(0)           # (1, q, V) fp32
+
+
 def load_checkpoint_state_dict(path):
     """HF directory with *.safetensors (or pytorch_model*.bin) -> flat state dict on CPU."""
     sd = {}

@@ -7,7 +7,7 @@ import torch
 
 from .. import ops
 from .config_yarn import LlamaConfig
-from .llama_core import (CausalLMOutput, LlamaWeights, load_checkpoint_state_dict, parse_random_spec,
+from .llama_core import (CausalLMOutput, DecoderLayers, LlamaWeights, load_checkpoint_state_dict, parse_random_spec,
                          rope_tables_plain, softmax_scale_for)
 
 
@@ -21,6 +21,7 @@ class LlamaForCausalLM:
         cos, sin = rope_tables_plain(D, config.max_position_embeddings, config.rope_theta)   # 68m.py:123-128
         self.cos, self.sin = cos.to(self.device), sin.to(self.device)
         self.scale = softmax_scale_for(D)
+        self.layers = DecoderLayers(self.weights, self.cos, self.sin, rotate_k=False)      # keys are cached un-rotated
         self.vocab_size = config.vocab_size
         # the one-launch forward (ops.DraftPersist) needs the whole chip to itself while it runs: an engine whose ranks share a
         # device switches it off (models/TP_llama._detect_shared_device)
@@ -95,8 +96,7 @@ class LlamaForCausalLM:
 
     def forward(self, input_ids, kv_cache, graph_cache=None, gamma_offset=-1, probs=None):
         """``probs`` = (temperature, top_p): also return the top-p probability row of the last token (out.probs)."""
-        W = self.weights
-        H, D = W.H, W.D
+        W, layers = self.weights, self.layers
         q_len = input_ids.shape[1]
         spec = gamma_offset >= 0
         native = self._native_model() if q_len <= ops.SKINNY_MAX_ROWS else None
@@ -128,44 +128,22 @@ class LlamaForCausalLM:
             slot0 = c.seq_len
             kv_len = slot0 + q_len
             pos = torch.arange(slot0, slot0 + q_len, dtype=torch.long, device=self.device)
-        mode = ops.FUSE_MODE if (ops.can_fuse(x, W.wqkv[0], W.wo[0], W.wgu[0], W.wd[0], W.lm_head)
-                                 and W.wqkv[0].wp_rope is not None) else "none"
-        fused = mode in ("all", "all2")
-        ss = ops.ss_buffer(x.shape[1], x.device) if mode == "all" else None     # sum(x^2) hand-off between GEMMs
+        fused = (ops.FUSE_MODE == "all" and ops.can_fuse(x, W.wqkv[0], W.wo[0], W.wgu[0], W.wd[0], W.lm_head)
+                 and W.wqkv[0].wp_rope is not None)
+        ss = ops.ss_buffer(x.shape[1], x.device) if fused else None     # sum(x^2) hand-off between GEMMs
         d = None
         for i in range(W.L):
             kl, vl = c.layer_kv(i)
             if not spec:
                 c.append_slot(i, q_len)
-            if fused:
-                q = ops.qkv_rope(x, W.wqkv[i], W.ln1[i], W.eps, self.cos, self.sin, pos, kl, vl, slot0, H, D,
-                                 rotate_k=False, ss_in=ss if i > 0 else None)
-            else:
-                if d is None:
-                    h = ops.rmsnorm(x, W.ln1[i], W.eps)
-                else:
-                    h = ops.rmsnorm(d, W.ln1[i], W.eps, residual=x, sum_out=x)
-                if mode == "rope":
-                    q = ops.qkv_rope(h, W.wqkv[i], None, 0.0, self.cos, self.sin, pos, kl, vl, slot0, H, D,
-                                     rotate_k=False)
-                else:
-                    q = ops.rope_append(ops.linear(h, W.wqkv[i]), self.cos, self.sin, pos, kl, vl, slot0, H, D,
-                                        rotate_k=False)
+            q = layers.qkv_fused(i, x, ss, pos, kl, vl, slot0) if fused else layers.qkv(i, x, d, pos, kl, vl, slot0)
             a = ops.attn_rope_on_read(q, kl, vl, self.cos, self.sin, kv_len, self.scale)
             if fused:
-                ops.linear(a, W.wo[i], resid=x, out=x, ss_out=ss)
-                act = ops.mlp_act(x, W.wgu[i], ln=W.ln2[i], eps=W.eps, ss_in=ss)
-                ops.linear(act, W.wd[i], resid=x, out=x, ss_out=ss)
+                layers.o_fused(i, a, x, ss)
+                layers.down_fused(i, layers.gate_up_fused(i, x, ss), x, ss)
             else:
-                o = ops.linear(a, W.wo[i])
-                h = ops.rmsnorm(o, W.ln2[i], W.eps, residual=x, sum_out=x)
-                act = ops.mlp_act(h, W.wgu[i])
-                d = ops.linear(act, W.wd[i])
-        if fused:
-            logits = ops.linear(x, W.lm_head, out_f32=True, ln=W.norm, eps=W.eps, ss_in=ss).unsqueeze(0)
-        else:
-            h = ops.rmsnorm(d, W.norm, W.eps, residual=x, sum_out=x)
-            logits = ops.linear(h, W.lm_head, out_f32=True).unsqueeze(0)
+                d = layers.mlp(i, x, layers.o_proj(i, a))
+        logits = layers.head_fused(x, ss) if fused else layers.head(x, d)
         out = CausalLMOutput(logits)
         if probs is not None:
             from ..utils.sampling import norm_logits

@@ -48,11 +48,20 @@ def _kv(t):
 
 # ------------------------------------------------------------------------------------------
 SKINNY_MAX_ROWS = 32
-# Decode-layer fusion level (A/B switch, env TRIFORCE_FUSE): "all" = norm prologues fed by the GEMM-to-GEMM
-# sum-of-squares hand-off + residual / RoPE epilogues (6 launches per layer); "all2" = same but every norm prologue
-# re-reads x; "rope" = only the RoPE + KV-append epilogue; "none" = one launch per op (9 per layer).
+# Decode-layer fusion (env TRIFORCE_FUSE): "all" = decode-sized blocks run the fused layer — norm prologues fed by the
+# GEMM-to-GEMM sum-of-squares hand-off, residual / RoPE + KV-append epilogues (5 launches per layer); "none" = one launch per
+# op everywhere (9 per layer), the form prefill chunks always take.
 import os as _os
-FUSE_MODE = _os.environ.get("TRIFORCE_FUSE", "all")
+
+
+def fuse_mode():
+    v = _os.environ.get("TRIFORCE_FUSE", "all")
+    if v not in ("all", "none"):
+        raise ValueError(f"TRIFORCE_FUSE={v!r}: expected all or none")
+    return v
+
+
+FUSE_MODE = fuse_mode()
 
 
 def pack_weight(w):
