@@ -435,6 +435,43 @@ int tf_kv_dequant_rows_pair(const void* src_k, const void* src_v, int64_t src_st
                             int64_t src_stride_h, const void* exp_k, const void* exp_v, int64_t exp_stride_l,
                             int64_t exp_stride_h, void* dst_k, void* dst_v, int64_t dst_stride_l, int64_t dst_stride_t,
                             int64_t dst_stride_h, int src_t0, int dst_t0, int n, int L, int H, int D, void* stream);
+/* FP8 RETRIEVAL CACHE (csrc/kv_fp8.hip, csrc/attn.hip) — the retrieval cache's rows [0, max_budget) stored in the row format
+ * above with TRIFORCE_RETRIEVAL_KV=fp8: codes [L][H][max_budget][128] and exponent bytes
+ * [L][H][max_budget], separately for K and V; no new numerics.  The gamma + 1 rows a retrieval-cache (spec) forward appends
+ * are scratch — every such forward rewrites them, the durable copy arrives through the tail refresh from the full cache —
+ * and stay fp16 in a small [L][H][gamma + 1][128] array.  The middle tier only drafts, so the decoding stays lossless with
+ * respect to the target for any such storage.
+ * Both row movers take either source: fp16 rows (src exponent pointers NULL; strides in halves) are quantized by the contract
+ * above, bit-identical to triforce_amd.ops.kv_quantize_ref; codes + exponents (strides in bytes, multiples of 16; exponents
+ * with token stride 1) are copied byte for byte — the middle tier then reads exactly the deq the target reads.  K and V in
+ * one launch.  D = 128.  NULL pointers, one source exponent pointer without the other, bad strides -> -EINVAL (checked
+ * before n == 0, a no-op).  No bounds check of rows or chunk ids against the arrays: the caller sizes them.
+ *
+ * tf_retrieval_gather_fp8: tf_retrieval_gather of one layer into codes: destination row s * chunk + r of head h = source row
+ *   idx[h][s] * chunk + r, s < sets, r < chunk.  exp_stride_h >= sets * chunk.
+ * tf_kv_quant_rows_pair: tf_kv_copy_rows_pair into codes over L layers: dst[l,h,dst_t0+i] = src[l,h,src_t0+i], i < n (the
+ *   refresh of the generated tail).
+ * tf_attn_decode_fp8_tail_act: tf_attn_decode_fp8_act whose keys [0, sk_codes) are codes + exponents and whose keys
+ *   [sk_codes, sk_codes + n_tail) are fp16 rows, row (h, i) at k_tail / v_tail + h * tail_stride_h + i * tail_stride_t
+ *   (halves, multiples of 8).  The source is picked per key row while the wave-private staging tile is filled, so a 16-key
+ *   tile may straddle the boundary; fragments, tile order, split rule and both merges are tf_attn_decode_act's: the output is
+ *   bit-identical to tf_attn_decode_act on [deq(codes) | tail rows] with the same nsplit, in either output layout.
+ *   D = 128, sq <= 32, 1 <= n_tail <= 32, sk_codes >= 1, exp_stride_h >= sk_codes; sk_dev must be NULL (the boundary is a
+ *   host value); anything else -> -EINVAL before any launch. */
+int tf_retrieval_gather_fp8(const void* k_src, const void* v_src, int64_t src_stride_t, int64_t src_stride_h,
+                            const void* k_src_exp, const void* v_src_exp, int64_t src_exp_stride_h, const int32_t* idx,
+                            void* k_codes, void* v_codes, void* k_exp, void* v_exp, int64_t code_stride_t,
+                            int64_t code_stride_h, int64_t exp_stride_h, int sets, int chunk, int H, int D, void* stream);
+int tf_kv_quant_rows_pair(const void* src_k, const void* src_v, int64_t src_stride_l, int64_t src_stride_t,
+                          int64_t src_stride_h, const void* src_exp_k, const void* src_exp_v, int64_t src_exp_stride_l,
+                          int64_t src_exp_stride_h, void* k_codes, void* v_codes, int64_t code_stride_l,
+                          int64_t code_stride_t, int64_t code_stride_h, void* k_exp, void* v_exp, int64_t exp_stride_l,
+                          int64_t exp_stride_h, int src_t0, int dst_t0, int n, int L, int H, int D, void* stream);
+int tf_attn_decode_fp8_tail_act(const void* q, const void* k_codes, const void* v_codes, const void* k_exp, const void* v_exp,
+                                const void* k_tail, const void* v_tail, void* out, int64_t out_sm, int64_t out_sk,
+                                int64_t stride_t, int64_t stride_h, int64_t exp_stride_h, int64_t tail_stride_t,
+                                int64_t tail_stride_h, int sq, int sk_codes, int n_tail, const int32_t* sk_dev, int H, int D,
+                                float scale, int nsplit, float* ws, int64_t ws_floats, uint32_t* tickets, void* stream);
 /* Split-K workspace of the CURRENT device (csrc/gemv.hip, SgKsplit): GEMMs with few output panels — the q|k|v and
  * gate|up shards of a tensor-parallel rank — split K across up to 4 workgroups per panel; their partial sums meet in
  * `ws` (zero-filled device memory, first 16 KiB = per-panel tickets, left zero by every launch; 8 MiB covers every shape

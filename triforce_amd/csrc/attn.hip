@@ -247,6 +247,42 @@ __device__ __forceinline__ void f8_rows_to_frags(const F8Tile& x, h16* stage, in
         vf[c] = *reinterpret_cast<const half8*>(stage + (16 + li) * LDR + 32 * c + 8 * g);
     }
 }
+// The FP8 retrieval cache's stream (tf_attn_decode_fp8_tail_act): keys [0, skc) are codes, keys [skc, sk) the
+// fp16 rows kt / vt (the spec rows of the forward, never quantized).  Only the last tiles of the stream reach past skc — three at
+// the most (n_tail <= 32), so with four waves a wave owns at most ONE of them.  The wave fetches that tile before its stream
+// starts, next to the ring's first loads (their latency is exposed anyway), each row from ITS source — 16 codes + the exponent
+// byte, or two 16-byte loads of the fp16 row — into a staging tile of its own, and consumes it after the stream, in tile order.
+// The stream loop itself then holds no conditional load: a load under an `if` inside it makes the waitcnt pass drain the ring
+// at every use (measured: 12 305 keys x 17 rows 43.8 -> 56.2 us).  Keys past sk repeat row sk - 1 like the fp16 loader.
+__device__ __forceinline__ void f8_tail_fill(const uint8_t* __restrict__ kbase, const uint8_t* __restrict__ vbase,
+                                             const uint8_t* __restrict__ kebase, const uint8_t* __restrict__ vebase, int64_t stride_t,
+                                             const h16* __restrict__ kt, const h16* __restrict__ vt, int64_t tail_st, int tile,
+                                             int skc, int sk, h16* stage, int lane) {
+    constexpr int D = 128, LDR = D + 8;
+    const int rl = lane >> 3, p = lane & 7;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int key = tile * 16 + 8 * j + rl;
+        half8 klo, khi, vlo, vhi;
+        if (key < skc) {
+            const int64_t off = (int64_t)key * stride_t + 16 * p;
+            const u32x4 kc = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kbase + off));
+            const u32x4 vc = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vbase + off));
+            f8_decode_row16(kc, kebase[key], klo, khi);
+            f8_decode_row16(vc, vebase[key], vlo, vhi);
+        } else {
+            const int64_t off = (int64_t)((key < sk ? key : sk - 1) - skc) * tail_st + 16 * p;
+            klo = load_half8(kt + off);
+            khi = load_half8(kt + off + 8);
+            vlo = load_half8(vt + off);
+            vhi = load_half8(vt + off + 8);
+        }
+        *reinterpret_cast<half8*>(stage + (8 * j + rl) * LDR + 16 * p) = klo;
+        *reinterpret_cast<half8*>(stage + (8 * j + rl) * LDR + 16 * p + 8) = khi;
+        *reinterpret_cast<half8*>(stage + (16 + 8 * j + rl) * LDR + 16 * p) = vlo;
+        *reinterpret_cast<half8*>(stage + (16 + 8 * j + rl) * LDR + 16 * p + 8) = vhi;
+    }
+}
 // Tiles in flight per wave of the FP8 stream: a ring of 3 (two loaded under each tile's MFMAs) = 8 KiB, the bytes the fp16
 // two-deep loop keeps in flight (half or twice that loses 10-25 %).
 #ifndef TF_ATTN_F8_RING
@@ -341,12 +377,15 @@ __device__ __forceinline__ void attn_tile(AttnState<D, QT>& st, const half8 (&kf
 
 // ws layout: o[H][nsplit][QR][D] | m[H][nsplit][QR] | l[H][nsplit][QR],  QR = QT*16
 // F8: k / v are e4m3fn codes (strides in bytes) with exponent bytes ke / ve ([H][e_sh] per head, one per key)
-template <int D, int QT, bool F8 = false>
+// TAIL (with F8): only keys [0, skc) are codes; keys [skc, sk) are the fp16 rows kt / vt ([H][t_sh] halves per head, t_st per row)
+template <int D, int QT, bool F8 = false, bool TAIL = false>
 __device__ __forceinline__ void attn_split_body(
     const h16* __restrict__ q, const h16* __restrict__ k, const h16* __restrict__ v, int64_t stride_t,
     int64_t stride_h, int sq, int sk_host, const int32_t* __restrict__ sk_dev, int H, float scale, int nsplit,
     float* __restrict__ ws, unsigned* __restrict__ tickets, h16* __restrict__ out, int64_t osm, int64_t osk,
-    const uint8_t* __restrict__ ke = nullptr, const uint8_t* __restrict__ ve = nullptr, int64_t e_sh = 0) {
+    const uint8_t* __restrict__ ke = nullptr, const uint8_t* __restrict__ ve = nullptr, int64_t e_sh = 0,
+    const h16* __restrict__ kt = nullptr, const h16* __restrict__ vt = nullptr, int64_t t_st = 0, int64_t t_sh = 0, int skc = 0) {
+    static_assert(!TAIL || F8, "the fp16 tail rows follow an FP8 stream");
     constexpr int NC = D / 32, NT = D / 16, QR = QT * 16;
     constexpr int NW = 4;                              // waves per workgroup
     const int split = blockIdx.x, h = blockIdx.y;
@@ -389,7 +428,7 @@ __device__ __forceinline__ void attn_split_body(
     // waves' partial results
     constexpr size_t MERGE_BYTES = sizeof(float) * ((size_t)NW * 16 * (D + 1) + 2 * NW * 16);
     static_assert(!F8 || D == 128, "FP8 stream: D = 128");
-    constexpr size_t STAGE_BYTES = (size_t)NW * 2 * 16 * (D + 8) * sizeof(h16);
+    constexpr size_t STAGE_BYTES = (size_t)NW * 2 * 16 * (D + 8) * sizeof(h16) * (TAIL ? 2 : 1);    // TAIL: + each wave's tail tile
     __shared__ __attribute__((aligned(16))) unsigned char sm_raw[MERGE_BYTES > STAGE_BYTES ? MERGE_BYTES : STAGE_BYTES];
     h16* stage = reinterpret_cast<h16*>(sm_raw) + (size_t)wave * 2 * 16 * (D + 8);
 
@@ -416,23 +455,54 @@ __device__ __forceinline__ void attn_split_body(
         const uint8_t* vb8 = reinterpret_cast<const uint8_t*>(v) + (int64_t)h * stride_h;
         const uint8_t* keb = ke + (int64_t)h * e_sh;
         const uint8_t* veb = ve + (int64_t)h * e_sh;
-        if (t < t_end) {
+        // TAIL: the stream proper ends in front of the first tile that reaches past the coded keys; this wave's tile of that
+        // kind (tt, at most one: see f8_tail_fill) sits in the wave's second staging tile until the stream is through
+        const int t_stream = TAIL ? min(t_end, skc >> 4) : t_end;
+        const int skl = TAIL ? skc : sk;               // keys the ring's loads may touch
+        h16* tstage = stage + (size_t)NW * 2 * 16 * (D + 8);
+        int tt = -1;
+        if constexpr (TAIL) {
+            const int first = skc >> 4;
+            const int c = t < first ? t + (first - t + NW - 1) / NW * NW : t;
+            if (c < t_end) tt = c;
+        }
+#define ATTN_TAIL_FILL()                                                                                             \
+    f8_tail_fill(kb8, vb8, keb, veb, stride_t, kt + (int64_t)h * t_sh, vt + (int64_t)h * t_sh, t_st, tt, skc, sk, tstage, lane)
+        if (t < t_stream) {
             F8Tile ring[RING];
-            const int tl = t_end - 1;
+            const int tl = t_stream - 1;
 #pragma unroll
-            for (int s = 0; s < RING; ++s) load_kv_rows_f8(kb8, vb8, keb, veb, stride_t, min(t + NW * s, tl), sk, lane, ring[s]);
-            while (t < t_end) {
+            for (int s = 0; s < RING; ++s) load_kv_rows_f8(kb8, vb8, keb, veb, stride_t, min(t + NW * s, tl), skl, lane, ring[s]);
+            if constexpr (TAIL) {
+                if (tt >= 0) ATTN_TAIL_FILL();
+            }
+            while (t < t_stream) {
 #pragma unroll
                 for (int s = 0; s < RING; ++s) {
                     const int ti = t + NW * s;
-                    if (ti < t_end) {
+                    if (ti < t_stream) {
                         half8 kf_[NC], vf_[NC];
                         f8_rows_to_frags(ring[s], stage, lane, li, g, kf_, vf_);
                         ATTN_TILE_FRAGS(kf_, vf_, ti);
                     }
-                    load_kv_rows_f8(kb8, vb8, keb, veb, stride_t, min(ti + NW * RING, tl), sk, lane, ring[s]);
+                    load_kv_rows_f8(kb8, vb8, keb, veb, stride_t, min(ti + NW * RING, tl), skl, lane, ring[s]);
                 }
                 t += NW * RING;
+            }
+        } else if constexpr (TAIL) {
+            if (tt >= 0) ATTN_TAIL_FILL();
+        }
+#undef ATTN_TAIL_FILL
+        if constexpr (TAIL) {
+            if (tt >= 0) {
+                constexpr int LDR = D + 8;
+                half8 kf_[NC], vf_[NC];
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    kf_[c] = *reinterpret_cast<const half8*>(tstage + li * LDR + 32 * c + 8 * g);
+                    vf_[c] = *reinterpret_cast<const half8*>(tstage + (16 + li) * LDR + 32 * c + 8 * g);
+                }
+                ATTN_TILE_FRAGS(kf_, vf_, tt);
             }
         }
     } else if (t < t_end) {
@@ -709,6 +779,19 @@ __global__ __launch_bounds__(256, QT == 2 ? ATTN_QT2_OCC : 1) void attn_split_f8
     attn_split_body<128, QT, true>(q, reinterpret_cast<const h16*>(k), reinterpret_cast<const h16*>(v), (int64_t)stride_t,
                                    (int64_t)stride_h, sq, sk_host, sk_dev, H, scale, nsplit, ws, tickets, out, osm, osk, ke, ve,
                                    e_sh);
+}
+
+// The FP8 retrieval-cache form (tf_attn_decode_fp8_tail_act): sk_host = sk_codes + the fp16 tail rows.
+template <int QT>
+__global__ __launch_bounds__(256, QT == 2 ? ATTN_QT2_OCC : 1) void attn_split_f8_tail_kernel(
+    const h16* __restrict__ q, const uint8_t* __restrict__ k, const uint8_t* __restrict__ v, const h16* __restrict__ kt,
+    int sq, int sk_host, int H, int nsplit, int stride_t, int stride_h,                   // <- 14 dwords preloaded into SGPRs
+    float scale, float* __restrict__ ws, unsigned* __restrict__ tickets, h16* __restrict__ out, int64_t osm, int64_t osk,
+    const uint8_t* __restrict__ ke, const uint8_t* __restrict__ ve, int64_t e_sh, const h16* __restrict__ vt, int64_t t_st,
+    int64_t t_sh, int skc) {
+    attn_split_body<128, QT, true, true>(q, reinterpret_cast<const h16*>(k), reinterpret_cast<const h16*>(v), (int64_t)stride_t,
+                                         (int64_t)stride_h, sq, sk_host, nullptr, H, scale, nsplit, ws, tickets, out, osm, osk,
+                                         ke, ve, e_sh, kt, vt, t_st, t_sh, skc);
 }
 
 // ---- 32-key step of the block kernel: two 16-key tiles A, B per softmax update ----------------------------
@@ -1955,14 +2038,20 @@ extern "C" int tf_attn_decode_act(const void* q, const void* k, const void* v, v
 template <int QT>
 static int launch_attn_f8(const void* q, const void* k, const void* v, const void* ke, const void* ve, void* out, int64_t osm,
                           int64_t osk, int64_t stride_t, int64_t stride_h, int64_t e_sh, int sq, int sk, const int32_t* sk_dev,
-                          int H, float scale, int nsplit, float* ws, unsigned* tickets, hipStream_t st) {
+                          int H, float scale, int nsplit, float* ws, unsigned* tickets, hipStream_t st, const void* kt = nullptr,
+                          const void* vt = nullptr, int64_t t_st = 0, int64_t t_sh = 0, int skc = 0) {
     constexpr int D = 128;
     if (tickets && nsplit > FUSED_MERGE_MAX_SPLITS &&
         (H > 64 || nsplit > FUSED_MERGE_BIG_SPLITS || (int64_t)nsplit * H > FUSED_MERGE_BIG_MAX_WGS || !g_attn_rendezvous))
         tickets = nullptr;
-    hipLaunchKernelGGL((attn_split_f8_kernel<QT>), dim3(nsplit, H), dim3(256), 0, st, (const h16*)q, (const uint8_t*)k,
-                       (const uint8_t*)v, sk_dev, sq, sk, H, nsplit, (int)stride_t, (int)stride_h, scale, ws, tickets,
-                       (h16*)out, osm, osk, (const uint8_t*)ke, (const uint8_t*)ve, e_sh);
+    if (kt)                                            // codes [0, skc) then fp16 rows: sk counts both
+        hipLaunchKernelGGL((attn_split_f8_tail_kernel<QT>), dim3(nsplit, H), dim3(256), 0, st, (const h16*)q, (const uint8_t*)k,
+                           (const uint8_t*)v, (const h16*)kt, sq, sk, H, nsplit, (int)stride_t, (int)stride_h, scale, ws, tickets,
+                           (h16*)out, osm, osk, (const uint8_t*)ke, (const uint8_t*)ve, e_sh, (const h16*)vt, t_st, t_sh, skc);
+    else
+        hipLaunchKernelGGL((attn_split_f8_kernel<QT>), dim3(nsplit, H), dim3(256), 0, st, (const h16*)q, (const uint8_t*)k,
+                           (const uint8_t*)v, sk_dev, sq, sk, H, nsplit, (int)stride_t, (int)stride_h, scale, ws, tickets,
+                           (h16*)out, osm, osk, (const uint8_t*)ke, (const uint8_t*)ve, e_sh);
     TF_LAUNCH_CHECK();
     if (tickets) return TF_OK;
     hipLaunchKernelGGL((attn_combine_kernel<D>), dim3(H, sq), dim3(D, COMBINE_GROUPS), 0, st, (const float*)ws,
@@ -1988,6 +2077,32 @@ extern "C" int tf_attn_decode_fp8_act(const void* q, const void* k_codes, const 
                                  sk_dev, H, scale, nsplit, ws, tickets, st);
     return launch_attn_f8<2>(q, k_codes, v_codes, k_exp, v_exp, out, out_sm, out_sk, stride_t, stride_h, exp_stride_h, sq, sk,
                              sk_dev, H, scale, nsplit, ws, tickets, st);
+}
+
+// FP8 retrieval cache (include/triforce_hip.h, "FP8 RETRIEVAL CACHE"): keys [0, sk_codes) as codes, then n_tail fp16 rows, in
+// the one launch — bit-identical to tf_attn_decode_act on [deq(codes) | tail rows] for the same nsplit.
+extern "C" int tf_attn_decode_fp8_tail_act(const void* q, const void* k_codes, const void* v_codes, const void* k_exp,
+                                           const void* v_exp, const void* k_tail, const void* v_tail, void* out, int64_t out_sm,
+                                           int64_t out_sk, int64_t stride_t, int64_t stride_h, int64_t exp_stride_h,
+                                           int64_t tail_stride_t, int64_t tail_stride_h, int sq, int sk_codes, int n_tail,
+                                           const int32_t* sk_dev, int H, int D, float scale, int nsplit, float* ws,
+                                           int64_t ws_floats, uint32_t* tickets, void* stream) {
+    if (!q || !k_codes || !v_codes || !k_exp || !v_exp || !k_tail || !v_tail || !out || !ws) return TF_EINVAL;
+    if (sk_dev) return TF_EINVAL;                                         // the boundary is a host value in this form
+    if (D != 128 || sq < 1 || sq > 32 || sk_codes < 1 || n_tail < 1 || n_tail > 32 || sk_codes > 0x7fffffff - 32) return TF_EINVAL;
+    if (H < 1 || nsplit < 1 || nsplit > COMBINE_MAX_SPLITS) return TF_EINVAL;
+    if (stride_t < D || (stride_t % 16) || (stride_h % 16) || stride_t > 0x7fffffff || stride_h > 0x7fffffff) return TF_EINVAL;
+    if (exp_stride_h < sk_codes) return TF_EINVAL;                        // one exponent byte per coded key of a head
+    if (tail_stride_t < D || (tail_stride_t % 8) || (tail_stride_h % 8)) return TF_EINVAL;      // 16-byte loads
+    if (out_sm < 8 || out_sk < 8 || (out_sm % 4) || (out_sk % 4)) return TF_EINVAL;
+    if (ws_floats < tf_attn_decode_ws_floats(H, sq, D, nsplit)) return TF_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    const int sk = sk_codes + n_tail;
+    if (sq <= 16)
+        return launch_attn_f8<1>(q, k_codes, v_codes, k_exp, v_exp, out, out_sm, out_sk, stride_t, stride_h, exp_stride_h, sq, sk,
+                                 nullptr, H, scale, nsplit, ws, tickets, st, k_tail, v_tail, tail_stride_t, tail_stride_h, sk_codes);
+    return launch_attn_f8<2>(q, k_codes, v_codes, k_exp, v_exp, out, out_sm, out_sk, stride_t, stride_h, exp_stride_h, sq, sk,
+                             nullptr, H, scale, nsplit, ws, tickets, st, k_tail, v_tail, tail_stride_t, tail_stride_h, sk_codes);
 }
 
 extern "C" int64_t tf_attn_block_ws_floats(int H, int D, int nsplit) { return (int64_t)H * nsplit * 128 * (D + 2); }

@@ -76,6 +76,12 @@ SIGNATURES = {
                                       _f32, _i32, _vp, _i64, _vp, _vp]),
     "tf_kv_dequant_rows_pair": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i32, _i32,
                                        _i32, _i32, _i32, _i32, _vp]),
+    "tf_retrieval_gather_fp8": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32,
+                                       _i32, _i32, _vp]),
+    "tf_kv_quant_rows_pair": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64,
+                                     _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "tf_attn_decode_fp8_tail_act": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32,
+                                           _i32, _i32, _vp, _i32, _i32, _f32, _i32, _vp, _i64, _vp, _vp]),
     "tf_topp_probs": (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _vp]),
     "tf_topk_topp_probs": (_i32, [_vp, _vp, _i32, _i32, _f32, _i32, _f32, _vp]),
     "tf_sample_inverse_cdf": (_i32, [_vp, _vp, _vp, _i32, _vp]),

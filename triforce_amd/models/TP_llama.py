@@ -24,7 +24,7 @@ import torch.nn.functional as F
 from .. import ops
 from ..utils.sampling import norm_logits
 from .cache import (DistributedKVCacheBuffer, DistributedRetrievalCache, DistributedRetrievalCache_Seqouia,
-                    DistributedSimpleCache, _refuse_fp8)
+                    DistributedSimpleCache, _refuse_fp8, _refuse_retrieval_fp8)
 from .config_yarn import LlamaConfig
 from .llama_core import (RETRIEVAL_WEIGHTS_ENV, DecoderLayers, LlamaWeights, parse_random_spec, retrieval_weights, rope_tables_for,
                          softmax_scale_for)
@@ -58,6 +58,7 @@ class DistributedLlama:
             raise NotImplementedError(f"{RETRIEVAL_WEIGHTS_ENV}=fp8: the FP8 retrieval tier exists only on the single-GPU "
                                       "engine (models/modeling_llama.py), not on the tensor-parallel / Sequoia engine")
         _refuse_fp8("the tensor-parallel / Sequoia engine")          # TRIFORCE_KV_CACHE=fp8: single-GPU resident cache only
+        _refuse_retrieval_fp8("the tensor-parallel / Sequoia engine")    # TRIFORCE_RETRIEVAL_KV=fp8: single-GPU RetrievalCache only
         self.device = torch.device(device) if device is not None else torch.device("cuda", local_rank)
         self.dtype = dtype
         self.local_rank, self.world_size = local_rank, world_size

@@ -52,6 +52,30 @@ def retrieval_index(override=None):
     return v == "1"
 
 
+# TRIFORCE_RETRIEVAL_KV: storage of the retrieval cache's rows [0, max_budget) (RetrievalCache).  "fp16" (default) or "fp8": the
+# row format of TRIFORCE_KV_CACHE=fp8, codes + one exponent byte per row (include/triforce_hip.h "FP8 RETRIEVAL CACHE", DESIGN
+# section 21).  The retrieval cache only drafts, so the decoding stays lossless with respect to the target either way.
+RETRIEVAL_KV_ENV = "TRIFORCE_RETRIEVAL_KV"
+
+
+def retrieval_kv_dtype(override=None):
+    """"fp16" or "fp8": ``override`` if given, else TRIFORCE_RETRIEVAL_KV.  fp8 needs the fused decode layer (TRIFORCE_FUSE=all)."""
+    v = override if override is not None else os.environ.get(RETRIEVAL_KV_ENV, "fp16")
+    v = str(v).strip().lower() or "fp16"
+    if v not in ("fp16", "fp8"):
+        raise ValueError(f"{RETRIEVAL_KV_ENV}={v!r}: expected fp16 or fp8")
+    if v == "fp8" and ops.FUSE_MODE != "all":
+        raise ValueError(f"{RETRIEVAL_KV_ENV}=fp8 needs the fused decode layer (TRIFORCE_FUSE=all, got {ops.FUSE_MODE!r}): "
+                         "the attention over codes + fp16 spec rows exists only in that form")
+    return v
+
+
+def _refuse_retrieval_fp8(what):
+    if retrieval_kv_dtype() == "fp8":
+        raise NotImplementedError(f"{RETRIEVAL_KV_ENV}=fp8 is implemented for the single-GPU retrieval cache (RetrievalCache) "
+                                  f"only, not for {what}")
+
+
 def _refuse_fp8(what):
     if kv_cache_dtype() == "fp8":
         raise NotImplementedError(f"{KV_CACHE_ENV}=fp8 is implemented for the single-GPU resident cache (FlashSimpleCache) "
@@ -312,9 +336,16 @@ class RetrievalCache(Cache):
     ``prefill`` — the rows [0, prefill) the selection covers — can be moved after construction with ``reanchor``
     (``prefill0`` keeps the constructor's value).  ``index`` (None: TRIFORCE_RETRIEVAL_INDEX) keeps the chunk means of the
     covered region in ``index`` [L][H][Cmax][D] fp16, Cmax = the full cache's capacity // chunk_size, allocated at the first
-    build; ``indexed_chunks[layer]`` chunks of it are valid, and a build computes only the missing ones."""
+    build; ``indexed_chunks[layer]`` chunks of it are valid, and a build computes only the missing ones.
 
-    def __init__(self, model, max_budget=1024, prefill=1024, chunk_size=8, gamma=6, index=None) -> None:
+    ``kv_dtype`` (None: TRIFORCE_RETRIEVAL_KV) = "fp8" stores rows [0, max_budget) as e4m3fn codes ``kc`` / ``vc``
+    [L][H][max_budget][D] with exponent bytes ``ke`` / ``ve`` [L][H][max_budget] (gathered and refreshed as codes: copied from
+    an FP8 full cache, quantized from an fp16 one); the gamma + 1 rows of a spec forward stay fp16 in ``spec_k`` / ``spec_v``
+    [L][H][gamma + 1][D]; ``.k`` / ``.v`` do not exist then."""
+
+    fp8 = False
+
+    def __init__(self, model, max_budget=1024, prefill=1024, chunk_size=8, gamma=6, index=None, kv_dtype=None) -> None:
         self.chunk_size = chunk_size
         self.prefill = self.prefill0 = prefill
         self.chunks = prefill // self.chunk_size
@@ -327,13 +358,60 @@ class RetrievalCache(Cache):
         self.layers, self.num_heads, self.head_dim = _geom(model)
         self.hidden_size = model.config.hidden_size
         self.device = model.device
-        self.k, self.v = _alloc(self.layers, self.num_heads, self.real_budget, self.head_dim, self.device)
-        self.key_cache, self.value_cache = _ref_view(self.k), _ref_view(self.v)
+        if retrieval_kv_dtype(kv_dtype) == "fp8":
+            self._init_fp8()
+        else:
+            self.k, self.v = _alloc(self.layers, self.num_heads, self.real_budget, self.head_dim, self.device)
+            self.key_cache, self.value_cache = _ref_view(self.k), _ref_view(self.v)
         self.init_graph = False
         self.last_scores = [None] * self.layers      # (H,C) fp16 / (H,sets) int32 of the last build, for parity checks
         self.last_idx = [None] * self.layers
         self.use_index = retrieval_index(index)
         self.index, self.indexed_chunks = None, [0] * self.layers
+
+    def _init_fp8(self):
+        L, H, T, D = self.layers, self.num_heads, self.max_budget, self.head_dim
+        if D != 128:
+            raise NotImplementedError(f"{RETRIEVAL_KV_ENV}=fp8 needs head_dim 128 (got {D}): the FP8 row format and its "
+                                      "attention are built for that width")
+        self.fp8 = True
+        f8 = torch.float8_e4m3fn
+        self.kc = torch.zeros(L, H, T, D, dtype=f8, device=self.device)
+        self.vc = torch.zeros(L, H, T, D, dtype=f8, device=self.device)
+        self.ke = torch.full((L, H, T), ops.KV_FP8_EMIN + 127, dtype=torch.uint8, device=self.device)
+        self.ve = torch.full((L, H, T), ops.KV_FP8_EMIN + 127, dtype=torch.uint8, device=self.device)
+        self.spec_k, self.spec_v = _alloc(L, H, self.gamma + 1, D, self.device)
+        self.key_cache, self.value_cache = _ref_view(self.kc), _ref_view(self.vc)
+
+    def __getattr__(self, name):
+        # only reached for missing attributes: .k / .v of an FP8 retrieval cache (fp16 storage that does not exist)
+        if name in ("k", "v") and self.__dict__.get("fp8", False):
+            raise AttributeError(f"RetrievalCache.{name}: the cache holds FP8 codes ({RETRIEVAL_KV_ENV}=fp8), there is no fp16 "
+                                 f"storage to index; use kc / vc / ke / ve, spec_k / spec_v or dequantize(layer)")
+        raise AttributeError(name)
+
+    def nbytes(self):
+        """Device bytes of the K / V storage (FP8: codes, exponents and the fp16 spec rows)."""
+        if not self.fp8:
+            return self.k.nbytes + self.v.nbytes
+        return sum(t.nbytes for t in (self.kc, self.vc, self.ke, self.ve, self.spec_k, self.spec_v))
+
+    def dequantize(self, layer):
+        """(k, v): fresh (H, real_budget, D) fp16 tensors of what the spec forward's attention reads in ``layer``: deq of the
+        coded rows, then the fp16 spec rows."""
+        if not self.fp8:
+            return self.k[layer].clone(), self.v[layer].clone()
+        H, D, B = self.num_heads, self.head_dim, self.max_budget
+        k = torch.empty(1, H, self.real_budget, D, dtype=torch.float16, device=self.device)
+        v = torch.empty_like(k)
+        ops.kv_dequant_rows_pair(self.kc[layer:layer + 1], self.vc[layer:layer + 1], self.ke[layer:layer + 1],
+                                 self.ve[layer:layer + 1], k, v, 0, 0, B)
+        k[0, :, B:], v[0, :, B:] = self.spec_k[layer], self.spec_v[layer]
+        return k[0], v[0]
+
+    def layer_codes(self, layer):
+        """FP8: (k codes, v codes, k exponents, v exponents) of ``layer``: (H,max_budget,D) and (H,max_budget) views."""
+        return self.kc[layer], self.vc[layer], self.ke[layer], self.ve[layer]
 
     def reanchor(self, new_prefill):
         """Move the covered region to rows [0, new_prefill): the tail then starts there.  Moves no data — the caller follows
@@ -365,6 +443,8 @@ class RetrievalCache(Cache):
               " | Chunks:", self.chunks, " | Select Sets:", self.select_sets)
 
     def layer_kv(self, layer_idx):
+        if self.fp8:                                  # the fp16 part: the spec rows (their row 0 is key max_budget)
+            return self.spec_k[layer_idx], self.spec_v[layer_idx]
         return self.k[layer_idx], self.v[layer_idx]
 
     @property
@@ -388,15 +468,42 @@ class RetrievalCache(Cache):
         else:
             scores = ops.retrieval_score(src_k, q[0].contiguous(), self.chunks, self.chunk_size)
         idx = ops.retrieval_topk(scores, self.select_sets)
-        ops.retrieval_gather(src_k, src_v, idx, self.k[layer_idx], self.v[layer_idx], self.chunk_size)
+        if not self.fp8:
+            ops.retrieval_gather(src_k, src_v, idx, self.k[layer_idx], self.v[layer_idx], self.chunk_size)
+        elif getattr(kv_cache, "fp8", False):         # codes -> codes: the middle tier reads the deq the target reads
+            kc, vc, ke, ve = kv_cache.layer_codes(layer_idx)
+            ops.retrieval_gather_fp8(kc, vc, idx, *self.layer_codes(layer_idx), self.chunk_size, src_exp=(ke, ve))
+        else:
+            ops.retrieval_gather_fp8(src_k, src_v, idx, *self.layer_codes(layer_idx), self.chunk_size)
         self.last_scores[layer_idx], self.last_idx[layer_idx] = scores, idx
         if layer_idx == self.layers - 1:
             self.init_graph = True
+
+    def _copy_tail_fp8(self, kv_cache, layers, g):
+        """The tail refresh into codes: copied from an FP8 full cache, quantized from fp16 rows."""
+        dst = (self.kc[layers], self.vc[layers], self.ke[layers], self.ve[layers])
+        if getattr(kv_cache, "fp8", False):
+            src = (kv_cache.kc[layers], kv_cache.vc[layers])
+            src_exp, t0 = (kv_cache.ke[layers], kv_cache.ve[layers]), self.prefill
+        else:
+            src_k, src_v, t0 = kv_cache.tail_source(layers, self.prefill)
+            src, src_exp = (src_k, src_v), None
+        if layers == slice(0, self.layers) and self.kc.is_cuda and type(kv_cache) is FlashSimpleCache:
+            # the per-step refresh over the resident cache: fixed tensors -> a launch plan, as in _copy_tail
+            key = (id(kv_cache), src[0].data_ptr())
+            plan = getattr(self, "_tail_plan", None)
+            if plan is None or plan[0] != key:
+                plan = self._tail_plan = (key, ops.KvQuantPairPlan(*src, *dst, src_exp=src_exp), t0)
+            plan[1](plan[2], self.max_budget - g, g)
+            return
+        ops.kv_quant_rows_pair(*src, *dst, t0, self.max_budget - g, g, src_exp=src_exp)
 
     def _copy_tail(self, kv_cache, layers):
         g = kv_cache.seq_len - self.prefill
         if g > self.max_budget:
             raise IndexError(f"generated tail ({g}) exceeds the retrieval budget ({self.max_budget})")
+        if self.fp8:
+            return self._copy_tail_fp8(kv_cache, layers, g)
         if getattr(kv_cache, "fp8", False):           # FP8 cache: the generated rows are dequantized into the retrieval cache
             ops.kv_dequant_rows_pair(kv_cache.kc[layers], kv_cache.vc[layers], kv_cache.ke[layers], kv_cache.ve[layers],
                                      self.k[layers], self.v[layers], self.prefill, self.max_budget - g, g)
@@ -423,14 +530,26 @@ class RetrievalCache(Cache):
 
     def update(self, new_k_cache, new_v_cache, layer_idx):
         k, v = _rows(new_k_cache), _rows(new_v_cache)
+        if self.fp8:                                  # the spec rows stay fp16; returns [deq(codes) | spec rows], reference shape
+            self.spec_k[layer_idx], self.spec_v[layer_idx] = k.permute(1, 0, 2), v.permute(1, 0, 2)
+            kd, vd = self.dequantize(layer_idx)
+            return kd.permute(1, 0, 2).unsqueeze(0), vd.permute(1, 0, 2).unsqueeze(0)
         s = self.spec_slot
         self.k[layer_idx, :, s:] = k.permute(1, 0, 2)
         self.v[layer_idx, :, s:] = v.permute(1, 0, 2)
         return self.key_cache[layer_idx][:, :self.real_budget], self.value_cache[layer_idx][:, :self.real_budget]
 
     def reset(self):
-        self.k.zero_()
-        self.v.zero_()
+        if self.fp8:
+            for t in (self.kc, self.vc):
+                t.view(torch.uint8).zero_()
+            self.ke.fill_(ops.KV_FP8_EMIN + 127)
+            self.ve.fill_(ops.KV_FP8_EMIN + 127)
+            self.spec_k.zero_()
+            self.spec_v.zero_()
+        else:
+            self.k.zero_()
+            self.v.zero_()
         if self.prefill != self.prefill0:            # a new prompt: the region the cache was built over, no chunk mean valid
             self.reanchor(self.prefill0)
         self.indexed_chunks = [0] * self.layers
@@ -630,6 +749,7 @@ class DistributedRetrievalCache:
     without a reset raises (cache.py:519-520,577-580)."""
 
     def __init__(self, config, max_budget=1024, device=None, prefill=1024, chunk_size=8, gamma=6) -> None:
+        _refuse_retrieval_fp8("DistributedRetrievalCache (the tensor-parallel and Sequoia engines)")
         self.config = config
         self.world_size, self.local_rank = config.world_size, config.local_rank
         self.device = torch.device(device)

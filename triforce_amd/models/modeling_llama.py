@@ -108,6 +108,11 @@ class LlamaForCausalLM:
         if f8 and not fused:
             raise RuntimeError(f"the FP8 retrieval tier needs the fused decode layer ({q_len} rows)")
         assert fused or dev_len is None, "the captured full-cache forward needs the fused decode kernels"
+        # FP8 retrieval cache (TRIFORCE_RETRIEVAL_KV=fp8): the spec forward's attention reads codes, then the
+        # fp16 rows this forward appends, in one launch
+        rkv8 = spec and getattr(graph_cache, "fp8", False)
+        if rkv8 and not fused:
+            raise RuntimeError(f"the FP8 retrieval cache needs the fused decode layer ({q_len} rows)")
         # the fused layer keeps residual stream / attention output / SwiGLU output k-octet-major (ops.Act): the GEMMs' B
         # operand is then read in 256-byte runs (ops.py, "activation layouts")
         packed = fused and ops.act_packed(q_len)
@@ -135,7 +140,11 @@ class LlamaForCausalLM:
                 graph_cache.init_graph_cache(kv_cache, q[:1], i)
             if codes and not fused and (build or rebuild):      # the build used the scratch: rows [0, sk) again
                 kl, vl = kv_cache.scratch_layer(i, sk)
-            a = self._attention(q, kl, vl, sk, codes if fused else None, sk_dev, packed, spec or dev_len is not None)
+            if rkv8:
+                a = ops.attn_decode_fp8_tail(q, *graph_cache.layer_codes(i), kl, vl, graph_cache.max_budget, self.scale,
+                                             packed=packed)
+            else:
+                a = self._attention(q, kl, vl, sk, codes if fused else None, sk_dev, packed, spec or dev_len is not None)
             if streaming and dev_len is None:
                 kv_cache.layer_done(i, slot, q_len)
             if fused:
@@ -155,6 +164,8 @@ class LlamaForCausalLM:
         rows [0, slot).  A captured forward (dev_len) appends at a slot the device holds and is sized by the capacity."""
         if spec_cache is not None:                      # :226-227  retrieval-cache forward
             assert q_len == spec_cache.gamma + 1, "spec forward takes exactly gamma+1 tokens (cache.py:184-189)"
+            if getattr(spec_cache, "fp8", False):       # FP8 retrieval cache: the views are its fp16 spec rows alone
+                return (*spec_cache.layer_kv(i), 0, spec_cache.real_budget, None)
             return (*spec_cache.layer_kv(i), spec_cache.spec_slot, spec_cache.real_budget, None)
         if dev_len is not None:                         # captured full-cache forward: lengths live on the device
             slot, sk = 0, kv_cache.max_budget

@@ -778,6 +778,138 @@ def kv_dequant_rows_pair(src_k, src_v, exp_k, exp_v, dst_k, dst_v, src_t0, dst_t
                                                 _stream()), "tf_kv_dequant_rows_pair")
 
 
+# ---- FP8 retrieval cache (TRIFORCE_RETRIEVAL_KV=fp8; include/triforce_hip.h "FP8 RETRIEVAL CACHE") --------
+def attn_decode_fp8_tail(q, k_codes, v_codes, k_exp, v_exp, k_tail, v_tail, sk_codes, scale, n_tail=None, nsplit=None,
+                         packed=False):
+    """attn_decode over keys [0, sk_codes) of an FP8 layer (codes (H,T,D), exponents (H,T)) followed by the first n_tail rows
+    (default: all) of the fp16 views k_tail / v_tail (H,n,D), in one launch: bit-identical to attn_decode on
+    [deq(codes) | tail rows] for the same nsplit."""
+    _dev(q, k_codes, v_codes, k_exp, v_exp, k_tail, v_tail)
+    sq, H, D = q.shape
+    assert q.dtype == _HALF and q.is_contiguous()
+    st, sh = _f8_kv(k_codes)
+    assert _f8_kv(v_codes) == (st, sh)
+    esh = _f8_exp(k_exp)
+    assert _f8_exp(v_exp) == esh
+    tst, tsh = _kv(k_tail)
+    assert _kv(v_tail) == (tst, tsh) and k_tail.shape == v_tail.shape and k_tail.shape[0] == H
+    n_tail = k_tail.shape[1] if n_tail is None else int(n_tail)
+    if not (1 <= sk_codes <= k_codes.shape[1] and sk_codes <= k_exp.shape[1] and 1 <= n_tail <= k_tail.shape[1]):
+        raise IndexError(f"attn_decode_fp8_tail: {sk_codes} coded keys of {k_codes.shape[1]}, {n_tail} tail rows of "
+                         f"{k_tail.shape[1]} (the kernel does not bounds-check)")
+    if nsplit is None:
+        nsplit = _pick_nsplit(H, int(sk_codes) + n_tail)
+    ws = _workspace(q.device, _ws_floats(H, sq, D, nsplit))
+    out = Act.empty(sq, H * D, q.device) if packed else torch.empty(sq, H * D, dtype=_HALF, device=q.device)
+    op, osm, osk = _lay(out)
+    stream = _stream()
+    tickets = _ticket_row(q.device, stream.value or 0) if ATTN_FUSED_MERGE and H <= _TICKET_WORDS else None
+    hip.check(hip.lib().tf_attn_decode_fp8_tail_act(_ptr(q), _ptr(k_codes), _ptr(v_codes), _ptr(k_exp), _ptr(v_exp), _ptr(k_tail),
+                                                    _ptr(v_tail), op, osm, osk, st, sh, esh, tst, tsh, sq, int(sk_codes), n_tail,
+                                                    None, H, D, float(scale), nsplit, _ptr(ws), ws.numel(), _ptr(tickets),
+                                                    stream), "tf_attn_decode_fp8_tail_act")
+    return out
+
+
+def retrieval_gather_fp8_ref(k_src, v_src, idx, chunk):
+    """Host restatement of retrieval_gather_fp8 from fp16 rows: (k codes, v codes, k exponents, v exponents) of the gathered
+    rows, (H, sets * chunk, D) and (H, sets * chunk) — kv_quantize_ref of the rows retrieval_gather would copy."""
+    rows = (idx.long().unsqueeze(-1) * chunk + torch.arange(chunk, device=idx.device)).reshape(idx.shape[0], -1)   # (H, sets * chunk)
+    pick = rows.unsqueeze(-1).expand(-1, -1, k_src.shape[2])
+    kc, ke, _ = kv_quantize_ref(torch.gather(k_src, 1, pick))
+    vc, ve, _ = kv_quantize_ref(torch.gather(v_src, 1, pick))
+    return kc, vc, ke, ve
+
+
+def retrieval_gather_fp8(k_src, v_src, idx, k_codes, v_codes, k_exp, v_exp, chunk, src_exp=None):
+    """retrieval_gather into an FP8 layer (codes (H,T,D), exponents (H,T)), K and V in one launch.  k_src / v_src: (H,T',D) fp16
+    views, quantized (bit-identical to retrieval_gather_fp8_ref); or with src_exp = (k exponents, v exponents) the e4m3fn
+    codes of an FP8 layer, copied with their exponent bytes."""
+    _dev(k_src, v_src, idx, k_codes, v_codes, k_exp, v_exp)
+    H, T, D = k_src.shape
+    if src_exp is None:
+        sst, ssh = _kv(k_src)
+        assert _kv(v_src) == (sst, ssh)
+        sek = sev = None
+        sesh = 0
+    else:
+        sst, ssh = _f8_kv(k_src)
+        assert _f8_kv(v_src) == (sst, ssh)
+        sek, sev = src_exp
+        _dev(sek, sev)
+        sesh = _f8_exp(sek)
+        assert _f8_exp(sev) == sesh and sek.shape[1] >= T
+    cst, csh = _f8_kv(k_codes)
+    assert _f8_kv(v_codes) == (cst, csh) and k_codes.shape[0] == H and k_codes.shape[2] == D
+    esh = _f8_exp(k_exp)
+    assert _f8_exp(v_exp) == esh
+    assert idx.dtype == torch.int32 and idx.is_contiguous() and idx.shape[0] == H
+    sets = idx.shape[1]
+    if sets * chunk > k_codes.shape[1] or sets * chunk > k_exp.shape[1]:
+        raise IndexError(f"retrieval_gather_fp8: {sets} chunks of {chunk} rows leave the {k_codes.shape[1]}-row cache")
+    hip.check(hip.lib().tf_retrieval_gather_fp8(_ptr(k_src), _ptr(v_src), sst, ssh, _ptr(sek), _ptr(sev), sesh, _ptr(idx),
+                                                _ptr(k_codes), _ptr(v_codes), _ptr(k_exp), _ptr(v_exp), cst, csh, esh, sets,
+                                                int(chunk), H, D, _stream()), "tf_retrieval_gather_fp8")
+
+
+def _lht_exp(t):
+    assert t.dim() == 3 and t.stride(2) == 1 and t.dtype == torch.uint8, "(L,H,T) uint8 exponents expected"
+    return t.stride(0), t.stride(1)                  # stride_l, stride_h
+
+
+def _lhtd_f8(t):
+    assert t.dim() == 4 and t.stride(3) == 1 and t.dtype == torch.float8_e4m3fn, "(L,H,T,D) e4m3fn expected"
+    return t.stride(0), t.stride(2), t.stride(1)     # stride_l, stride_t, stride_h
+
+
+class KvQuantPairPlan:
+    """Rows of K and V into an FP8 cache over fixed tensors, all layers in one launch: dst codes (L,H,T,D) / exponents
+    (L,H,T) rows [dst_t0, dst_t0 + n) = src rows [src_t0, src_t0 + n).  src_k / src_v: (L,H,T',D) fp16 views (quantized by the
+    FP8 KV contract), or with ``src_exp`` = (k exponents, v exponents) e4m3fn codes (copied with their exponent bytes)."""
+
+    def __init__(self, src_k, src_v, dst_kc, dst_vc, dst_ke, dst_ve, src_exp=None):
+        _dev(src_k, src_v, dst_kc, dst_vc, dst_ke, dst_ve)
+        L, H, _, D = src_k.shape
+        assert src_k.shape == src_v.shape and dst_kc.shape == dst_vc.shape and dst_ke.shape == dst_ve.shape
+        assert dst_kc.shape[0] == L and dst_kc.shape[1] == H and dst_kc.shape[3] == D and dst_ke.shape[:2] == (L, H)
+        if src_exp is None:
+            src = _lhtd(src_k)
+            assert _lhtd(src_v) == src
+            exp = (None, None, 0, 0)
+            self.src_rows = src_k.shape[2]
+        else:
+            src = _lhtd_f8(src_k)
+            assert _lhtd_f8(src_v) == src
+            sek, sev = src_exp
+            _dev(sek, sev)
+            assert _lht_exp(sek) == _lht_exp(sev) and sek.shape[:2] == (L, H) and sev.shape == sek.shape
+            exp = (_ptr(sek), _ptr(sev)) + _lht_exp(sek)
+            self.src_rows = min(src_k.shape[2], sek.shape[2])
+        dst = _lhtd_f8(dst_kc)
+        assert _lhtd_f8(dst_vc) == dst and _lht_exp(dst_ke) == _lht_exp(dst_ve)
+        self.keep = (src_k, src_v, dst_kc, dst_vc, dst_ke, dst_ve, src_exp)
+        self.dst_rows = min(dst_kc.shape[2], dst_ke.shape[2])
+        self.head = (_ptr(src_k), _ptr(src_v)) + src + exp + (_ptr(dst_kc), _ptr(dst_vc)) + dst \
+            + (_ptr(dst_ke), _ptr(dst_ve)) + _lht_exp(dst_ke)
+        self.dims = (L, H, D)
+        self.fn = hip.lib().tf_kv_quant_rows_pair
+
+    def __call__(self, src_t0, dst_t0, n):
+        if n <= 0:
+            return
+        if src_t0 < 0 or dst_t0 < 0 or src_t0 + n > self.src_rows or dst_t0 + n > self.dst_rows:
+            raise IndexError(f"kv_quant_rows_pair: rows [{src_t0}, {src_t0 + n}) of {self.src_rows} -> [{dst_t0}, {dst_t0 + n}) of "
+                             f"{self.dst_rows} leave the cache (the kernel does not bounds-check)")
+        hip.check(self.fn(*self.head, int(src_t0), int(dst_t0), int(n), *self.dims, _stream()), "tf_kv_quant_rows_pair")
+
+
+def kv_quant_rows_pair(src_k, src_v, dst_kc, dst_vc, dst_ke, dst_ve, src_t0, dst_t0, n, src_exp=None):
+    """One call of a KvQuantPairPlan over these tensors (the tensors are validated on every call)."""
+    if n <= 0:
+        return
+    KvQuantPairPlan(src_k, src_v, dst_kc, dst_vc, dst_ke, dst_ve, src_exp)(src_t0, dst_t0, n)
+
+
 def attn_block(q, k_layer, v_layer, sk, scale, nsplit=None, tree_mask=None, mask_row0=0, tree_start=0):
     """Attention of a block of <=128 query rows in one pass over the keys.  tree_mask None: bottom-right causal
     (a prefill chunk).  tree_mask (n_rows, words) int32 bit rows: Sequoia tree attention — keys [0, tree_start)
