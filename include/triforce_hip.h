@@ -706,6 +706,41 @@ int tf_ar_set_error_mirror(void* flags_local, void* host_word);
 /* Fault injection for tests: sets (code > 0) or clears (0) the sticky error word of a control block from the host. */
 int tf_ar_inject_error(void* flags_local, int code);
 
+/* -------------------------------------------------------------------------------------------
+ * GROUPED-QUERY ATTENTION: H query heads over Hkv = H / g KV heads, query head h reads KV head h / g —
+ * the reference's repeat_kv (models/tensor_op.py:8-17) in front of flash_attn_with_kvcache (models/modeling_llama.py:240;
+ * its projections at :213-215 and its caches, models/cache.py:20-61, already take num_key_value_heads).  Each entry is its
+ * multi-head neighbour with two head counts; H % Hkv != 0, sizes < 1, NULL buffers and D other than 64 / 128 -> TF_EINVAL.
+ * tf_attn_decode_gqa_act: tf_attn_decode_act (models/modeling_llama.py:240 for verify / decode blocks of sq <= 32 rows).
+ *   The sq token rows of gs query heads of one KV head are stacked into one gs * sq <= 32 row problem of the split-KV
+ *   kernel, gs = the largest divisor of g with gs * sq <= 32; a KV head has g / gs such sub-groups, each its own workgroup
+ *   column (cols = Hkv * g / gs).  K / V is read from HBM once per KV head whenever g * sq <= 32, else g / gs times.
+ *   ws: tf_attn_decode_ws_floats(cols, gs * sq, D, nsplit) floats; split count: tf_attn_decode_pick_nsplit(cols, sk);
+ *   tickets: cols zeroed words = one launch (left zero), NULL = two launches; both bit-identical.  sk_dev as in
+ *   tf_attn_decode_act.  K / V fp16.
+ * tf_attn_prefill_gqa: tf_attn_prefill (utils/graph_infer.py:30-37 -> models/modeling_llama.py:240 with q_len = the chunk),
+ *   1 <= sq <= 4096; split count and workspace from tf_attn_prefill_pick_nsplit / _ws_floats with H = the QUERY heads.
+ * tf_skinny_qkv_rope_gqa_act: tf_skinny_qkv_rope_act (models/modeling_llama.py:213-224: q / k / v projections + RoPE, then
+ *   the cache update of models/cache.py:50-61); weight rows [q: H D | k: Hkv D | v: Hkv D], N = (H + 2 Hkv) D, packed in
+ *   triforce_amd.ops.rope_row_order(H, Hkv, D); q_out [M][H][D]; k / v rows to KV head hd of the Hkv-head cache.  Row-major
+ *   x: xs_m = ld, xs_k = 8.
+ * tf_rope_append_gqa: tf_rope_append for fused rows [q: H D | k: Hkv D | v: Hkv D] (the un-fused prefill-chunk path).
+ * ------------------------------------------------------------------------------------------- */
+int tf_attn_decode_gqa_act(const void* q, const void* k, const void* v, void* out, int64_t out_sm, int64_t out_sk,
+                           int64_t stride_t, int64_t stride_h, int sq, int sk, const int32_t* sk_dev, int H, int Hkv, int D,
+                           float scale, int nsplit, float* ws, int64_t ws_floats, uint32_t* tickets, void* stream);
+int tf_attn_prefill_gqa(const void* q, const void* k, const void* v, void* out, int64_t stride_t, int64_t stride_h,
+                        int sq, int sk, int H, int Hkv, int D, float scale, int nsplit, float* ws, int64_t ws_floats,
+                        void* stream);
+int tf_skinny_qkv_rope_gqa_act(const void* wqkv_packed, const void* x, int64_t xs_m, int64_t xs_k, const void* ln_w,
+                               float eps, const float* ss_in, const void* cos, const void* sin, const int64_t* positions,
+                               void* q_out, void* k_cache, void* v_cache, int64_t stride_t, int64_t stride_h, int slot0,
+                               const int32_t* slot0_dev, int M, int H, int Hkv, int D, int K, int rotate_k, void* stream);
+int tf_rope_append_gqa(const void* qkv, int64_t qkv_row_stride, const void* cos, const void* sin,
+                       const int64_t* positions, void* q_out, void* k_cache, void* v_cache,
+                       int64_t stride_t, int64_t stride_h, int slot0, const int32_t* slot0_dev,
+                       int rows, int H, int Hkv, int D, int rotate_k, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,7 +23,11 @@ def build_engine(args, target, draft):
     # (--followups: a question's rows sit between the document and its answer; 0 by default.  --reanchor_at: the answer may
     #  be longer than the retrieval budget, its rows are the gen_len rows the full cache has room for either way)
     full = FlashSimpleCache(target, args.prefill + args.gen_len + 16 + (args.followup_len if args.followups > 0 else 0))
-    retrieval = RetrievalCache(target, max_budget=args.budget, prefill=args.prefill, gamma=args.gamma,
+    budget = args.budget
+    if budget > args.prefill:                      # a prompt shorter than the budget: every chunk of it is selected
+        budget = args.prefill - args.prefill % args.chunk_size
+        print(colored(f"retrieval budget {args.budget} > prefill {args.prefill}: using {budget}", "yellow"))
+    retrieval = RetrievalCache(target, max_budget=budget, prefill=args.prefill, gamma=args.gamma,
                                chunk_size=args.chunk_size)
     streaming = StreamingLLMEvictionCache(draft, start_size=16, recent_size=args.draft_cache_budget - 16 - args.gamma,
                                           gamma=args.gamma)

@@ -296,11 +296,13 @@ struct TreeMask {                      // tree-attention visibility bits (block 
 
 // MASKED = false: every key of the tile is visible to every query row of the wave (all tiles but the last one or
 // two of a causal stream; the unmasked prefix of a tree pass) — the per-key compare/select chain is dropped.
-template <int D, int QT, bool TREE = false, bool MASKED = true>
+// GQA = true (attn_split_body's grouped-query form): the wave's rows are the sq token rows of several query heads stacked;
+// qtok[qt] is the TOKEN index of this lane's row of q-tile qt, which is what the causal limit is made of.
+template <int D, int QT, bool TREE = false, bool MASKED = true, bool GQA = false>
 __device__ __forceinline__ void attn_tile(AttnState<D, QT>& st, const half8 (&kf)[D / 32],
                                           const half8 (&vf)[D / 32], half8 sel0, half8 sel1, int tile,
                                           int sk, int sq, float scale, int li, int g, int qbase = 0,
-                                          TreeMask tm = TreeMask{nullptr, 0, 0, 0}) {
+                                          TreeMask tm = TreeMask{nullptr, 0, 0, 0}, const int* qtok = nullptr) {
     constexpr int NC = D / 32, NT = D / 16;
     // V tile -> key-contiguous fragments through the matrix core (exact: multiplies by 0/1)
     half4 va[NT];
@@ -317,7 +319,7 @@ __device__ __forceinline__ void attn_tile(AttnState<D, QT>& st, const half8 (&kf
 #pragma unroll
         for (int c = 0; c < NC; ++c) s = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[c], st.qf[qt][c], s, 0, 0, 0);
         // lane holds S^T[key = tile*16 + 4g + r][q = qt*16 + li]
-        const int qrow = qbase + qt * 16 + li;
+        const int qrow = GQA ? qtok[qt] : qbase + qt * 16 + li;
         const int kmax = (qrow < sq) ? (sk - sq + qrow) : (sk - 1);   // bottom-right causal
         float x[4];
         bool ok[4];
@@ -378,14 +380,22 @@ __device__ __forceinline__ void attn_tile(AttnState<D, QT>& st, const half8 (&kf
 // ws layout: o[H][nsplit][QR][D] | m[H][nsplit][QR] | l[H][nsplit][QR],  QR = QT*16
 // F8: k / v are e4m3fn codes (strides in bytes) with exponent bytes ke / ve ([H][e_sh] per head, one per key)
 // TAIL (with F8): only keys [0, skc) are codes; keys [skc, sk) are the fp16 rows kt / vt ([H][t_sh] halves per head, t_st per row)
-template <int D, int QT, bool F8 = false, bool TAIL = false>
+// GQA (fp16 stream only): blockIdx.y is a (KV head, sub-group) column c of a grouped-query launch.  The sq token rows of the
+// gs query heads c * gs .. c * gs + gs - 1 — all of KV head c * gs / g — are stacked into one gs * sq <= QR row problem:
+// stacked row r = (query head c * gs + r / sq, token r % sq).  H is the number of QUERY heads (the row stride of q and out);
+// the workspace and the tickets are indexed by the column (gridDim.y of them).  The K/V stream loop, the staging and the
+// softmax are the multi-head ones; what differs is the Q fragment load, the causal limit (a row's TOKEN index) and where
+// the merge writes a row.
+template <int D, int QT, bool F8 = false, bool TAIL = false, bool GQA = false>
 __device__ __forceinline__ void attn_split_body(
     const h16* __restrict__ q, const h16* __restrict__ k, const h16* __restrict__ v, int64_t stride_t,
     int64_t stride_h, int sq, int sk_host, const int32_t* __restrict__ sk_dev, int H, float scale, int nsplit,
     float* __restrict__ ws, unsigned* __restrict__ tickets, h16* __restrict__ out, int64_t osm, int64_t osk,
     const uint8_t* __restrict__ ke = nullptr, const uint8_t* __restrict__ ve = nullptr, int64_t e_sh = 0,
-    const h16* __restrict__ kt = nullptr, const h16* __restrict__ vt = nullptr, int64_t t_st = 0, int64_t t_sh = 0, int skc = 0) {
+    const h16* __restrict__ kt = nullptr, const h16* __restrict__ vt = nullptr, int64_t t_st = 0, int64_t t_sh = 0, int skc = 0,
+    int gs = 1, int g_kv = 1) {
     static_assert(!TAIL || F8, "the fp16 tail rows follow an FP8 stream");
+    static_assert(!GQA || !F8, "the grouped-query form reads an fp16 cache");
     constexpr int NC = D / 32, NT = D / 16, QR = QT * 16;
     constexpr int NW = 4;                              // waves per workgroup
     const int split = blockIdx.x, h = blockIdx.y;
@@ -401,13 +411,20 @@ __device__ __forceinline__ void attn_split_body(
     const int t_end = min(ntiles, t_begin + tps);
 
     AttnState<D, QT> st;
+    const int rows = GQA ? gs * sq : sq;               // query rows of this workgroup (GQA: the stacked rows)
+    const int Hw = GQA ? (int)gridDim.y : H;           // heads of the workspace layout (GQA: columns)
+    int qtok[QT];                                      // GQA: token index of this lane's row per q-tile (padding rows: a valid one)
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
         const int row = qt * 16 + li;
+        qtok[qt] = GQA ? row % sq : row;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             half8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-            st.qf[qt][c] = (row < sq) ? load_half8(q + ((int64_t)row * H + h) * D + 32 * c + 8 * g) : z;
+            if constexpr (GQA)
+                st.qf[qt][c] = (row < rows) ? load_half8(q + ((int64_t)qtok[qt] * H + h * gs + row / sq) * D + 32 * c + 8 * g) : z;
+            else
+                st.qf[qt][c] = (row < sq) ? load_half8(q + ((int64_t)row * H + h) * D + 32 * c + 8 * g) : z;
         }
 #pragma unroll
         for (int t = 0; t < NT; ++t) st.acc[qt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -421,8 +438,9 @@ __device__ __forceinline__ void attn_split_body(
         sel1[e] = (8 * g + e == 16 + li) ? (h16)1.0f : (h16)0.0f;
     }
 
-    const h16* kbase = k + (int64_t)h * stride_h;
-    const h16* vbase = v + (int64_t)h * stride_h;
+    const int hkv = GQA ? (h * gs) / g_kv : h;         // the KV head this workgroup streams
+    const h16* kbase = k + (int64_t)hkv * stride_h;
+    const h16* vbase = v + (int64_t)hkv * stride_h;
 
     // One block of LDS: the row -> fragment staging tiles of the stream loop, then — behind a barrier — the merge of the
     // waves' partial results
@@ -437,6 +455,7 @@ __device__ __forceinline__ void attn_split_body(
 #define ATTN_TILE_FRAGS(KF, VF, T)                                                                    \
     do {                                                                                                \
         if ((T) * 16 + 15 <= sk - sq) attn_tile<D, QT, false, false>(st, KF, VF, sel0, sel1, (T), sk, sq, scale, li, g); \
+        else if constexpr (GQA) attn_tile<D, QT, false, true, true>(st, KF, VF, sel0, sel1, (T), sk, sq, scale, li, g, 0, TreeMask{nullptr, 0, 0, 0}, qtok); \
         else attn_tile<D, QT, false, true>(st, KF, VF, sel0, sel1, (T), sk, sq, scale, li, g);        \
     } while (0)
     // what was loaded are rows; the fragments are made here, right before their use
@@ -549,8 +568,8 @@ __device__ __forceinline__ void attn_split_body(
     float (*sm_l)[16] = sm_m + NW;
     __syncthreads();                                   // another wave may still be reading its staging tile where this one is about to write
     float* ws_o = ws;
-    float* ws_m = ws + (int64_t)H * nsplit * QR * D;
-    float* ws_l = ws_m + (int64_t)H * nsplit * QR;
+    float* ws_m = ws + (int64_t)Hw * nsplit * QR * D;
+    float* ws_l = ws_m + (int64_t)Hw * nsplit * QR;
     const int64_t pbase = ((int64_t)h * nsplit + split) * QR;
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
@@ -613,7 +632,7 @@ __device__ __forceinline__ void attn_split_body(
         s_last = __hip_atomic_fetch_add(&tickets[h], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(nsplit - 1);
     __syncthreads();
     const int64_t hbase = (int64_t)h * nsplit * QR;
-    if (D == 128 && nsplit > FUSED_MERGE_MAX_SPLITS) {
+    if (!GQA && D == 128 && nsplit > FUSED_MERGE_MAX_SPLITS) {     // (the grouped-query launch never asks for this form)
         // ---- many splits, small grid (host-checked: every workgroup of the launch is resident): RENDEZVOUS merge ----
         // All nsplit workgroups of the head wait for the head's last arrival, then each folds ITS slice of the output —
         // elements e = split, split + nsplit, ... of the sq x D/4 float4 items — 8 threads per element, one per
@@ -707,7 +726,7 @@ __device__ __forceinline__ void attn_split_body(
     if (!s_last) return;
     // nsplit <= FUSED_MERGE_MAX_SPLITS: every load of an output element is issued up front — one memory
     // latency — and each split is its own accumulation chain of attn_combine_kernel
-    for (int e = tid; e < sq * (D / 4); e += 64 * NW) {
+    for (int e = tid; e < rows * (D / 4); e += 64 * NW) {
         const int r = e / (D / 4), d4 = e - r * (D / 4);
         float pm[FUSED_MERGE_MAX_SPLITS], pl[FUSED_MERGE_MAX_SPLITS];
         f32x4 px[FUSED_MERGE_MAX_SPLITS];
@@ -744,7 +763,12 @@ __device__ __forceinline__ void attn_split_body(
         for (int c = 0; c < 4; ++c) o4[c] = (h16)(acc[c] / l);
         // output element (row r, column h * D + 4 d4 ...) in the caller's activation layout (see tf_attn_decode_act):
         // row-major rows of H * D (osm = H * D, osk = 8) or k-octet-major (osm = 8, osk = 8 * R)
-        *reinterpret_cast<half4*>(out + (int64_t)r * osm + (int64_t)((h * D + 4 * d4) >> 3) * osk + ((4 * d4) & 7)) = o4;
+        if constexpr (GQA) {                           // stacked row r -> (token r % sq, query head h * gs + r / sq)
+            const int hq = h * gs + r / sq;
+            *reinterpret_cast<half4*>(out + (int64_t)(r % sq) * osm + (int64_t)((hq * D + 4 * d4) >> 3) * osk + ((4 * d4) & 7)) = o4;
+        } else {
+            *reinterpret_cast<half4*>(out + (int64_t)r * osm + (int64_t)((h * D + 4 * d4) >> 3) * osk + ((4 * d4) & 7)) = o4;
+        }
     }
     if (tid == 0) __hip_atomic_store(&tickets[h], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // left zero for the next launch (graph replays included)
 }
@@ -766,6 +790,17 @@ __global__ __launch_bounds__(256, ATTN_QT2_OCC) void attn_split_q2_kernel(
     float* __restrict__ ws, unsigned* __restrict__ tickets, h16* __restrict__ out, int64_t osm, int64_t osk) {
     attn_split_body<D, 2>(q, k, v, (int64_t)stride_t, (int64_t)stride_h, sq, sk_host, sk_dev, H, scale, nsplit, ws, tickets, out,
                           osm, osk);
+}
+
+// The grouped-query form (tf_attn_decode_gqa_act): grid (nsplit, Hkv * g / gs); H = query heads, g = H / Hkv query heads per
+// KV head, gs of them stacked per workgroup (see attn_split_body).  Bounds as the multi-head kernels of the same q-tile count.
+template <int D, int QT>
+__global__ __launch_bounds__(256, QT == 2 ? ATTN_QT2_OCC : 1) void attn_split_gqa_kernel(
+    const h16* __restrict__ q, const h16* __restrict__ k, const h16* __restrict__ v, const int32_t* __restrict__ sk_dev,
+    int sq, int sk_host, int H, int nsplit, int stride_t, int stride_h, float scale,      // <- 14 dwords preloaded into SGPRs
+    float* __restrict__ ws, unsigned* __restrict__ tickets, h16* __restrict__ out, int64_t osm, int64_t osk, int gs, int g_kv) {
+    attn_split_body<D, QT, false, false, true>(q, k, v, (int64_t)stride_t, (int64_t)stride_h, sq, sk_host, sk_dev, H, scale, nsplit,
+                                               ws, tickets, out, osm, osk, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 0, gs, g_kv);
 }
 
 // The FP8-KV form (tf_attn_decode_fp8_act): k / v are code pointers, ke / ve the exponent bytes.  The one-q-tile form keeps the
@@ -1597,6 +1632,38 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_kernel(
                                       nullptr, 0, 0, 0, split, h, s_begin, min(nslabs, s_begin + sps));
 }
 
+// tf_attn_prefill_gqa: attn_prefill_kernel with query head h reading KV head h / g.  The bodies form a head's K / V base as
+// k + h * stride_h, so they are handed k - (h - h / g) * stride_h: the base they form is KV head h / g of the cache (the
+// intermediate pointer is never dereferenced).  Everything else — grid, split, workspace, merge — is the multi-head launch.
+template <int D>
+__global__ __launch_bounds__(256, 2) void attn_prefill_gqa_kernel(
+    const h16* __restrict__ q, const h16* __restrict__ k, const h16* __restrict__ v, int64_t stride_t,
+    int64_t stride_h, int sq, int sk, int H, float scale, int nsplit, float* __restrict__ ws, int nrb, int rbg, int g) {
+    const int id = blockIdx.x;
+    const int pairs = H * nsplit;                                     // host guarantees pairs % 8 == 0
+    const int xcd = id & 7, j = id >> 3;
+    const int rb_lo = j % rbg, rest = j / rbg;
+    const int pair = (rest % (pairs >> 3)) * 8 + xcd;
+    const int rb = rb_lo + rbg * (rest / (pairs >> 3));
+    if (rb >= nrb) return;
+    const int h = pair / nsplit, split = pair - h * nsplit;
+    const int r0 = rb * 128;
+    const int rows = min(128, sq - r0);
+    const int sk_eff = sk - (sq - (r0 + rows));                        // keys visible to the last row of this block
+    const int nslabs_all = (sk + BLK_SLAB - 1) / BLK_SLAB;
+    const int nslabs = (sk_eff + BLK_SLAB - 1) / BLK_SLAB;
+    const int sps = (nslabs_all + nsplit - 1) / nsplit;
+    const int s_begin = split * sps;
+    float* ws_rb = ws + (int64_t)rb * H * nsplit * 128 * (D + 2);
+    const int64_t back = (int64_t)(h - h / g) * stride_h;
+    if constexpr (BlkLayout<D>::TR)
+        attn_prefill_ahead_body<D>(q + (int64_t)r0 * H * D, k - back, v - back, stride_t, stride_h, rows, sk_eff, H, scale, nsplit,
+                                   ws_rb, split, h, s_begin, min(nslabs, s_begin + sps));
+    else
+        attn_block_lds_body<D, false>(q + (int64_t)r0 * H * D, k - back, v - back, stride_t, stride_h, rows, sk_eff, H, scale,
+                                      nsplit, ws_rb, nullptr, 0, 0, 0, split, h, s_begin, min(nslabs, s_begin + sps));
+}
+
 template <int D>
 static size_t blk_lds_bytes() {
     return (size_t)2 * (BlkLayout<D>::K_HALFS + BlkLayout<D>::V_HALFS) * sizeof(h16);
@@ -1605,10 +1672,11 @@ static size_t blk_lds_bytes() {
 // Merge of the per-split partials.  grid (H, sq), block (D, CG): thread (d, g) folds the splits s == g (mod CG)
 // with independent loads (the first version walked all splits serially per thread: 29 us at nsplit=32 — a
 // dependent-latency chain, 8% on top of the 331 us split kernel); the CG partial sums meet in LDS.
-template <int D>
-__global__ __launch_bounds__(D * COMBINE_GROUPS) void attn_combine_kernel(const float* __restrict__ ws,
-                                                                          h16* __restrict__ out, int sq, int H,
-                                                                          int nsplit, int QR, int64_t osm, int64_t osk) {
+// GQA: grid (columns, stacked rows) of a grouped-query launch — H is the column count, row qq of column h is (token
+// qq % sq, query head h * gs + qq / sq); same arithmetic.
+template <int D, bool GQA>
+__device__ __forceinline__ void attn_combine_body(const float* __restrict__ ws, h16* __restrict__ out, int sq, int H,
+                                                  int nsplit, int QR, int64_t osm, int64_t osk, int gs) {
     __shared__ float sm_w[COMBINE_MAX_SPLITS];
     __shared__ float sm_l[COMBINE_MAX_SPLITS];
     __shared__ float sm_o[COMBINE_GROUPS][D];
@@ -1657,8 +1725,28 @@ __global__ __launch_bounds__(D * COMBINE_GROUPS) void attn_combine_kernel(const 
         float acc = 0.f;
 #pragma unroll
         for (int gg = 0; gg < COMBINE_GROUPS; ++gg) acc += sm_o[gg][d];
-        out[(int64_t)qq * osm + (int64_t)((h * D + d) >> 3) * osk + (d & 7)] = (h16)(acc / l);
+        if constexpr (GQA) {
+            const int hq = h * gs + qq / sq;
+            out[(int64_t)(qq % sq) * osm + (int64_t)((hq * D + d) >> 3) * osk + (d & 7)] = (h16)(acc / l);
+        } else {
+            out[(int64_t)qq * osm + (int64_t)((h * D + d) >> 3) * osk + (d & 7)] = (h16)(acc / l);
+        }
     }
+}
+
+template <int D>
+__global__ __launch_bounds__(D * COMBINE_GROUPS) void attn_combine_kernel(const float* __restrict__ ws,
+                                                                          h16* __restrict__ out, int sq, int H,
+                                                                          int nsplit, int QR, int64_t osm, int64_t osk) {
+    attn_combine_body<D, false>(ws, out, sq, H, nsplit, QR, osm, osk, 1);
+}
+
+template <int D>
+__global__ __launch_bounds__(D * COMBINE_GROUPS) void attn_combine_gqa_kernel(const float* __restrict__ ws,
+                                                                              h16* __restrict__ out, int sq, int cols,
+                                                                              int nsplit, int QR, int64_t osm, int64_t osk,
+                                                                              int gs) {
+    attn_combine_body<D, true>(ws, out, sq, cols, nsplit, QR, osm, osk, gs);
 }
 
 // Merge for many query rows (block attention, > 32 rows): ONE WAVE per (row, head), no LDS, no barrier.  The grid of
@@ -2033,6 +2121,63 @@ extern "C" int tf_attn_decode_act(const void* q, const void* k, const void* v, v
                            ws_floats, tickets, stream);
 }
 
+// ---- grouped-query decode attention: tf_attn_decode_gqa_act ------------------------------------------------------
+// gs = the largest divisor of g = H / Hkv with gs * sq <= 32 (ops.gqa_stack states the same rule): the rows of gs query
+// heads of one KV head are one workgroup column, g / gs columns per KV head.  K / V is therefore read from HBM once per KV
+// head whenever g * sq <= 32, else g / gs times.
+static int gqa_stack(int g, int sq) {
+    int gs = 1;
+    for (int d = 1; d <= g; ++d)
+        if (g % d == 0 && d * sq <= 32) gs = d;
+    return gs;
+}
+
+template <int D, int QT>
+static int launch_attn_gqa(const void* q, const void* k, const void* v, void* out, int64_t osm, int64_t osk, int64_t stride_t,
+                           int64_t stride_h, int sq, int sk, const int32_t* sk_dev, int H, int g, int gs, int cols, float scale,
+                           int nsplit, float* ws, unsigned* tickets, hipStream_t st) {
+    dim3 grid(nsplit, cols), block(256);
+    if (stride_t > 0x7fffffff || stride_h > 0x7fffffff) return TF_EINVAL;   // (the kernel takes the two strides as 32-bit arguments)
+    if (tickets && nsplit > FUSED_MERGE_MAX_SPLITS) tickets = nullptr;      // many splits: the parallel merge kernel
+    hipLaunchKernelGGL((attn_split_gqa_kernel<D, QT>), grid, block, 0, st, (const h16*)q, (const h16*)k, (const h16*)v, sk_dev,
+                       sq, sk, H, nsplit, (int)stride_t, (int)stride_h, scale, ws, tickets, (h16*)out, osm, osk, gs, g);
+    TF_LAUNCH_CHECK();
+    if (tickets) return TF_OK;
+    hipLaunchKernelGGL((attn_combine_gqa_kernel<D>), dim3(cols, gs * sq), dim3(D, COMBINE_GROUPS), 0, st, (const float*)ws,
+                       (h16*)out, sq, cols, nsplit, QT * 16, osm, osk, gs);
+    TF_LAUNCH_CHECK();
+    return TF_OK;
+}
+
+// flash_attn_with_kvcache(q, k, v, softmax_scale, causal=True) with num_key_value_heads < num_heads (the reference's
+// repeat_kv, models/tensor_op.py:8-17; call site models/modeling_llama.py:240): q [sq][H][D], K / V views of Hkv heads,
+// query head h reads KV head h / (H / Hkv).  Output in the activation layout of tf_attn_decode_act.  Workspace and split
+// count: tf_attn_decode_ws_floats(cols, gs * sq, D, nsplit), tf_attn_decode_pick_nsplit(cols, sk), cols = Hkv * g / gs.
+// tickets: cols zeroed words (NULL: two launches); every call leaves them zero.
+extern "C" int tf_attn_decode_gqa_act(const void* q, const void* k, const void* v, void* out, int64_t out_sm, int64_t out_sk,
+                                      int64_t stride_t, int64_t stride_h, int sq, int sk, const int32_t* sk_dev, int H, int Hkv,
+                                      int D, float scale, int nsplit, float* ws, int64_t ws_floats, uint32_t* tickets,
+                                      void* stream) {
+    if (!q || !k || !v || !out || !ws) return TF_EINVAL;
+    if (sq < 1 || sq > 32 || sk < 1 || H < 1 || Hkv < 1 || (H % Hkv) || nsplit < 1 || nsplit > COMBINE_MAX_SPLITS) return TF_EINVAL;
+    if (D != 128 && D != 64) return TF_EINVAL;
+    if ((stride_t % 8) || (stride_h % 8)) return TF_EINVAL;          // 16-B loads
+    if (out_sm < 8 || out_sk < 8 || (out_sm % 4) || (out_sk % 4)) return TF_EINVAL;   // 8-byte output stores
+    const int g = H / Hkv, gs = gqa_stack(g, sq), cols = Hkv * (g / gs), R = gs * sq;
+    if (ws_floats < tf_attn_decode_ws_floats(cols, R, D, nsplit)) return TF_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    const int QT = (R + 15) / 16;
+#define GQA_LAUNCH(D_, QT_)                                                                                                  \
+    return launch_attn_gqa<D_, QT_>(q, k, v, out, out_sm, out_sk, stride_t, stride_h, sq, sk, sk_dev, H, g, gs, cols, scale, nsplit, \
+                                    ws, tickets, st)
+    if (D == 128 && QT == 1) GQA_LAUNCH(128, 1);
+    if (D == 128 && QT == 2) GQA_LAUNCH(128, 2);
+    if (D == 64 && QT == 1) GQA_LAUNCH(64, 1);
+    if (D == 64 && QT == 2) GQA_LAUNCH(64, 2);
+#undef GQA_LAUNCH
+    return TF_EINVAL;
+}
+
 // FP8 KV cache (include/triforce_hip.h): the same split / merge as tf_attn_decode_act (bit-identical to it on the
 // dequantized cache for the same nsplit), K / V read as e4m3fn codes with one exponent byte per (head, key).
 template <int QT>
@@ -2206,6 +2351,47 @@ extern "C" int tf_attn_prefill(const void* q, const void* k, const void* v, void
     if (D == 128) return launch_prefill<128>(q, k, v, out, stride_t, stride_h, sq, sk, H, scale, nsplit, ws, st);
     if (D == 64) return launch_prefill<64>(q, k, v, out, stride_t, stride_h, sq, sk, H, scale, nsplit, ws, st);
     return TF_EINVAL;
+}
+
+template <int D>
+static int launch_prefill_gqa(const void* q, const void* k, const void* v, void* out, int64_t stride_t, int64_t stride_h,
+                              int sq, int sk, int H, int g, float scale, int nsplit, float* ws, hipStream_t st) {
+    static bool attr_set = false;                         // 70 KiB of dynamic LDS: above the 64 KiB default limit
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute((const void*)attn_prefill_gqa_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)blk_lds_bytes<D>());
+        if (e != hipSuccess) return (int)e;
+        attr_set = true;
+    }
+    const int nrb = (sq + 127) / 128, rbg = nrb < 8 ? nrb : 8;
+    const int groups = (nrb + rbg - 1) / rbg;
+    const int64_t blocks = (int64_t)H * nsplit * rbg * groups;
+    hipLaunchKernelGGL((attn_prefill_gqa_kernel<D>), dim3((unsigned)blocks), dim3(256), blk_lds_bytes<D>(), st, (const h16*)q,
+                       (const h16*)k, (const h16*)v, stride_t, stride_h, sq, sk, H, scale, nsplit, ws, nrb, rbg, g);
+    TF_LAUNCH_CHECK();
+    hipLaunchKernelGGL((attn_combine_rows_kernel<D>), dim3((sq * H + 3) / 4), dim3(256), 0, st, (const float*)ws,
+                       (h16*)out, sq, H, nsplit, 128, 128);
+    TF_LAUNCH_CHECK();
+    return TF_OK;
+}
+
+// tf_attn_prefill for grouped-query attention (flash_attn_with_kvcache with num_key_value_heads < num_heads,
+// models/modeling_llama.py:240 on a prefill chunk): 1..4096 query rows, H query heads over Hkv KV heads, query head h reads
+// KV head h / (H / Hkv).  Split count and workspace: tf_attn_prefill_pick_nsplit / tf_attn_prefill_ws_floats with H = the
+// QUERY heads; (H * nsplit) % 8 == 0.
+extern "C" int tf_attn_prefill_gqa(const void* q, const void* k, const void* v, void* out, int64_t stride_t,
+                                   int64_t stride_h, int sq, int sk, int H, int Hkv, int D, float scale, int nsplit, float* ws,
+                                   int64_t ws_floats, void* stream) {
+    if (!q || !k || !v || !out || !ws) return TF_EINVAL;
+    if (sq < 1 || sq > PREFILL_MAX_ROWS || sk < sq || H < 1 || Hkv < 1 || (H % Hkv) || nsplit < 1 || nsplit > COMBINE_MAX_SPLITS)
+        return TF_EINVAL;
+    if ((H * nsplit) % 8) return TF_EINVAL;
+    if ((stride_t % 8) || (stride_h % 8)) return TF_EINVAL;
+    if (D != 128 && D != 64) return TF_EINVAL;
+    if (ws_floats < tf_attn_prefill_ws_floats(H, sq, D, nsplit)) return TF_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    if (D == 128) return launch_prefill_gqa<128>(q, k, v, out, stride_t, stride_h, sq, sk, H, H / Hkv, scale, nsplit, ws, st);
+    return launch_prefill_gqa<64>(q, k, v, out, stride_t, stride_h, sq, sk, H, H / Hkv, scale, nsplit, ws, st);
 }
 
 // Attention of a block of 1..128 query rows against the cache, D = 128 or 64.  mask == NULL: bottom-right causal

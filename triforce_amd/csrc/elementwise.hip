@@ -92,6 +92,45 @@ __global__ void rope_append_kernel(const h16* __restrict__ qkv, int64_t row_stri
     vc[d + half] = vp[d + half];
 }
 
+// rope_append_kernel for grouped-query rows [q: H D | k: Hkv D | v: Hkv D]: grid (rows, H), block D/2 threads; block (row, h)
+// rotates query head h and, for h < Hkv, rotates / copies KV head h into the cache.
+__global__ void rope_append_gqa_kernel(const h16* __restrict__ qkv, int64_t row_stride, const h16* __restrict__ cosb,
+                                       const h16* __restrict__ sinb, const int64_t* __restrict__ positions,
+                                       h16* __restrict__ q_out, h16* __restrict__ k_cache, h16* __restrict__ v_cache,
+                                       int64_t stride_t, int64_t stride_h, int slot0, const int32_t* __restrict__ slot0_dev,
+                                       int H, int Hkv, int D, int rotate_k) {
+    const int row = blockIdx.x, h = blockIdx.y, d = threadIdx.x, half = D >> 1;
+    const int64_t pos = positions[row];
+    const int slot = (slot0_dev ? *slot0_dev : slot0) + row;
+    const h16* base = qkv + (int64_t)row * row_stride;
+    const h16 c1 = cosb[pos * D + d], c2 = cosb[pos * D + d + half];
+    const h16 s1 = sinb[pos * D + d], s2 = sinb[pos * D + d + half];
+    {
+        const h16* qp = base + (int64_t)h * D;
+        const h16 x1 = qp[d], x2 = qp[d + half];
+        h16* qo = q_out + ((int64_t)row * H + h) * D;
+        qo[d] = hadd_rn(hmul_rn(x1, c1), hmul_rn((h16)(-(float)x2), s1));
+        qo[d + half] = hadd_rn(hmul_rn(x2, c2), hmul_rn(x1, s2));
+    }
+    if (h >= Hkv) return;
+    const h16* kp = base + (int64_t)(H + h) * D;
+    const h16* vp = base + (int64_t)(H + Hkv + h) * D;
+    h16* kc = k_cache + (int64_t)slot * stride_t + (int64_t)h * stride_h;
+    h16* vc = v_cache + (int64_t)slot * stride_t + (int64_t)h * stride_h;
+    {
+        const h16 x1 = kp[d], x2 = kp[d + half];
+        if (rotate_k) {
+            kc[d] = hadd_rn(hmul_rn(x1, c1), hmul_rn((h16)(-(float)x2), s1));
+            kc[d + half] = hadd_rn(hmul_rn(x2, c2), hmul_rn(x1, s2));
+        } else {
+            kc[d] = x1;
+            kc[d + half] = x2;
+        }
+    }
+    vc[d] = vp[d];
+    vc[d + half] = vp[d + half];
+}
+
 __global__ __launch_bounds__(256) void silu_mul_kernel(const h16* __restrict__ gu, h16* __restrict__ out, int I,
                                                        int64_t total_vec) {
     const int vpr = I / 8;
@@ -129,6 +168,22 @@ extern "C" int tf_rope_append(const void* qkv, int64_t qkv_row_stride, const voi
     hipLaunchKernelGGL(rope_append_kernel, dim3(rows, H), dim3(D / 2), 0, (hipStream_t)stream, (const h16*)qkv,
                        qkv_row_stride, (const h16*)cosb, (const h16*)sinb, positions, (h16*)q_out, (h16*)k_cache,
                        (h16*)v_cache, stride_t, stride_h, slot0, slot0_dev, H, D, rotate_k);
+    TF_LAUNCH_CHECK();
+    return TF_OK;
+}
+
+// tf_rope_append for grouped-query attention (the un-fused prefill-chunk path): qkv rows [q: H D | k: Hkv D | v: Hkv D],
+// q_out [rows][H][D], k / v rows into the Hkv heads of the cache.  D = 64 or 128.
+extern "C" int tf_rope_append_gqa(const void* qkv, int64_t qkv_row_stride, const void* cosb, const void* sinb,
+                                  const int64_t* positions, void* q_out, void* k_cache, void* v_cache, int64_t stride_t,
+                                  int64_t stride_h, int slot0, const int32_t* slot0_dev, int rows, int H, int Hkv, int D,
+                                  int rotate_k, void* stream) {
+    if (!qkv || !cosb || !sinb || !positions || !q_out || !k_cache || !v_cache) return TF_EINVAL;
+    if (rows < 1 || H < 1 || Hkv < 1 || (H % Hkv) || (D != 64 && D != 128)) return TF_EINVAL;
+    if (H > 65535) return TF_EINVAL;                                     // grid.y
+    hipLaunchKernelGGL(rope_append_gqa_kernel, dim3(rows, H), dim3(D / 2), 0, (hipStream_t)stream, (const h16*)qkv,
+                       qkv_row_stride, (const h16*)cosb, (const h16*)sinb, positions, (h16*)q_out, (h16*)k_cache,
+                       (h16*)v_cache, stride_t, stride_h, slot0, slot0_dev, H, Hkv, D, rotate_k);
     TF_LAUNCH_CHECK();
     return TF_OK;
 }

@@ -161,8 +161,21 @@ struct SgRope {                       // arguments of the RoPE + KV-append epilo
     h16* v_cache;
     int64_t stride_t, stride_h;
     const int32_t* slot0_dev;
+    // SG_QKVG (grouped-query): H = query heads | KV heads << 16 (sg_rope_heads) — packed into the one field so that this
+    // struct, a by-value argument of EVERY skinny GEMM kernel, keeps its size and the multi-head kernels their argument layout
     int slot0, H, D, rotate_k;
 };
+
+// (query heads, KV heads) of the RoPE epilogue: two counts only in the grouped-query mode
+template <int MODE>
+__device__ __forceinline__ void sg_rope_heads(const SgRope& rp, int& H, int& Hkv) {
+    if (MODE == SG_QKVG) {
+        H = rp.H & 0xffff;
+        Hkv = rp.H >> 16;
+    } else {
+        H = Hkv = rp.H;
+    }
+}
 
 // h = w_ln * fp16(x * inv): the cast precedes the weight multiply (modeling_llama.py:141-143); the fp16 product of
 // two fp16 values rounded once is the native half multiply.
@@ -411,9 +424,13 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const half8* __
                 xerr = xc_ld(&xc.ctl->error);
             }
         }
-        if (MODE == SG_QKV && epi) {
-            const int H = rp.H, D = rp.D, pph = D >> 4;
-            const int sec = panel / (H * pph), pp = panel % pph;
+        if ((MODE == SG_QKV || MODE == SG_QKVG) && epi) {
+            const int D = rp.D, pph = D >> 4;
+            int H, Hkv;
+            sg_rope_heads<MODE>(rp, H, Hkv);
+            int sec = panel / (H * pph);
+            if (MODE == SG_QKVG) sec = panel < H * pph ? 0 : (panel < (H + Hkv) * pph ? 1 : 2);
+            const int pp = panel % pph;
             const int d = 8 * pp + 4 * (g & 1) + ((g >= 2) ? (D >> 1) : 0);
 #pragma unroll
             for (int t = 0; t < MT; ++t) {
@@ -689,10 +706,17 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const half8* __
             s[r] = S[t][r];
             s2[r] = S2[t][r];
         }
-        if (MODE == SG_QKV) {
+        if (MODE == SG_QKV || MODE == SG_QKVG) {
             // panel -> (section, head, 8-wide rotary block): q and k panels hold rows d0..d0+7 | d0+D/2..d0+D/2+7
-            const int H = rp.H, D = rp.D, half = D >> 1, pph = D >> 4;
-            const int sec = panel / (H * pph), hd = (panel / pph) % H, pp = panel % pph;
+            const int D = rp.D, half = D >> 1, pph = D >> 4;
+            int H, Hkv;
+            sg_rope_heads<MODE>(rp, H, Hkv);
+            int sec = panel / (H * pph), hd = (panel / pph) % H;
+            if (MODE == SG_QKVG) {                                       // grouped-query: q has H heads, k and v have Hkv
+                sec = panel < H * pph ? 0 : (panel < (H + Hkv) * pph ? 1 : 2);
+                hd = panel / pph - (sec == 0 ? 0 : sec == 1 ? H : H + Hkv);
+            }
+            const int pp = panel % pph;
             h16 val[4], oth[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -1313,6 +1337,41 @@ extern "C" int tf_skinny_qkv_rope_act(const void* wqkv_packed, const void* x, in
     rp.D = D;
     rp.rotate_k = rotate_k;
     return ln_w ? launch_sg<SG_QKV, true>(a, rp, st) : launch_sg<SG_QKV, false>(a, rp, st);
+}
+
+// tf_skinny_qkv_rope_act for grouped-query attention: rows [q: H D | k: Hkv D | v: Hkv D] (N = (H + 2 Hkv) D) in
+// ops.rope_row_order(H, Hkv, D); q_out stays [M][H][D], the k / v rows go to KV head hd of the cache (Hkv heads).
+// Row-major callers pass xs_m = ld, xs_k = 8.
+extern "C" int tf_skinny_qkv_rope_gqa_act(const void* wqkv_packed, const void* x, int64_t xs_m, int64_t xs_k,
+                                          const void* ln_w, float eps, const float* ss_in, const void* cosb,
+                                          const void* sinb, const int64_t* positions, void* q_out, void* k_cache,
+                                          void* v_cache, int64_t stride_t, int64_t stride_h, int slot0,
+                                          const int32_t* slot0_dev, int M, int H, int Hkv, int D, int K, int rotate_k,
+                                          void* stream) {
+    if (!wqkv_packed || !x || !cosb || !sinb || !positions || !q_out || !k_cache || !v_cache) return TF_EINVAL;
+    if (H < 1 || Hkv < 1 || (H % Hkv) || H > 0x7fff || (D != 64 && D != 128)) return TF_EINVAL;
+    SgArgs a = {};
+    a.wp = wqkv_packed, a.x = x, a.ln_w = ln_w;
+    a.xa = SgAct{xs_m, xs_k}, a.ra = SgAct{8, 8}, a.ya = SgAct{8, 8};
+    a.eps = eps, a.M = M, a.N = (H + 2 * Hkv) * D, a.K = K, a.ss_in = ss_in;
+    if (!sg_shape_ok(M, a.N, K, a.xa) || (ss_in && !ln_w)) return TF_EINVAL;
+    if ((stride_t % 4) || (stride_h % 4)) return TF_EINVAL;                          // 8-byte epilogue stores
+    hipStream_t st = (hipStream_t)stream;
+    SgRope rp;
+    rp.cosb = (const h16*)cosb;
+    rp.sinb = (const h16*)sinb;
+    rp.positions = positions;
+    rp.q_out = (h16*)q_out;
+    rp.k_cache = (h16*)k_cache;
+    rp.v_cache = (h16*)v_cache;
+    rp.stride_t = stride_t;
+    rp.stride_h = stride_h;
+    rp.slot0_dev = slot0_dev;
+    rp.slot0 = slot0;
+    rp.H = H | (Hkv << 16);                                                           // (see SgRope)
+    rp.D = D;
+    rp.rotate_k = rotate_k;
+    return ln_w ? launch_sg<SG_QKVG, true>(a, rp, st) : launch_sg<SG_QKVG, false>(a, rp, st);
 }
 
 extern "C" int tf_skinny_qkv_rope(const void* wqkv_packed, const void* x, int64_t ldx, const void* ln_w, float eps,

@@ -3,7 +3,7 @@
 // tests/native/test_sg_rule.cpp can pin the rule on the host with g++; gemv.hip only dispatches what this header returns.
 #pragma once
 
-enum { SG_PLAIN = 0, SG_GATEUP = 1, SG_F32 = 2, SG_QKV = 3 };
+enum { SG_PLAIN = 0, SG_GATEUP = 1, SG_F32 = 2, SG_QKV = 3, SG_QKVG = 4 };   // SG_QKVG: SG_QKV with two head counts (GQA); same launch rule
 
 // Waves per workgroup = K-splits of one 16-row panel.  A wave keeps 4 KiB of weights in flight, so a grid of few panels
 // (o_proj / down_proj: N = 4096 -> 256 workgroups, one per CU) needs more waves per panel to cover the HBM

@@ -157,6 +157,16 @@ SIGNATURES["tf_draft_persist_stamps"] = (_i32, [_vp])
 SIGNATURES["tf_draft_persist_error"] = (_i32, [_vp])
 SIGNATURES["tf_draft_persist_reset"] = (_i32, [_vp, _vp, _i32])
 
+# grouped-query attention (include/triforce_hip.h "GROUPED-QUERY ATTENTION")
+SIGNATURES["tf_attn_decode_gqa_act"] = (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _i32, _i32, _i32,
+                                               _f32, _i32, _vp, _i64, _vp, _vp])
+SIGNATURES["tf_attn_prefill_gqa"] = (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp,
+                                            _i64, _vp])
+SIGNATURES["tf_skinny_qkv_rope_gqa_act"] = (_i32, [_vp, _vp, _i64, _i64, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                                   _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp])
+SIGNATURES["tf_rope_append_gqa"] = (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i32, _i32, _i32,
+                                           _i32, _i32, _vp])
+
 ABI_VERSION = 1
 _lib = None
 

@@ -89,6 +89,11 @@ class Cache:
         raise NotImplementedError("Make sure to implement `update` in a subclass.")
 
 
+def _refuse_gqa(cfg, what):
+    from .config_yarn import refuse_gqa
+    refuse_gqa(cfg, what)
+
+
 def _geom(model):
     cfg = model.config
     heads = cfg.num_key_value_heads
@@ -129,6 +134,7 @@ class FlashSimpleCache(Cache):
         self.device = model.device
         self.scores = []
         if kv_cache_dtype(kv_dtype) == "fp8":
+            _refuse_gqa(model.config, f"{KV_CACHE_ENV}=fp8 (the FP8 KV cache)")
             self._init_fp8()
             return
         self.k, self.v = _alloc(self.layers, self.num_heads, max_budget, self.head_dim, self.device)
@@ -249,6 +255,7 @@ class OffloadingFlashSimpleCache(Cache):
 
     def __init__(self, model, max_budget=1024, tail_capacity=None) -> None:
         _refuse_fp8("OffloadingFlashSimpleCache")
+        _refuse_gqa(model.config, "the offloading cache (OffloadingFlashSimpleCache)")
         self.seq_len = 0
         self.max_budget = max_budget
         self.layers, self.num_heads, self.head_dim = _geom(model)
@@ -358,7 +365,9 @@ class RetrievalCache(Cache):
         self.layers, self.num_heads, self.head_dim = _geom(model)
         self.hidden_size = model.config.hidden_size
         self.device = model.device
+        self.q_heads = model.config.num_attention_heads       # > num_heads: grouped-query, selection per KV head
         if retrieval_kv_dtype(kv_dtype) == "fp8":
+            _refuse_gqa(model.config, f"{RETRIEVAL_KV_ENV}=fp8 (the FP8 retrieval cache)")
             self._init_fp8()
         else:
             self.k, self.v = _alloc(self.layers, self.num_heads, self.real_budget, self.head_dim, self.device)
@@ -452,8 +461,10 @@ class RetrievalCache(Cache):
         return self.real_budget - self.gamma - 1
 
     def init_graph_cache(self, kv_cache, query_states, layer_idx):
-        q = query_states.reshape(-1, self.num_heads, self.head_dim)
+        q = query_states.reshape(-1, self.q_heads, self.head_dim)
         assert 1 == q.shape[0], "query_states should be 1 for init"
+        # grouped-query: one selection per KV head from the group's mean query; multi-head: q itself
+        q = ops.group_mean_query(q[0], self.num_heads).unsqueeze(0)
         if getattr(kv_cache, "fp8", False):           # FP8 cache: score / select / gather over the dequantized prefill rows
             src_k, src_v = kv_cache.scratch_layer(layer_idx, self.prefill)
         else:
@@ -651,6 +662,7 @@ class DistributedSimpleCache(Cache):
 
     def __init__(self, config, max_budget=1024, device=None, on_chip_layers=0, ssl=0):
         _refuse_fp8("DistributedSimpleCache (the tensor-parallel and Sequoia engines)")
+        _refuse_gqa(config, "DistributedSimpleCache (the tensor-parallel, offloading and Sequoia engines)")
         self.config = config
         self.world_size, self.local_rank = config.world_size, config.local_rank
         self.device = torch.device(device)
@@ -750,6 +762,7 @@ class DistributedRetrievalCache:
 
     def __init__(self, config, max_budget=1024, device=None, prefill=1024, chunk_size=8, gamma=6) -> None:
         _refuse_retrieval_fp8("DistributedRetrievalCache (the tensor-parallel and Sequoia engines)")
+        _refuse_gqa(config, "DistributedRetrievalCache (the tensor-parallel and Sequoia engines)")
         self.config = config
         self.world_size, self.local_rank = config.world_size, config.local_rank
         self.device = torch.device(device)

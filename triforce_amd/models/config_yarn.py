@@ -12,6 +12,14 @@ _DEFAULTS = dict(
     rms_norm_eps=1e-6, rope_theta=10000.0, rope_scaling=None, attention_bias=False, pad_token_id=None,
     bos_token_id=1, eos_token_id=2, _name_or_path="",
 )
+GQA_HEAD_DIMS = (64, 128)        # head widths of the grouped-query kernels (tf_attn_decode_gqa_act, tf_attn_prefill_gqa)
+
+
+def refuse_gqa(cfg, what):
+    """ValueError for a grouped-query config in a component that has one head count only."""
+    if cfg.num_key_value_heads != cfg.num_attention_heads:
+        raise ValueError(f"GQA ({cfg.num_attention_heads} query / {cfg.num_key_value_heads} KV heads) is not supported by "
+                         f"{what}: grouped-query attention runs on the single-GPU resident engine with fp16 tiers only")
 
 
 class LlamaConfig:
@@ -30,9 +38,14 @@ class LlamaConfig:
             raise ValueError(f"hidden_act {self.hidden_act!r} is not supported (silu only)")
         if self.attention_bias:
             raise ValueError("attention_bias is not supported")
-        if self.num_key_value_heads != self.num_attention_heads:
-            # the reference's retrieval cache is MHA-only
-            raise ValueError("GQA is not supported: num_key_value_heads must equal num_attention_heads")
+        H, Hkv = self.num_attention_heads, self.num_key_value_heads
+        if not isinstance(Hkv, int) or Hkv < 1 or H % Hkv:
+            raise ValueError(f"GQA: num_attention_heads ({H}) must be a multiple of num_key_value_heads ({Hkv})")
+        if Hkv != H and self.hidden_size // H not in GQA_HEAD_DIMS:
+            # grouped-query attention (the reference's retrieval cache is MHA-only):
+            # the GQA kernels are built for these head widths
+            raise ValueError(f"GQA ({H} query / {Hkv} KV heads) needs head_dim in {GQA_HEAD_DIMS}, got "
+                             f"{self.hidden_size // H}")
         rs = self.rope_scaling
         if rs is not None:
             if not isinstance(rs, dict) or "type" not in rs or "factor" not in rs:
@@ -47,6 +60,11 @@ class LlamaConfig:
     @property
     def head_dim(self):
         return self.hidden_size // self.num_attention_heads
+
+    @property
+    def kv_groups(self):
+        """Query heads per KV head (1: multi-head attention)."""
+        return self.num_attention_heads // self.num_key_value_heads
 
     @classmethod
     def from_dict(cls, d):

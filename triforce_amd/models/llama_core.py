@@ -95,8 +95,13 @@ class LlamaWeights:
         self.L = cfg.num_hidden_layers
         self.H = cfg.num_attention_heads
         self.D = cfg.hidden_size // self.H
+        self.Hkv = cfg.num_key_value_heads                  # < H: grouped-query attention
+        if self.Hkv != self.H and world_size > 1:
+            raise ValueError(f"GQA ({self.H} query / {self.Hkv} KV heads) is not supported by tensor-parallel weight shards "
+                             f"(world_size={world_size})")
         assert self.H % world_size == 0 and cfg.intermediate_size % world_size == 0
         self.H_local = self.H // world_size
+        self.Hkv_local = self.Hkv // world_size if self.Hkv == self.H else self.Hkv
         self.I_local = cfg.intermediate_size // world_size
         self.eps = cfg.rms_norm_eps
         self.embed = self.lm_head = self.norm = None
@@ -114,7 +119,7 @@ class LlamaWeights:
         return w[:, self.rank * n_local:(self.rank + 1) * n_local]
 
     def load_state_dict(self, sd):
-        dev, hd = self.device, self.H_local * self.D
+        dev, hd, kvd = self.device, self.H_local * self.D, self.Hkv_local * self.D
 
         def get(name):
             return sd[name].to(torch.float16)
@@ -125,8 +130,8 @@ class LlamaWeights:
         for i in range(self.L):
             p = f"model.layers.{i}."
             q = self._shard_rows(get(p + "self_attn.q_proj.weight"), hd)
-            k = self._shard_rows(get(p + "self_attn.k_proj.weight"), hd)
-            v = self._shard_rows(get(p + "self_attn.v_proj.weight"), hd)
+            k = self._shard_rows(get(p + "self_attn.k_proj.weight"), kvd)
+            v = self._shard_rows(get(p + "self_attn.v_proj.weight"), kvd)
             self.wqkv.append(torch.cat([q, k, v], dim=0).contiguous().to(dev))
             self.wo.append(self._shard_cols(get(p + "self_attn.o_proj.weight"), hd).contiguous().to(dev))
             g = self._shard_rows(get(p + "mlp.gate_proj.weight"), self.I_local)
@@ -154,7 +159,7 @@ class LlamaWeights:
         self.lm_head = draw("lm_head", cfg.vocab_size, hid)
         self.norm = torch.ones(hid, dtype=torch.float16, device=dev)
         for i in range(self.L):
-            self.wqkv.append(draw(("qkv", i, self.rank), 3 * hd, hid))
+            self.wqkv.append(draw(("qkv", i, self.rank), hd + 2 * self.Hkv_local * self.D, hid))
             self.wo.append(draw(("o", i, self.rank), hid, hd))
             self.wgu.append(draw(("gu", i, self.rank), 2 * self.I_local, hid))
             self.wd.append(draw(("d", i, self.rank), hid, self.I_local))
@@ -192,6 +197,8 @@ class LlamaWeights:
         """Aligned synthetic weights (models/aligned.py): real shapes, dense values, planted successor table so that
         draft / retrieval / full-cache forwards agree to a tunable degree."""
         from . import aligned
+        from .config_yarn import refuse_gqa
+        refuse_gqa(self.cfg, "aligned synthetic weights (models/aligned.py init_aligned)")
         return aligned.init_weights(self, spec, role, attn_keys=attn_keys)
 
     def finalize(self):
@@ -203,7 +210,8 @@ class LlamaWeights:
         self.lm_head = PL(self.lm_head)
         if tied:
             self.embed = self.lm_head.w
-        self.wqkv = [PL(w, rope=(self.H_local, self.D)) for w in self.wqkv]
+        rope = (self.H_local, self.D) if self.Hkv == self.H else (self.H_local, self.Hkv_local, self.D)
+        self.wqkv = [PL(w, rope=rope) for w in self.wqkv]
         self.wo = [PL(w) for w in self.wo]
         self.wgu = [PL(w, split=2) for w in self.wgu]
         self.wd = [PL(w) for w in self.wd]
@@ -214,6 +222,9 @@ class LlamaWeights:
     def build_fp8_(self):
         """FP8 copies (ops.Fp8Linear) of q|k|v, o, gate|up, down and lm_head for the retrieval-cache forward; each is
         re-quantized in place whenever its PackedLinear is refreshed."""
+        if self.Hkv != self.H:
+            raise ValueError(f"GQA ({self.H} query / {self.Hkv} KV heads) is not supported by {RETRIEVAL_WEIGHTS_ENV}=fp8: "
+                             "no grouped-query FP8 q|k|v epilogue exists")
         for pl in [self.lm_head] + self.wqkv + self.wo + self.wgu + self.wd:
             if pl.fp8 is None:
                 pl.fp8 = ops.Fp8Linear(pl)
@@ -245,6 +256,11 @@ class DecoderLayers:
     def __init__(self, W, cos, sin, rotate_k=True):
         self.W, self.cos, self.sin, self.rotate_k = W, cos, sin, rotate_k
 
+    def _kv_heads(self):
+        """The KV head count for the q|k|v ops, passed only by a grouped-query model (the multi-head call is unchanged)."""
+        W = self.W
+        return {} if W.Hkv_local == W.H_local else {"Hkv": W.Hkv_local}
+
     def _capture(self, x):
         """W.capture (a list, while aligned weights are calibrated) receives the final residual stream, before the norm."""
         if self.W.capture is not None:
@@ -256,7 +272,7 @@ class DecoderLayers:
         W = self.W
         w = W.wqkv[i]
         return ops.qkv_rope(x, w.fp8 if f8 else w, W.ln1[i], W.eps, self.cos, self.sin, pos, kl, vl, slot, W.H_local, W.D,
-                            rotate_k=self.rotate_k, slot0_dev=slot_dev, ss_in=ss if i > 0 else None)
+                            rotate_k=self.rotate_k, slot0_dev=slot_dev, ss_in=ss if i > 0 else None, **self._kv_heads())
 
     def o_fused(self, i, a, x, ss, f8=False, out=None):
         w = self.W.wo[i].fp8 if f8 else self.W.wo[i]
@@ -288,7 +304,7 @@ class DecoderLayers:
         else:                                       # x += mlp_out of the previous layer, fused into the norm
             h = ops.rmsnorm(d, W.ln1[i], W.eps, residual=x, sum_out=x)
         return ops.rope_append(ops.linear(h, W.wqkv[i]), self.cos, self.sin, pos, kl, vl, slot, W.H_local, W.D,
-                               rotate_k=self.rotate_k, slot0_dev=slot_dev)
+                               rotate_k=self.rotate_k, slot0_dev=slot_dev, **self._kv_heads())
 
     def o_proj(self, i, a, out=None):
         return ops.linear(a, self.W.wo[i], out=out)

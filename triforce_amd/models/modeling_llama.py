@@ -18,11 +18,27 @@ from .llama_core import (CausalLMOutput, DecoderLayers, LlamaWeights, load_check
                          retrieval_weights, rope_tables_for, softmax_scale_for)
 
 
+def _check_gqa_env():
+    """A grouped-query target runs the fp16 tiers and the one-launch prefill attention only: refuse the rest at construction."""
+    from .cache import kv_cache_dtype, retrieval_kv_dtype, KV_CACHE_ENV, RETRIEVAL_KV_ENV
+    from .llama_core import RETRIEVAL_WEIGHTS_ENV
+    for env, value in ((KV_CACHE_ENV, kv_cache_dtype()), (RETRIEVAL_KV_ENV, retrieval_kv_dtype()),
+                       (RETRIEVAL_WEIGHTS_ENV, retrieval_weights())):
+        if value == "fp8":
+            raise ValueError(f"GQA is not supported with {env}=fp8: the FP8 tiers have no grouped-query kernels")
+    if not ops.ATTN_PREFILL_ONE_LAUNCH:
+        raise ValueError("GQA is not supported with TRIFORCE_PREFILL_ONE_LAUNCH=0: the per-block prefill kernel "
+                         "(tf_attn_block) has one head count")
+
+
 class LlamaForCausalLM:
     def __init__(self, config: LlamaConfig, device="cuda:0"):
         self.config = config
         self.device = torch.device(device)
         self.dtype = torch.float16
+        self.gqa = config.num_key_value_heads != config.num_attention_heads     # grouped-query target (DESIGN section 22)
+        if self.gqa:
+            _check_gqa_env()
         self.weights = LlamaWeights(config, self.device)
         # TRIFORCE_RETRIEVAL_WEIGHTS=fp8: the retrieval-cache (spec) forward streams FP8 copies of its five GEMM weights
         # (DESIGN section 16); every other forward keeps the fp16 weights
@@ -180,7 +196,8 @@ class LlamaForCausalLM:
     def _attention(self, q, kl, vl, sk, codes, sk_dev, packed, decode):
         """``codes``: the FP8 cache's own kernel (decode-sized blocks only).  ``decode``: the retrieval-cache forward and the
         captured forward, split-KV decode kernel whatever the layout; an eager full-cache block takes it only with k-octet-major
-        rows and is a prefill block otherwise."""
+        rows and is a prefill block otherwise.  A grouped-query target (q has more heads than the cache views) takes the GQA
+        kernels through the same two calls: ops.attn_decode / ops.attn_prefill dispatch on the head counts."""
         if codes:
             return ops.attn_decode_fp8(q, *codes, sk, self.scale, sk_dev=sk_dev, packed=packed)
         if decode or packed:

@@ -29,6 +29,17 @@ CONFIGS = {
                  max_position_embeddings=131072, rms_norm_eps=1e-6,
                  rope_scaling=dict(type="yarn", factor=16.0, original_max_position_embeddings=256),
                  _name_or_path="tiny-yarn-target"),
+    # the tiny target with grouped-query attention: 4 query heads over 2 KV heads, D = 128
+    "tiny-gqa": dict(hidden_size=512, intermediate_size=768, num_hidden_layers=2, num_attention_heads=4,
+                     num_key_value_heads=2, max_position_embeddings=131072, rms_norm_eps=1e-6,
+                     rope_scaling=dict(type="yarn", factor=16.0, original_max_position_embeddings=256),
+                     _name_or_path="tiny-yarn-gqa-target"),
+    # NousResearch/Yarn-Llama-2-70b-32k (grouped-query, 64 / 8 heads).  Written from memory of the model card: there is
+    # no hub access offline, so these values are NOT checked against the published config.json
+    "llama-70B-32K": dict(hidden_size=8192, intermediate_size=28672, num_hidden_layers=80, num_attention_heads=64,
+                          num_key_value_heads=8, max_position_embeddings=32768, rms_norm_eps=1e-5,
+                          rope_scaling=dict(type="yarn", factor=8.0, original_max_position_embeddings=4096),
+                          _name_or_path="NousResearch/Yarn-Llama-2-70b-32k"),
 }
 
 

@@ -71,15 +71,35 @@ def pack_weight(w):
     return w.view(N // 16, 16, K // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous()
 
 
-def rope_row_order(H, D, device=None):
+def rope_row_order(H, Hkv, D, device=None):
     """Row permutation of a fused [q | k | v] weight for the RoPE epilogue of tf_skinny_qkv_rope: every 16-row panel
     of the q and k sections holds rows d0..d0+7 and their rotary partners d0+D/2..d0+D/2+7 of one head; v rows keep
-    their order."""
+    their order.  The q section has H heads, the k and v sections Hkv (= H: multi-head attention; < H: grouped-query
+    weights, tf_skinny_qkv_rope_gqa_act)."""
     assert D % 32 == 0
     d = torch.arange(D // 2, device=device).view(D // 16, 8)
     per_head = torch.cat([d, d + D // 2], dim=1).reshape(-1)                     # (D,)
-    qk = (torch.arange(2 * H, device=device).view(-1, 1) * D + per_head.view(1, -1)).reshape(-1)
-    return torch.cat([qk, torch.arange(2 * H * D, 3 * H * D, device=device)])
+    qk = (torch.arange(H + Hkv, device=device).view(-1, 1) * D + per_head.view(1, -1)).reshape(-1)
+    return torch.cat([qk, torch.arange((H + Hkv) * D, (H + 2 * Hkv) * D, device=device)])
+
+
+def gqa_stack(g, sq):
+    """Row-stacking rule of the grouped-query decode attention (tf_attn_decode_gqa_act): the sq rows of gs query heads of one
+    KV head share a workgroup column, gs = the largest divisor of the group size g with gs * sq <= 32; returns
+    (gs, g // gs = sub-groups per KV head)."""
+    assert g >= 1 and 1 <= sq <= SKINNY_MAX_ROWS
+    gs = max(d for d in range(1, g + 1) if g % d == 0 and d * sq <= SKINNY_MAX_ROWS)
+    return gs, g // gs
+
+
+def group_mean_query(q, Hkv):
+    """q̄ of the grouped-query retrieval selection: q (H, D) fp16 -> (Hkv, D) fp16, the fp32 mean over
+    the H / Hkv query heads of each KV head rounded to fp16.  H == Hkv: q itself, bit for bit."""
+    H, D = q.shape
+    if H == Hkv:
+        return q
+    assert H % Hkv == 0
+    return q.view(Hkv, H // Hkv, D).float().mean(dim=1).to(q.dtype)
 
 
 # ---- narrow panels (round 5; csrc/gemv.hip skinny_gemm_n8_kernel) ----------------------------------------------------
@@ -142,11 +162,24 @@ def _ensure_sg_workspace(device):
     _SG_WS[device] = ws
 
 
+def _rope3(rope):
+    """(H, Hkv, D) of a PackedLinear ``rope`` mark: (H, D) or (H, Hkv, D)."""
+    return (rope[0], rope[0], rope[1]) if len(rope) == 2 else tuple(rope)
+
+
+def _rope_rows(rope):
+    H, Hkv, D = _rope3(rope)
+    return (H + 2 * Hkv) * D
+
+
 class PackedLinear:
     """A weight matrix with (on a HIP device) its pre-packed copy for the skinny decode GEMM.  ``w`` stays
     available for the >32-row prefill GEMMs (hipBLASLt).  ``split`` = number of equal row blocks that were
     fused (2 for gate|up) — each block is packed on its own so the SwiGLU kernel can pair them.  ``rope=(H, D)``
-    marks a fused q|k|v weight: a second packed copy in rotary-pair row order feeds tf_skinny_qkv_rope."""
+    marks a fused q|k|v weight: a second packed copy in rotary-pair row order feeds tf_skinny_qkv_rope.
+    ``rope=(H, Hkv, D)`` with Hkv < H marks a grouped-query weight ([q: H D | k: Hkv D | v: Hkv D] rows): its rotary copy
+    feeds tf_skinny_qkv_rope_gqa_act, and it gets neither the 8-row-panel copy nor an FP8 copy (no GQA epilogue exists
+    for either)."""
 
     def __init__(self, w, split=1, pack=None, rope=None):
         self.w = w
@@ -160,13 +193,16 @@ class PackedLinear:
         self.wp = self.parts[0] if (ok and split == 1) else None
         self.rope = rope
         self.wp_rope = None
-        if ok and rope is not None and rope[1] % 32 == 0 and self.N == 3 * rope[0] * rope[1]:
-            self.wp_rope = pack_weight(w[rope_row_order(rope[0], rope[1], w.device)])
+        self.gqa = rope is not None and len(rope) == 3 and rope[1] != rope[0]
+        if rope is not None and len(rope) == 3 and not self.gqa:
+            self.rope = rope = (rope[0], rope[2])                 # equal head counts: the multi-head spelling
+        if ok and rope is not None and rope[-1] % 32 == 0 and self.N == _rope_rows(rope):
+            self.wp_rope = pack_weight(w[rope_row_order(*_rope3(rope), w.device)])
         # narrow-panel copies (few-panel shards only): gate|up streams, and the q|k|v weight in its 8-row rotary order
         self.parts_n8 = self.wp_rope_n8 = None
         if ok and w.is_cuda and split == 2 and n8_applies(self.N // split, self.K):
             self.parts_n8 = [pack_weight_n8(b) for b in w.chunk(split, dim=0)]
-        if self.wp_rope is not None and w.is_cuda and n8_applies(self.N, self.K):
+        if self.wp_rope is not None and not self.gqa and w.is_cuda and n8_applies(self.N, self.K):
             self.wp_rope_n8 = pack_weight_n8(w[rope_row_order_n8(rope[0], rope[1], w.device)])
         self.fp8 = None           # Fp8Linear of the retrieval-verify tier (models/llama_core.LlamaWeights.build_fp8_)
 
@@ -176,7 +212,7 @@ class PackedLinear:
             for dst, blk in zip(self.parts, self.w.chunk(self.split, dim=0)):
                 dst.copy_(pack_weight(blk))
         if self.wp_rope is not None:
-            self.wp_rope.copy_(pack_weight(self.w[rope_row_order(self.rope[0], self.rope[1], self.w.device)]))
+            self.wp_rope.copy_(pack_weight(self.w[rope_row_order(*_rope3(self.rope), self.w.device)]))
         if self.parts_n8 is not None:
             for dst, blk in zip(self.parts_n8, self.w.chunk(self.split, dim=0)):
                 dst.copy_(pack_weight_n8(blk))
@@ -232,6 +268,9 @@ class Fp8Linear:
     def __init__(self, pl):
         assert isinstance(pl, PackedLinear)
         self.src, self.N, self.K, self.split, self.rope = pl, pl.N, pl.K, pl.split, pl.rope
+        if getattr(pl, "gqa", False):
+            raise ValueError(f"GQA q|k|v weight (H, Hkv, D = {pl.rope}) is not supported by the FP8 weight tier (Fp8Linear): "
+                             "no grouped-query FP8 epilogue exists")
         if not pl.w.is_cuda:
             raise hip.TriforceHipError("FP8 weights need a HIP device tensor (no CPU fallback)")
         if self.K % 64 or (self.N // self.split) % 16 or self.N % self.split:
@@ -247,7 +286,7 @@ class Fp8Linear:
     def _streams(self):
         w = self.src.w
         if self.rope is not None:
-            return [w[rope_row_order(self.rope[0], self.rope[1], w.device)]]
+            return [w[rope_row_order(self.rope[0], self.rope[0], self.rope[1], w.device)]]
         return list(w.chunk(self.split, dim=0))
 
     def refresh_(self):
@@ -264,7 +303,7 @@ class Fp8Linear:
         w = torch.cat(rows, dim=0)
         if self.rope is not None:
             out = torch.empty_like(w)
-            out[rope_row_order(self.rope[0], self.rope[1], w.device)] = w
+            out[rope_row_order(self.rope[0], self.rope[0], self.rope[1], w.device)] = w
             return out
         return w
 
@@ -527,15 +566,18 @@ def ss_buffer(hidden, device):
 
 
 def qkv_rope(x, wqkv, ln, eps, cos, sin, positions, k_layer, v_layer, slot0, H, D, rotate_k=True, slot0_dev=None,
-             ss_in=None):
+             ss_in=None, Hkv=None):
     """One kernel for [RMSNorm ->] fused q|k|v GEMM -> RoPE -> KV append: x (rows, hidden) is the residual stream
     (ln = input_layernorm weight, or None when x is already normalised; a row-major tensor or an Act); q (rows,H,D)
-    is returned rotated, the k (rotated unless rotate_k is False) and v rows land in the cache at slot0+i."""
+    is returned rotated, the k (rotated unless rotate_k is False) and v rows land in the cache at slot0+i.
+    ``Hkv`` < H: a grouped-query weight (PackedLinear rope=(H, Hkv, D)), k / v rows go to the Hkv heads of the cache."""
     _dev(ln, cos, sin, positions, k_layer, v_layer, slot0_dev)
+    gqa = Hkv is not None and Hkv != H
     f8 = isinstance(wqkv, Fp8Linear)
     if f8:
         _fp8_rows_ok(x, wqkv)
-    assert (f8 or (isinstance(wqkv, PackedLinear) and wqkv.wp_rope is not None)) and wqkv.rope == (H, D)
+    assert f8 or (isinstance(wqkv, PackedLinear) and wqkv.wp_rope is not None)
+    assert wqkv.rope == ((H, Hkv, D) if gqa else (H, D))
     rows = x.shape[0]
     assert x.is_cuda and x.dtype == _HALF and x.shape[1] == wqkv.K and rows <= SKINNY_MAX_ROWS
     assert positions.dtype == torch.int64 and positions.numel() == rows and positions.is_contiguous()
@@ -544,6 +586,13 @@ def qkv_rope(x, wqkv, ln, eps, cos, sin, positions, k_layer, v_layer, slot0, H, 
     assert _kv(v_layer) == (st, sh)
     q = torch.empty(rows, H, D, dtype=_HALF, device=x.device)
     xp, xsm, xsk = _lay(x)
+    if gqa:
+        assert not f8 and k_layer.shape[0] == Hkv and v_layer.shape[0] == Hkv and H % Hkv == 0
+        hip.check(hip.lib().tf_skinny_qkv_rope_gqa_act(_ptr(wqkv.wp_rope), xp, xsm, xsk, _ptr(ln), float(eps), _ptr(ss_in),
+                                                       _ptr(cos), _ptr(sin), _ptr(positions), _ptr(q), _ptr(k_layer),
+                                                       _ptr(v_layer), st, sh, int(slot0), _ptr(slot0_dev), rows, H, Hkv, D,
+                                                       wqkv.K, 1 if rotate_k else 0, _stream()), "tf_skinny_qkv_rope_gqa_act")
+        return q
     if f8:
         hip.check(hip.lib().tf_skinny_qkv_rope_fp8_act(_ptr(wqkv.codes[0]), _ptr(wqkv.scales[0]), xp, xsm, xsk, _ptr(ln),
                                                        float(eps), _ptr(ss_in), _ptr(cos), _ptr(sin), _ptr(positions), _ptr(q),
@@ -574,10 +623,22 @@ def rmsnorm(x, w, eps, residual=None, sum_out=None):
     return y
 
 
-def rope_append(qkv, cos, sin, positions, k_layer, v_layer, slot0, H, D, rotate_k=True, slot0_dev=None):
-    """Split fused qkv rows, rotate q (and k), append k/v rows to the cache at slot0+i.  Returns q (rows,H,D)."""
+def rope_append(qkv, cos, sin, positions, k_layer, v_layer, slot0, H, D, rotate_k=True, slot0_dev=None, Hkv=None):
+    """Split fused qkv rows, rotate q (and k), append k/v rows to the cache at slot0+i.  Returns q (rows,H,D).
+    ``Hkv`` < H: grouped-query rows [q: H D | k: Hkv D | v: Hkv D] (tf_rope_append_gqa)."""
     _dev(qkv, cos, sin, positions, k_layer, v_layer)
     rows = qkv.shape[0]
+    if Hkv is not None and Hkv != H:
+        assert qkv.dtype == _HALF and qkv.stride(1) == 1 and qkv.shape[1] == (H + 2 * Hkv) * D and H % Hkv == 0
+        assert positions.dtype == torch.int64 and positions.numel() == rows and positions.is_contiguous()
+        assert cos.dtype == _HALF and cos.is_contiguous() and cos.shape[1] == D
+        st, sh = _kv(k_layer)
+        assert _kv(v_layer) == (st, sh) and k_layer.shape[0] == Hkv and v_layer.shape[0] == Hkv
+        q = torch.empty(rows, H, D, dtype=_HALF, device=qkv.device)
+        hip.check(hip.lib().tf_rope_append_gqa(_ptr(qkv), qkv.stride(0), _ptr(cos), _ptr(sin), _ptr(positions), _ptr(q),
+                                               _ptr(k_layer), _ptr(v_layer), st, sh, int(slot0), _ptr(slot0_dev), rows, H, Hkv,
+                                               D, 1 if rotate_k else 0, _stream()), "tf_rope_append_gqa")
+        return q
     assert qkv.dtype == _HALF and qkv.stride(1) == 1 and qkv.shape[1] == 3 * H * D
     assert positions.dtype == torch.int64 and positions.numel() == rows and positions.is_contiguous()
     assert cos.dtype == _HALF and cos.is_contiguous() and cos.shape[1] == D
@@ -657,6 +718,8 @@ def attn_decode(q, k_layer, v_layer, sk, scale, sk_dev=None, nsplit=None, packed
     q (sq,H,D); returns (sq, H*D) fp16 — a row-major tensor, or with ``packed`` an Act (what o_proj then reads)."""
     _dev(q, k_layer, v_layer, sk_dev)
     sq, H, D = q.shape
+    if k_layer.shape[0] != H:                          # fewer KV heads than query heads: the grouped-query kernel
+        return attn_decode_gqa(q, k_layer, v_layer, sk, scale, sk_dev=sk_dev, nsplit=nsplit, packed=packed)
     assert q.dtype == _HALF and q.is_contiguous()
     st, sh = _kv(k_layer)
     assert _kv(v_layer) == (st, sh)
@@ -682,6 +745,38 @@ def attn_decode(q, k_layer, v_layer, sk, scale, sk_dev=None, nsplit=None, packed
     if timed:
         ev1.record()
         ATTN_TIMER.append((ev0, ev1, int(sk), H, D))
+    return out
+
+
+def attn_decode_gqa(q, k_layer, v_layer, sk, scale, sk_dev=None, nsplit=None, packed=False, fused_merge=None, out=None):
+    """attn_decode for grouped-query attention: q (sq, H, D) against KV views of Hkv = H / g heads, query
+    head h reading KV head h // g.  The sq rows of gs query heads of one KV head are stacked into one gs * sq <= 32 row
+    problem (gqa_stack), so K / V is streamed once per KV head whenever g * sq <= 32.  ``fused_merge``: None = the module
+    default, True / False = the one- / two-launch form (bit-identical).  ``out``: write into this (sq, H * D) row-major
+    tensor or Act instead of a fresh one.  Not timed into ATTN_TIMER."""
+    _dev(q, k_layer, v_layer, sk_dev)
+    sq, H, D = q.shape
+    Hkv = k_layer.shape[0]
+    assert q.dtype == _HALF and q.is_contiguous() and v_layer.shape[0] == Hkv
+    if Hkv < 1 or H % Hkv or sq > SKINNY_MAX_ROWS:
+        raise hip.TriforceHipError(f"attn_decode_gqa: {H} query heads over {Hkv} KV heads, {sq} rows")
+    st, sh = _kv(k_layer)
+    assert _kv(v_layer) == (st, sh)
+    gs, sub = gqa_stack(H // Hkv, sq)
+    cols = Hkv * sub                                   # workgroup columns = (KV head, sub-group) pairs
+    if nsplit is None:
+        nsplit = _pick_nsplit(cols, int(sk))
+    ws = _workspace(q.device, _ws_floats(cols, gs * sq, D, nsplit))
+    if out is None:
+        out = Act.empty(sq, H * D, q.device) if packed else torch.empty(sq, H * D, dtype=_HALF, device=q.device)
+    assert tuple(out.shape) == (sq, H * D)
+    op, osm, osk = _lay(out)
+    stream = _stream()
+    fused = ATTN_FUSED_MERGE if fused_merge is None else fused_merge
+    tickets = _ticket_row(q.device, stream.value or 0) if fused and cols <= _TICKET_WORDS else None
+    hip.check(hip.lib().tf_attn_decode_gqa_act(_ptr(q), _ptr(k_layer), _ptr(v_layer), op, osm, osk, st, sh, sq, int(sk),
+                                               _ptr(sk_dev), H, Hkv, D, float(scale), nsplit, _ptr(ws), ws.numel(),
+                                               _ptr(tickets), stream), "tf_attn_decode_gqa_act")
     return out
 
 
@@ -970,6 +1065,8 @@ def attn_prefill(q, k_layer, v_layer, sk, scale):
     sq = q.shape[0]
     if sq <= 32:
         return attn_decode(q, k_layer, v_layer, sk, scale)
+    if k_layer.shape[0] != q.shape[1]:                 # grouped-query: every block above 32 rows, 33..128 included
+        return attn_prefill_gqa(q, k_layer, v_layer, sk, scale)
     if sq <= 128:
         return attn_block(q, k_layer, v_layer, sk, scale)
     if not ATTN_PREFILL_ONE_LAUNCH or sq > 4096:
@@ -989,6 +1086,35 @@ def attn_prefill(q, k_layer, v_layer, sk, scale):
     out = torch.empty(sq, H * D, dtype=_HALF, device=q.device)
     hip.check(L.tf_attn_prefill(_ptr(q), _ptr(k_layer), _ptr(v_layer), _ptr(out), st, sh, sq, int(sk), H, D, float(scale),
                                 nsplit, _ptr(ws), ws.numel(), _stream()), "tf_attn_prefill")
+    return out
+
+
+def attn_prefill_gqa(q, k_layer, v_layer, sk, scale):
+    """Causal attention of a prefill block of 33..4096 rows for grouped-query attention (tf_attn_prefill_gqa): tf_attn_prefill
+    with query head h reading KV head h // g.  Longer blocks are cut into 4096-row pieces."""
+    _dev(q, k_layer, v_layer)
+    sq, H, D = q.shape
+    Hkv = k_layer.shape[0]
+    if not ATTN_PREFILL_ONE_LAUNCH:
+        raise ValueError("TRIFORCE_PREFILL_ONE_LAUNCH=0 is not supported with a GQA model: the per-block kernel "
+                         "(tf_attn_block) has one head count")
+    if Hkv < 1 or H % Hkv:
+        raise hip.TriforceHipError(f"attn_prefill_gqa: {H} query heads over {Hkv} KV heads")
+    if sq > 4096:
+        outs = []
+        for r0 in range(0, sq, 4096):
+            r1 = min(sq, r0 + 4096)
+            outs.append(attn_prefill_gqa(q[r0:r1].contiguous(), k_layer, v_layer, sk - (sq - r1), scale))
+        return torch.cat(outs, dim=0)
+    assert q.dtype == _HALF and q.is_contiguous() and v_layer.shape[0] == Hkv
+    st, sh = _kv(k_layer)
+    assert _kv(v_layer) == (st, sh)
+    L = hip.lib()
+    nsplit = L.tf_attn_prefill_pick_nsplit(H, sq, int(sk))
+    ws = _workspace(q.device, L.tf_attn_prefill_ws_floats(H, sq, D, nsplit))
+    out = torch.empty(sq, H * D, dtype=_HALF, device=q.device)
+    hip.check(L.tf_attn_prefill_gqa(_ptr(q), _ptr(k_layer), _ptr(v_layer), _ptr(out), st, sh, sq, int(sk), H, Hkv, D,
+                                    float(scale), nsplit, _ptr(ws), ws.numel(), _stream()), "tf_attn_prefill_gqa")
     return out
 
 
