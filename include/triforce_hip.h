@@ -741,6 +741,27 @@ int tf_rope_append_gqa(const void* qkv, int64_t qkv_row_stride, const void* cos,
                        int64_t stride_t, int64_t stride_h, int slot0, const int32_t* slot0_dev,
                        int rows, int H, int Hkv, int D, int rotate_k, void* stream);
 
+/* -------------------------------------------------------------------------------------------
+ * PER-TOKEN LOG-PROBABILITIES.  For fp32 logits rows x[r] (row r at logits + r * row_stride,
+ * row_stride >= V elements) and a target id per row:
+ *   logprob[r] = x[r][t] - max_i x[r][i] - log sum_i exp(x[r][i] - max_i x[r][i]),   lse[r] = max + log sum
+ * — the log-probability at temperature 1 with no top-k / top-p filter.  fp32 throughout, one workgroup per row, the row is
+ * streamed in one pass (any V >= 1, any rows >= 1; no 32768 limit), 16-byte loads between the row's first and last 16-byte
+ * boundary whatever base and stride are, a fixed summation order.  -inf entries are legal and carry mass 0; a -inf target
+ * gives -inf; NaN entries and a row of -inf alone are outside the contract.  A target outside [0, V) means "no target":
+ * logprob[r] = 0 and nothing is read for it.
+ * tf_token_logprobs: targets is a DEVICE array of `rows` ids and may be NULL when only lse is wanted; lse may be NULL; at
+ *   least one of (targets and logprob) or lse must be given.
+ * tf_token_logprobs_ids: the ids (host memory, rows <= 32) travel as kernel arguments like tf_set_tokens' — the decode step
+ *   knows them on the host and needs no upload; logprob is required, lse may be NULL.
+ * TF_EINVAL before any launch: NULL logits, rows < 1, V < 1, row_stride < V, the output rule above (and rows > 32, NULL
+ * host_ids / logprob for the _ids form).
+ * ------------------------------------------------------------------------------------------- */
+int tf_token_logprobs(const float* logits, int64_t row_stride, const int64_t* targets, int rows, int V, float* logprob,
+                      float* lse, void* stream);
+int tf_token_logprobs_ids(const float* logits, int64_t row_stride, const int64_t* host_ids, int rows, int V,
+                          float* logprob, float* lse, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

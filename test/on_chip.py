@@ -45,17 +45,35 @@ def followups(args, tokenizer, engine, prompt, vocab_size, sampling):
     if args.followup_len < 1:
         raise SystemExit("--followups needs --followup_len >= 1")
     session = TriForceSession(tokenizer, engine, args.gamma, verbose=args.verbose, rebuild_every=args.rebuild_every,
-                              reanchor_at=args.reanchor_at, **sampling)
+                              reanchor_at=args.reanchor_at, logprobs=args.logprobs, **sampling)
     session.prefill(prompt)
     first = session.generate(args.gen_len)
     print(colored(f"[Session] prefill {prompt.shape[1]} tokens: time to first token {first['ttft']:.3f} s, "
                   f"{first['tokens_per_s']:.2f} tokens/s", "red"))
+    if args.logprobs:
+        print(colored(f"[Session] generation: mean log-probability {cli.mean(first['logprobs']):.4f}", "red"))
     gen = torch.Generator().manual_seed(0)
     for i in range(args.followups):
         question = torch.randint(3, vocab_size, (1, args.followup_len), generator=gen).to(prompt.device)
         st = session.ask(question, args.gen_len, keep=args.prefill)
         print(colored(f"[Session] follow-up {i + 1}/{args.followups} ({args.followup_len} tokens, keep {args.prefill}): "
                       f"time to first token {st['ttft']:.3f} s, {st['tokens_per_s']:.2f} tokens/s", "red"))
+        if args.logprobs:
+            print(colored(f"[Session] follow-up {i + 1}/{args.followups}: mean log-probability of the answer "
+                          f"{cli.mean(st['logprobs']):.4f} over {len(st['logprobs'])} tokens", "red"))
+
+
+def report_logprobs(tokenizer, engine, prompts, run):
+    """--logprobs: one more TriForce run per prompt that scores the prompt during its prefill and every emitted token
+    (DESIGN section 23), outside the timed runs above."""
+    import math
+    for i, p in enumerate(prompts):
+        st = TriForce(tokenizer, engine, p, return_details=True, logprobs=True, prompt_logprobs=True, **run)
+        nll = -float(st["prompt_logprobs"].double().mean())
+        print(colored(f"[Logprobs] prompt {i + 1}/{len(prompts)} ({p.shape[1]} tokens): mean negative log-likelihood {nll:.4f}, "
+                      f"perplexity {math.exp(nll):.3f}", "red"))
+        print(colored(f"[Logprobs] generation: mean log-probability {cli.mean(st['logprobs']):.4f} over "
+                      f"{len(st['logprobs'])} tokens", "red"))
 
 
 def main():
@@ -88,6 +106,8 @@ def main():
     for _ in range(3):
         TriForce(tokenizer, engine, clip(prompts[0]), **run)
     results = [TriForce(tokenizer, engine, clip(p), file_path=args.file, **run) for p in prompts]
+    if args.logprobs:
+        report_logprobs(tokenizer, engine, [clip(p) for p in prompts], run)
     method_latency = 1000 / cli.mean([speed for _, speed in results])
     print(colored(f"average acceptance rate (NOT per token): {cli.mean([acc for acc, _ in results])}", "red"))
     print(colored(f"[TriForce] average latency: {method_latency} ms", "red"))

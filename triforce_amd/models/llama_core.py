@@ -291,10 +291,13 @@ class DecoderLayers:
             return ops.linear(act, w, resid=x, out=x, ss_out=ss)                # x += mlp_out
         return ops.linear(act, w, out=out)
 
-    def head_fused(self, x, ss, f8=False):
+    def head_fused(self, x, ss, f8=False, next_ids=None, logprobs_out=None):
         W = self.W
         self._capture(x)
-        return ops.linear(x, W.lm_head.fp8 if f8 else W.lm_head, out_f32=True, ln=W.norm, eps=W.eps, ss_in=ss).unsqueeze(0)
+        logits = ops.linear(x, W.lm_head.fp8 if f8 else W.lm_head, out_f32=True, ln=W.norm, eps=W.eps, ss_in=ss)
+        if next_ids is not None:                    # (a prompt chunk of <= 32 rows: every row's logits exist already)
+            ops.token_logprobs(logits, next_ids, out=logprobs_out)
+        return logits.unsqueeze(0)
 
     # -- un-fused ------------------------------------------------------------------------------
     def qkv(self, i, x, d, pos, kl, vl, slot, slot_dev=None):
@@ -315,11 +318,19 @@ class DecoderLayers:
         h = ops.rmsnorm(o, W.ln2[i], W.eps, residual=x, sum_out=x)
         return ops.linear(ops.mlp_act(h, W.wgu[i]), W.wd[i], out=out)
 
-    def head(self, x, d, last_rows=None):
-        """last_rows = k: logits of the trailing k rows only (chunked prefill)."""
+    def head(self, x, d, last_rows=None, next_ids=None, logprobs_out=None):
+        """last_rows = k: logits of the trailing k rows only (chunked prefill).
+        next_ids (rows,) int64 + logprobs_out (rows,) fp32: logprobs_out[i] = log-probability of next_ids[i] under row i
+        (DESIGN section 23).  The rows go through the lm_head in blocks of ops.SCORE_BLOCK_ROWS, each block's fp32 logits
+        are scored by ops.token_logprobs and dropped: no (chunk, V) logits block exists.  The returned logits are unchanged."""
         W = self.W
         h = ops.rmsnorm(d, W.norm, W.eps, residual=x, sum_out=x)
         self._capture(x)
+        if next_ids is not None:
+            assert next_ids.numel() == h.shape[0] == logprobs_out.numel()
+            for r0 in range(0, h.shape[0], ops.SCORE_BLOCK_ROWS):
+                r1 = min(h.shape[0], r0 + ops.SCORE_BLOCK_ROWS)
+                ops.token_logprobs(ops.linear(h[r0:r1], W.lm_head, out_f32=True), next_ids[r0:r1], out=logprobs_out[r0:r1])
         if last_rows is not None and last_rows < h.shape[0]:
             h = h[-last_rows:]
         return ops.linear(h, W.lm_head, out_f32=True).unsqueeze(0)           # (1, q, V) fp32

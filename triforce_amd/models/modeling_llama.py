@@ -93,8 +93,11 @@ class LlamaForCausalLM:
         return self.forward(input_ids, kv_cache, graph_cache, position_ids, spec, rebuild_retrieval, dev_len)
 
     def forward(self, input_ids, kv_cache, graph_cache=None, position_ids=None, spec=False, rebuild_retrieval=False,
-                dev_len=None, last_rows=None):
+                dev_len=None, last_rows=None, next_ids=None, logprobs_out=None):
         """last_rows = k: logits of the trailing k rows only (chunked prefill: utils/graph_infer.py chunked_prefill).
+        next_ids (q_len,) int64 + logprobs_out (q_len,) fp32 device tensors: logprobs_out[i] receives the log-probability
+        (temperature 1, unfiltered) of next_ids[i] under row i — the prompt's log-probabilities; the
+        logits returned are unchanged.
         dev_len = (slot_dev, sk_dev) int32 device scalars: the hipGraph-capturable form of the full-cache decode
         forward — the append slot and the key count are read from device memory by the kernels (tf_skinny_qkv_rope
         slot0_dev, tf_attn_decode sk_dev), position_ids must be given, the launch is sized by the cache capacity and
@@ -170,7 +173,10 @@ class LlamaForCausalLM:
                 d = layers.mlp(i, x, layers.o_proj(i, a))
         if streaming:
             kv_cache.end_forward()
-        return CausalLMOutput(layers.head_fused(x, ss, f8) if fused else layers.head(x, d, last_rows))
+        if next_ids is None:
+            return CausalLMOutput(layers.head_fused(x, ss, f8) if fused else layers.head(x, d, last_rows))
+        score = dict(next_ids=next_ids.reshape(-1), logprobs_out=logprobs_out)
+        return CausalLMOutput(layers.head_fused(x, ss, f8, **score) if fused else layers.head(x, d, last_rows, **score))
 
     @staticmethod
     def _kv_view(i, q_len, fused, kv_cache, spec_cache, dev_len):

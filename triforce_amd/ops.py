@@ -1562,6 +1562,45 @@ def topk_topp_probs(logits, temperature, top_k, top_p):
     return probs
 
 
+# Rows of normalised hidden state that DecoderLayers.head scores per lm_head GEMM when it is asked for the prompt's
+# log-probabilities: the fp32 logits block is SCORE_BLOCK_ROWS x V (131 MB at 32 000) instead of chunk x V.
+SCORE_BLOCK_ROWS = 1024
+TOKEN_LOGPROBS_MAX_IDS = 32
+
+
+def token_logprobs(logits, targets=None, out=None, lse=None):
+    """out[r] = log_softmax(logits[r])[targets[r]] at temperature 1, no top-k / top-p filter, for (rows, V) fp32 device logits
+    (unit stride on V, any row stride >= V, any V) — tf_token_logprobs, one launch; a target outside [0, V) gives 0.
+    ``targets``: an int64 device tensor of ``rows`` ids; or a python list of <= 32 ids, which travel as kernel arguments
+    (tf_token_logprobs_ids: no upload); or None when only ``lse`` (fp32, rows) = log sum exp of every row is wanted.
+    ``out`` / ``lse``: contiguous fp32 device tensors of ``rows`` entries to write (``out`` is allocated when there are
+    targets and none is given).  Returns ``out`` (``lse`` when there are no targets)."""
+    _dev(logits, out, lse)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.numel() > 0
+    rows, V = logits.shape
+    stride = logits.stride(0) if rows > 1 else max(logits.stride(0), V)
+    assert stride >= V, "rows of the logits block overlap"
+    if targets is None:
+        assert lse is not None, "token_logprobs needs targets or lse"
+    elif out is None:
+        out = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    for t in (out, lse):
+        assert t is None or (t.dtype == torch.float32 and t.numel() == rows and t.is_contiguous())
+    if isinstance(targets, (list, tuple)):
+        assert len(targets) == rows <= TOKEN_LOGPROBS_MAX_IDS
+        host = (ctypes.c_int64 * rows)(*[int(t) for t in targets])
+        hip.check(hip.lib().tf_token_logprobs_ids(_ptr(logits), stride, host, rows, V, _ptr(out), _ptr(lse), _stream()),
+                  "tf_token_logprobs_ids")
+        return out
+    if targets is not None:
+        _dev(targets)
+        targets = targets.reshape(-1)
+        assert targets.dtype == torch.int64 and targets.numel() == rows and targets.is_contiguous()
+    hip.check(hip.lib().tf_token_logprobs(_ptr(logits), stride, _ptr(targets), rows, V, _ptr(out), _ptr(lse), _stream()),
+              "tf_token_logprobs")
+    return lse if targets is None else out
+
+
 def sample_inverse_cdf(probs, u, token_out):
     """token_out[0] <- first index with inclusive cumsum(probs) > u[0]*sum(probs).  All device tensors."""
     _dev(probs, u)

@@ -80,7 +80,10 @@ def _worst_walk(successors):
 class SpecTree:
     def __init__(self, engine, temperature: float = 0.6, top_p: float = 0.9, max_length=256, vocab_size=32000,
                  grow_map=None, residual_graph=None, sampling_callables=None, sample_gather_indices=None,
-                 tokenizer=None, rng=None, rand_values=None) -> None:
+                 tokenizer=None, rng=None, rand_values=None, logprobs=False, prompt_logprobs=False) -> None:
+        if logprobs or prompt_logprobs:                  # (refused before anything is captured: DESIGN section 23)
+            raise NotImplementedError("logprobs / prompt_logprobs are implemented for the single-GPU resident TriForce and "
+                                      "autoregressive loops only, not for the Sequoia tree loop (SpecTree)")
         self.graph_engine = engine
         self.temperature, self.top_p = temperature, top_p
         self.residual_graph = residual_graph            # relu(p-q)/sum — computed inside tf_tree_accept

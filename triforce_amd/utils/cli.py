@@ -69,6 +69,9 @@ SCRIPT_OWN = {
         ("--reanchor_at", int, 0, "re-anchor the retrieval cache (fold the generated rows into the covered region and "
                                   "re-select) before its generated tail exceeds N rows, gamma + 2 <= N <= --budget: "
                                   "generation and follow-ups may then pass the budget; 0 = never"),
+        ("--logprobs", "flag", None, "score the prompt during prefill and every emitted token (temperature 1, unfiltered): "
+                                     "prints the prompt's mean negative log-likelihood and perplexity, and the mean "
+                                     "log-probability of the generation and of each follow-up answer"),
     ],
 }
 

@@ -34,13 +34,23 @@ def _eos(tokenizer):
 
 @torch.inference_mode()
 def Autoregressive(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, top_p=0.9, temperature=0.6, verbose=False,
-                   rng=None, return_tokens=False):
+                   rng=None, return_tokens=False, logprobs=False):
+    """``logprobs``: also the log-probability (temperature 1, unfiltered: DESIGN section 23) of every emitted token, scored
+    on the device from the step's own logits -> (tokens / s, ids, logprobs)."""
     eng = graph_engine.engine
     device = eng.model.device
+    lp = None
+    if logprobs:
+        refusal = _logprobs_refusal(graph_engine, "logprobs")
+        if refusal is not None:
+            raise NotImplementedError(refusal)
+        lp = torch.empty(max_len + 1, dtype=torch.float32, device=device)
     rng = rng or UniformSource(device)
     eng.kv_cache.reset()
     logits = graph_engine.inference(input_ids=input_ids)
     next_token = sample(norm_logits(logits[:, -1, :], temperature=temperature, top_k=top_k, top_p=top_p), rng=rng)
+    if lp is not None:
+        ops.token_logprobs(logits[:, -1, :], next_token.view(-1), out=lp[0:1])
     toks = [next_token]
     n = 0
     _sync(device)
@@ -52,16 +62,35 @@ def Autoregressive(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, to
         next_token = sample(norm_logits(logits[:, -1, :], temperature=temperature, top_k=top_k, top_p=top_p), rng=rng)
         toks.append(next_token)
         n += 1
+        if lp is not None:                  # device targets, the step's own logits (a graph's static buffer until its next replay)
+            ops.token_logprobs(logits[:, -1, :], next_token.view(-1), out=lp[n:n + 1])
     _sync(device)
     time2 = time.time()
-    if verbose or return_tokens:
+    if verbose or return_tokens or logprobs:
         ids = torch.cat(toks, dim=1)[0].tolist()
         if verbose:
             for t in ids:
                 spec_stream(t, tokenizer, "cyan")
+        if logprobs:
+            return n / (time2 - time1), ids, lp[:n + 1].tolist()
         if return_tokens:
             return n / (time2 - time1), ids
     return n / (time2 - time1)
+
+
+def _logprobs_refusal(graph_engine, what):
+    """Why ``logprobs`` / ``prompt_logprobs`` cannot be served over this engine (None: they can) — DESIGN section 23: the
+    single-GPU GraphInferenceEngine over a resident FlashSimpleCache (fp16 or FP8) and a RetrievalCache."""
+    from ..models.cache import FlashSimpleCache, RetrievalCache
+    from .graph_infer import GraphInferenceEngine
+    if not isinstance(graph_engine, GraphInferenceEngine):
+        return (f"{what} is implemented for the single-GPU resident GraphInferenceEngine only, not for "
+                f"{type(graph_engine).__name__} (tensor-parallel loop)")
+    eng = graph_engine.engine
+    if type(eng.kv_cache) is not FlashSimpleCache or type(eng.graph_cache) is not RetrievalCache:
+        return (f"{what} is implemented for the resident FlashSimpleCache + RetrievalCache only, not for "
+                f"{type(eng.kv_cache).__name__} + {type(eng.graph_cache).__name__}")
+    return None
 
 
 class _Record:
@@ -330,7 +359,13 @@ class TriForceRunner:
     ``max_len`` tokens, bench.py drives it for an exact number of steps."""
 
     def __init__(self, tokenizer, graph_engine, gamma, top_k=-1, top_p=0.9, temperature=0.6, verbose=False, rng=None,
-                 inclusive_accept=False, sync_record=None, rebuild_every=0, reanchor_at=0):
+                 inclusive_accept=False, sync_record=None, rebuild_every=0, reanchor_at=0, logprobs=False,
+                 prompt_logprobs=False):
+        # logprobs: keep the log-probability (temperature 1, unfiltered: DESIGN section 23) of every emitted token, scored on the
+        #              device from the logits of the verify that produced it — one launch per step, no host read before stats()
+        # prompt_logprobs: prefill() also scores the prompt, log p(input_ids[i + 1] | input_ids[:i + 1]) for i = 0 .. n - 2
+        self.logprobs, self.want_prompt_logprobs = bool(logprobs), bool(prompt_logprobs)
+        self._lp, self._lp_n, self.prompt_logprobs = None, 0, None
         # rebuild_every: N > 0 re-selects the retrieval cache's prefill chunks during every N-th target verify
         #                (SURVEY 8f row 4); 0 = the reference's behaviour, one build per prompt
         self.rebuild_every, self.rebuilds = int(rebuild_every), 0
@@ -352,6 +387,10 @@ class TriForceRunner:
         self.health = None
         self.tokenizer, self.ge, self.eng = tokenizer, graph_engine, graph_engine.engine
         self.gamma, self.top_k, self.top_p, self.temperature, self.verbose = gamma, top_k, top_p, temperature, verbose
+        if self.logprobs or self.want_prompt_logprobs:  # (refused before anything is captured or allocated)
+            refusal = self._extend_refusal("logprobs / prompt_logprobs")
+            if refusal is not None:
+                raise NotImplementedError(refusal)
         if self.reanchor_at != 0:                      # (refused before anything is captured or allocated)
             refusal = self._extend_refusal("reanchor_at")
             if refusal is not None:
@@ -381,12 +420,23 @@ class TriForceRunner:
         self.time_extend, self.extend_seconds = False, None
 
     @torch.inference_mode()
-    def prefill(self, input_ids):
+    def prefill(self, input_ids, prompt_logprobs=None):
+        """``prompt_logprobs`` (None: the runner's setting): score the prompt in the same pass — ``self.prompt_logprobs`` is the
+        (n - 1,) fp32 device tensor of log p(input_ids[i + 1] | input_ids[:i + 1]), handed out by stats()."""
         eng, ge = self.eng, self.ge
+        score = self.want_prompt_logprobs if prompt_logprobs is None else bool(prompt_logprobs)
+        if score and not self.want_prompt_logprobs:
+            refusal = self._extend_refusal("prompt_logprobs")
+            if refusal is not None:
+                raise NotImplementedError(refusal)
         eng.kv_cache.reset()
         eng.graph_cache.reset()
         eng.draft_cache.reset()
-        ge.inference(input_ids=input_ids[:, :-1])
+        self.prompt_logprobs = None
+        if score:
+            self.prompt_logprobs = ge.inference(input_ids=input_ids[:, :-1], next_ids=input_ids[0, 1:].contiguous())[1]
+        else:
+            ge.inference(input_ids=input_ids[:, :-1])
         logits = ge.inference(input_ids=input_ids[:, -1:])         # q_len==1 -> the retrieval cache is built here
         ge.graph_draft_prefill(input_ids=input_ids)
         if self.verbose:
@@ -534,6 +584,23 @@ class TriForceRunner:
         if self.verbose:
             spec_stream(self.next_token, self.tokenizer, "cyan")
         self.emitted = [self.next_token]
+        if self.logprobs:
+            self._lp_n = 0                             # (a new answer: extend() starts here too)
+            self._score(logits[0, -1:], [self.next_token])
+
+    def _score(self, logits, ids):
+        """Append the log-probabilities of ``ids`` under rows 0 .. len(ids) - 1 of the (rows, V) fp32 ``logits`` to the device
+        buffer, in emission order: one launch, the ids as kernel arguments, nothing read back."""
+        k, n = len(ids), self._lp_n
+        if k == 0:
+            return
+        if self._lp is None or n + k > self._lp.numel():
+            grown = torch.empty(max(1024, 2 * (n + k)), dtype=torch.float32, device=self.device)
+            if n:
+                grown[:n].copy_(self._lp[:n])
+            self._lp = grown
+        ops.token_logprobs(logits[:k], list(ids), out=self._lp[n:n + k])
+        self._lp_n = n + k
 
     def _device_sets(self):
         """The captured verify graphs' device scalars (``ge.verify_sets``) when this runner sets its steps up on the device, else
@@ -595,6 +662,7 @@ class TriForceRunner:
         eager = self.eager_every > 0 and (len(self.counts) + 1) % self.eager_every == 0
         sets = self._device_sets()
         on_device = sets is not None and not rebuild and not eager
+        logits = None                                                  # (set by the last route below only)
         if on_device:
             if not ge.verify_lengths_current(gamma):
                 ge.sync_verify_lengths(gamma)                          # stale (first step, after an eager / rebuild step): one launch each
@@ -654,6 +722,14 @@ class TriForceRunner:
         else:
             rng.advance(consumed)
         self.last_reason = reason          # 0 rejection + resample, 1 everything accepted (bonus token), 2 accepted eos
+        if self.logprobs:
+            # rows 0 .. count of the verify that just ran are the target's distributions for generated[:count] and for the
+            # resampled / bonus token: scored HERE, before any later launch of this step can touch a static logits buffer
+            if on_device:
+                vlogits = ge.target_graphs[len(ids)].logits
+            else:                                      # verify_probs_ids / verify_probs leave theirs with the engine
+                vlogits = ge.last_logits if logits is None else logits
+            self._score(vlogits[0], generated[:count] + ([pred] if reason != 2 else []))
 
         pass_tokens = [next_token] + generated[:count] + [PAD_TOKEN] * (g2 + 1 - count)
         self._fed += pass_tokens[:count + 1]          # the rows this step leaves in the full cache (extend)
@@ -721,7 +797,13 @@ class TriForceRunner:
 
     def stats(self, seconds):
         acceptance_rate = self.accepted_count / max(self.draft_count, 1)
-        return dict(acceptance_rate=acceptance_rate, tokens_per_s=self.n / seconds, tokens=self.emitted, n=self.n,
+        extra = {}
+        if self.logprobs:                              # the one device-to-host read of the values
+            extra["logprobs"] = self._lp[:self._lp_n].tolist()
+            assert len(extra["logprobs"]) == len(self.emitted)
+        if self.prompt_logprobs is not None:
+            extra["prompt_logprobs"] = self.prompt_logprobs.float().cpu()
+        return dict(**extra, acceptance_rate=acceptance_rate, tokens_per_s=self.n / seconds, tokens=self.emitted, n=self.n,
                     counts=self.counts, accepted=self.accepted_count, drafted=self.draft_count,
                     avg_tokens=acceptance_rate * self.gamma, resampled=self.resample_count,
                     bonus=self.target_sample_count, seconds=seconds, outer_steps=len(self.counts),
@@ -730,9 +812,13 @@ class TriForceRunner:
 
 @torch.inference_mode()
 def TriForce(tokenizer, graph_engine, input_ids, gamma=4, max_len=256, top_k=-1, top_p=0.9, temperature=0.6, verbose=False,
-             file_path=None, dataset=None, spec_args=None, rng=None, return_details=False, rebuild_every=0, reanchor_at=0):
+             file_path=None, dataset=None, spec_args=None, rng=None, return_details=False, rebuild_every=0, reanchor_at=0,
+             logprobs=False, prompt_logprobs=False):
+    """``logprobs`` / ``prompt_logprobs``: ``return_details`` then carries ``logprobs`` — a list aligned
+    with ``tokens`` — and ``prompt_logprobs`` — an fp32 host tensor of n - 1 values."""
     run = TriForceRunner(tokenizer, graph_engine, gamma, top_k, top_p, temperature, verbose, rng,
-                         rebuild_every=rebuild_every, reanchor_at=reanchor_at)
+                         rebuild_every=rebuild_every, reanchor_at=reanchor_at, logprobs=logprobs,
+                         prompt_logprobs=prompt_logprobs)
     run.prefill(input_ids)
     eng, device = run.eng, run.device
     _sync(device)
@@ -767,9 +853,10 @@ class TriForceSession:
     Every answer returns the runner's stats plus ``ttft`` — the seconds from the call to the first token of the answer."""
 
     def __init__(self, tokenizer, graph_engine, gamma=4, top_k=-1, top_p=0.9, temperature=0.6, verbose=False, rng=None,
-                 rebuild_every=0, reanchor_at=0):
+                 rebuild_every=0, reanchor_at=0, logprobs=False, prompt_logprobs=False):
         self.run = TriForceRunner(tokenizer, graph_engine, gamma, top_k, top_p, temperature, verbose, rng,
-                                  rebuild_every=rebuild_every, reanchor_at=reanchor_at)
+                                  rebuild_every=rebuild_every, reanchor_at=reanchor_at, logprobs=logprobs,
+                                  prompt_logprobs=prompt_logprobs)
         self.ttft = None
 
     @property
@@ -910,7 +997,10 @@ def sample_dist(probs, rng=None):
 class _DistEngine:
     """Presents a DistributedLlama through the GraphInferenceEngine surface the decode loops drive."""
 
-    def __init__(self, llm):
+    def __init__(self, llm, logprobs=False, prompt_logprobs=False):
+        if logprobs or prompt_logprobs:                # (refused before anything is captured: DESIGN section 23)
+            raise NotImplementedError("logprobs / prompt_logprobs are implemented for the single-GPU resident "
+                                      "GraphInferenceEngine only, not for _DistEngine (tensor-parallel loop)")
         self.llm = llm
         self._inner = {}
         self.sampling = dict(probs=True, temperature=llm.temperature, top_p=llm.top_p)
@@ -1001,8 +1091,11 @@ class _DistEngine:
 
 @torch.inference_mode()
 def Baseline_Dist(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, top_p=0.9, temperature=0.6, verbose=False,
-                  local_rank=0, rng=None):
+                  local_rank=0, rng=None, logprobs=False):
     """Autoregressive TP baseline (reference decoding.py:243-287): returns (ms per token, generated ids)."""
+    if logprobs:
+        raise NotImplementedError("logprobs is implemented for the single-GPU resident GraphInferenceEngine only, not for "
+                                  "Baseline_Dist (tensor-parallel loop)")
     llm = graph_engine
     rng = rng or UniformSource(llm.device, seed=1)
     llm.reset()
@@ -1045,8 +1138,12 @@ def Middle_Spec_Dist(next_token, llm, gamma, verbose, tokenizer, rng=None):
 
 @torch.inference_mode()
 def TriForce_Dist(tokenizer, llm, input_ids, gamma=4, max_len=256, top_k=-1, top_p=0.9, temperature=0.6, verbose=False,
-                  file_path=None, dataset=None, spec_args=None, rng=None, return_details=False):
+                  file_path=None, dataset=None, spec_args=None, rng=None, return_details=False, logprobs=False,
+                  prompt_logprobs=False):
     """Reference decoding.py:291-428: returns (avg accepted tokens, seconds per token)."""
+    if logprobs or prompt_logprobs:                    # (refused before the engine wrapper or anything else is built)
+        raise NotImplementedError("logprobs / prompt_logprobs are implemented for the single-GPU resident "
+                                  "GraphInferenceEngine only, not for TriForce_Dist (tensor-parallel loop)")
     ge = _DistEngine(llm)
     rng = rng or UniformSource(llm.device, seed=1)          # same seed on every rank: identical uniform streams
     run = TriForceRunner(tokenizer, ge, gamma, top_k, top_p, temperature, verbose, rng, inclusive_accept=True,

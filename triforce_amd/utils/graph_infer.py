@@ -27,13 +27,17 @@ PREFILL_CHUNK = int(os.environ.get("TRIFORCE_PREFILL_CHUNK", "4096"))
 assert PREFILL_CHUNK % 128 == 0 and PREFILL_CHUNK > 0
 
 
-def chunked_prefill(forward, input_ids):
+def chunked_prefill(forward, input_ids, next_ids=None):
     """Run ``forward(chunk) -> logits (1, rows, V)`` over the prompt; returns the logits of the reference's last chunk.
     A ``forward`` that takes ``last_rows`` is asked for only the rows that are returned — the trailing rows of the final
     chunk, one row of every other chunk — instead of a (4096, V) fp32 logits block (524 MB, ~1 TFLOP of lm_head GEMM)
-    per chunk of which at most 128 rows were ever used."""
+    per chunk of which at most 128 rows were ever used.
+    ``next_ids`` (n,) int64: also score every row against its id — ``forward`` is handed each chunk's
+    slice as ``next_ids`` / ``logprobs_out``; returns (logits, (n,) fp32 log-probabilities)."""
     import inspect
     n = input_ids.shape[-1]
+    if next_ids is not None:
+        return _chunked_prefill_scored(forward, input_ids, next_ids.reshape(-1))
     chunk = PREFILL_CHUNK if input_ids.is_cuda else 128
     keep = n - 128 * (math.ceil(n / 128) - 1)          # rows of the reference's last 128-token chunk
     try:
@@ -47,6 +51,21 @@ def chunked_prefill(forward, input_ids):
     return logits[:, -keep:]
 
 
+def _chunked_prefill_scored(forward, input_ids, next_ids):
+    """chunked_prefill with the prompt's log-probabilities: same chunks, same ``last_rows``, same logits."""
+    n = input_ids.shape[-1]
+    assert next_ids.numel() == n and next_ids.dtype == torch.long
+    chunk = PREFILL_CHUNK if input_ids.is_cuda else 128
+    keep = n - 128 * (math.ceil(n / 128) - 1)
+    lp = torch.empty(n, dtype=torch.float32, device=input_ids.device)
+    nchunks = math.ceil(n / chunk)
+    for i in range(nchunks):
+        rows = slice(i * chunk, (i + 1) * chunk)
+        logits = forward(input_ids[:, rows], last_rows=keep if i == nchunks - 1 else 1, next_ids=next_ids[rows],
+                         logprobs_out=lp[rows])
+    return logits[:, -keep:], lp
+
+
 class InferenceEngine:
     def __init__(self, model, cache, graph_cache, draft, draft_cache) -> None:
         self.model = model.eval()                  # target (7B)
@@ -56,8 +75,17 @@ class InferenceEngine:
         self.draft_cache = draft_cache
 
     @torch.inference_mode()
-    def model_run(self, input_ids: torch.LongTensor, rebuild_retrieval=False):
+    def model_run(self, input_ids: torch.LongTensor, rebuild_retrieval=False, next_ids=None):
+        """``next_ids`` (n,) int64: also the log-probability of next_ids[i] under row i -> (logits, (n,) fp32)."""
         n = input_ids.shape[-1]
+        if next_ids is not None:
+            next_ids = next_ids.reshape(-1)
+            if n > 64:
+                return chunked_prefill(lambda ids, last_rows=None, **score: self.model.forward(
+                    ids, self.kv_cache, None, last_rows=last_rows, **score).logits, input_ids, next_ids=next_ids)
+            lp = torch.empty(n, dtype=torch.float32, device=input_ids.device)
+            return self.model.forward(input_ids, self.kv_cache, self.graph_cache, rebuild_retrieval=rebuild_retrieval,
+                                      next_ids=next_ids, logprobs_out=lp).logits, lp
         if n > 64:                                 # chunked prefill (graph_infer.py:30-37)
             logits = chunked_prefill(lambda ids, last_rows=None: self.model.forward(
                 ids, self.kv_cache, None, last_rows=last_rows).logits, input_ids)
@@ -394,6 +422,10 @@ class GraphInferenceEngine:
         # top-k of the TARGET's verify distribution (reference decoding.py:62,90: the two draft tiers always run with -1).
         # Not a key of ``sampling``: that dict is splatted into the draft / retrieval-verify capture functions.
         self.top_k = -1
+        # (1, rows, V) fp32 logits of the last target verify that went through verify_probs / verify_probs_ids — a captured
+        # graph's static buffer or the eager forward's result; valid until the next target forward (what a runner with
+        # ``logprobs`` scores; the replay_in_place route leaves them in its _TargetGraph.logits)
+        self.last_logits = None
 
     @torch.inference_mode()
     def initialize_cuda_graph(self, gamma=6, probs=False, temperature=0.6, top_p=0.9, verbose=True,
@@ -442,7 +474,11 @@ class GraphInferenceEngine:
 
     # -- the surface used by utils/decoding.py ---------------------------------------------------------------
     @torch.inference_mode()
-    def inference(self, input_ids: torch.LongTensor, rebuild_retrieval=False, eager=False):
+    def inference(self, input_ids: torch.LongTensor, rebuild_retrieval=False, eager=False, next_ids=None):
+        """``next_ids`` (n,) int64 device ids: the eager forward, which also scores row i against next_ids[i] ->
+        (logits, (n,) fp32 log-probabilities) — the prompt's log-probabilities."""
+        if next_ids is not None:
+            return self.engine.model_run(input_ids=input_ids, rebuild_retrieval=rebuild_retrieval, next_ids=next_ids)
         tg = None if (eager or rebuild_retrieval) else self._target_graph(input_ids)
         if tg is not None:
             return tg(input_ids)[0].clone()
@@ -468,8 +504,9 @@ class GraphInferenceEngine:
         these settings, else the eager forward + norm_logits.  The result is valid until the next target forward."""
         tg = None if (eager or rebuild_retrieval) else self._target_graph(input_ids)
         if tg is not None and tg.probs and self._captured_with(temperature, top_p, top_k):
-            return tg(input_ids)[1]
-        logits = self.inference(input_ids, rebuild_retrieval=rebuild_retrieval, eager=eager)
+            self.last_logits, probs = tg(input_ids)
+            return probs
+        logits = self.last_logits = self.inference(input_ids, rebuild_retrieval=rebuild_retrieval, eager=eager)
         return norm_logits(logits[0], temperature=temperature, top_k=top_k, top_p=top_p)
 
     @torch.inference_mode()
@@ -481,7 +518,8 @@ class GraphInferenceEngine:
         if tg is None or tg.cache is not self.engine.kv_cache or not tg.probs or not tg.ids.is_cuda \
                 or not self._captured_with(temperature, top_p, top_k):
             return None
-        return tg(list(ids))[1], tg.ids
+        self.last_logits, probs = tg(list(ids))
+        return probs, tg.ids
 
     def verify_sets(self, gamma):
         """(pos, slot, sk, q_len) of the captured verify lengths gamma + 1 / gamma + 2 — what tf_accept_chain_step keeps current —
