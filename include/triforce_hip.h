@@ -573,6 +573,16 @@ int tf_accept_chain_cur(const float* p, const float* q, const int64_t* tokens, c
  *   the positions (n_pos entries from S'), append slot (S') and key count (S' + qlen) of the NEXT verify, S' = *s_src + count + 1
  *   = the cache length after the roll-back (s_src: the append slot of the verify just run).  Neither the catch-up draft nor the
  *   next target verify then needs a set-up launch behind a record read.  tok_len >= g2 + 2; g2 <= 62. */
+/* tf_middle_accept2_cur: up to `depth` (1 or 2) successive inner positions n, n + 2 decided from ONE
+ *   retrieval verify.  The caller ran the draft ahead: tokens[n + 1] = d ~ q1 with ubuf[c]; tokens[n + 2] = a guess of the follow-up
+ *   token (drawn from the draft's next row with ubuf[c + 2], the uniform the follow-up itself uses); tokens[n + 3] ~ q3 with
+ *   ubuf[c + 3] (c = *cursor).  Stage 1 is tf_middle_accept_cur's arithmetic (one shared device function).  If it accepts AND its
+ *   follow-up equals tokens[n + 2], stage 2 decides position n + 2 from rows n + 2, n + 3 of p with ubuf[c + 4], ubuf[c + 5],
+ *   writes tokens[n + 3 + acc2] and sets *cursor = c + 6; otherwise tokens[n + 1 + acc1] and *cursor = c + 3, exactly as
+ *   tf_middle_accept_cur.  out[8] (depth 2; 5 for depth 1) = (acc1, b1, d1, c, stage2_ran, acc2, b2, d2), zeros for a stage that
+ *   did not run, every entry written.  n + 2 (depth - 1) + 1 <= gamma; same store order and stream contract as above. */
+int tf_middle_accept2_cur(const float* p, const float* q1, const float* q3, int64_t* tokens, int tokens_len, const float* ubuf,
+                          int64_t* cursor, int n, int gamma, int V, int depth, int64_t* out, void* stream);
 int tf_accept_chain_step(const float* p, const float* q, int64_t* tok_buf, int tok_len, const float* ubuf, int64_t* cursor,
                          int g2, int V, int inclusive, int64_t eos_token_id, int64_t pad, const int32_t* s_src, int nsets,
                          int64_t* pos_a, int n_pos_a, int32_t* slot_a, int32_t* sk_a, int qlen_a, int64_t* pos_b, int n_pos_b,

@@ -227,6 +227,20 @@ __global__ __launch_bounds__(SAMP_THREADS) void accept_chain_kernel(
     }
 }
 
+// One Middle_Spec decision at position n (decoding.py:190-220): the accept test of the drafted token d with u[0], then the
+// follow-up draw with u[1] from row n + 1 (accepted) or row n (rejected) of the retrieval model's rows.  The ONE place this
+// arithmetic is written: middle_accept_kernel and every stage of middle_accept2_kernel call it, so they agree by construction.
+struct MidDecision { int acc, b; };
+__device__ __forceinline__ MidDecision middle_decide(const float* __restrict__ p, const float* __restrict__ q_d, int64_t d,
+                                                     const float* __restrict__ u, int n, int V, SampleShared* sh) {
+    const float ratio = p[(int64_t)n * V + d] / q_d[d];
+    const float m = (ratio != ratio) ? ratio : fminf(1.0f, ratio);
+    MidDecision r;
+    r.acc = (u[0] < m) ? 1 : 0;
+    r.b = block_sample<false>(p + (int64_t)(n + r.acc) * V, nullptr, V, u[1], sh);
+    return r;
+}
+
 __global__ __launch_bounds__(SAMP_THREADS) void middle_accept_kernel(
     const float* __restrict__ p, const float* __restrict__ q_d, int64_t* __restrict__ tokens,
     const float* __restrict__ uniforms_base, int64_t* cursor, int uoff, int n, int gamma, int V, int64_t* __restrict__ out,
@@ -235,10 +249,8 @@ __global__ __launch_bounds__(SAMP_THREADS) void middle_accept_kernel(
     int64_t at;
     const float* uniforms = cur_uniforms(uniforms_base, cursor, &at) + uoff;
     const int64_t d = tokens[n + 1];
-    const float ratio = p[(int64_t)n * V + d] / q_d[d];
-    const float m = (ratio != ratio) ? ratio : fminf(1.0f, ratio);
-    const int acc = (uniforms[0] < m) ? 1 : 0;
-    const int b = block_sample<false>(p + (int64_t)(n + acc) * V, nullptr, V, uniforms[1], &sh);
+    const MidDecision dec = middle_decide(p, q_d, d, uniforms, n, V, &sh);
+    const int acc = dec.acc, b = dec.b;
     if (threadIdx.x == 0) {
         // first what the next chain reads on the device (write-through, drained), then the record the host waits for
         // (write_limit = gamma: the verify block's gamma + 1 entries; gamma + 1 when `tokens` is the engine's longer token buffer,
@@ -250,6 +262,56 @@ __global__ __launch_bounds__(SAMP_THREADS) void middle_accept_kernel(
         out[1] = b;
         out[2] = d;
         if (cursor) out[3] = at;             // where this decision's numbers began (the host checks its mirror)
+    }
+}
+
+// Up to `depth` successive Middle_Spec decisions from ONE retrieval verify.  The caller has run the draft
+// ahead: tokens[n + 1] = d drawn with u[0]; for every further stage s, tokens[n + 2s] is a GUESS of stage s - 1's follow-up token
+// (drawn from the draft's row with u[3(s-1) + 2], the uniform the follow-up itself uses) and tokens[n + 2s + 1] the draft token
+// drawn behind it with u[3s]; q[s] is the draft row that token came from.  Row i of p depends on tokens <= i only, so when
+// stage s - 1 accepted and its follow-up IS the guess, rows n + 2s, n + 2s + 1 of p are the rows a verify replayed after stage
+// s - 1 would have produced, and stage s is decided here from the uniforms it would have used (u[3s + 1], u[3s + 2]).  A stage
+// that rejects, or whose follow-up misses the guess, ends the loop: the tokens behind it are stale and the next iteration's
+// draw overwrites them.  Record: out[0..3] = (acc, b, d, cursor at entry) of stage 0 as middle_accept_kernel writes them,
+// out[4] = further stages run, out[5 + 3(s-1) ..] = (acc, b, d) of stage s >= 1 (zeros when it did not run) — 5 + 3(depth-1)
+// entries, every one written at every launch (the host's mailbox poll waits for each armed entry).
+#define MID_MAX_DEPTH 4
+struct MidDraftRows { const float* q[MID_MAX_DEPTH]; };
+
+__global__ __launch_bounds__(SAMP_THREADS) void middle_accept2_kernel(
+    const float* __restrict__ p, MidDraftRows qs, int64_t* __restrict__ tokens, const float* __restrict__ uniforms_base,
+    int64_t* cursor, int n, int gamma, int V, int depth, int64_t* __restrict__ out, int write_limit) {
+    __shared__ SampleShared sh;
+    __shared__ int64_t s_rec[3 * MID_MAX_DEPTH];          // (acc, b, d) per stage: thread 0 writes and reads it, no barrier needed
+    int64_t at;
+    const float* u = cur_uniforms(uniforms_base, cursor, &at);
+    int ran = 0, pos = n;
+    MidDecision dec = {0, 0};
+    for (int s = 0; s < depth; ++s) {
+        pos = n + 2 * s;
+        const int64_t d = tokens[pos + 1];
+        dec = middle_decide(p, qs.q[s], d, u + 3 * s + 1, pos, V, &sh);
+        ran = s + 1;
+        if (threadIdx.x == 0) {
+            s_rec[3 * s] = dec.acc;
+            s_rec[3 * s + 1] = dec.b;
+            s_rec[3 * s + 2] = d;
+        }
+        // (every thread reads the same words: the branch is uniform over the block; nothing has been written to tokens yet)
+        if (!(s + 1 < depth && dec.acc == 1 && (int64_t)dec.b == tokens[pos + 2])) break;
+    }
+    if (threadIdx.x == 0) {
+        // first what the next chain reads on the device (write-through, drained), then the record the host waits for
+        if (pos + 1 + dec.acc <= write_limit) st_agent_i64(&tokens[pos + 1 + dec.acc], (int64_t)dec.b);
+        st_agent_i64(cursor, at + 3 * ran);
+        drain_stores();
+        out[0] = s_rec[0];
+        out[1] = s_rec[1];
+        out[2] = s_rec[2];
+        out[3] = at;
+        out[4] = ran - 1;
+        for (int s = 1; s < depth; ++s)
+            for (int k = 0; k < 3; ++k) out[5 + 3 * (s - 1) + k] = s < ran ? s_rec[3 * s + k] : 0;
     }
 }
 
@@ -596,6 +658,24 @@ extern "C" int tf_middle_accept_cur(const float* p, const float* q_d, int64_t* t
     const int limit = tokens_len >= gamma + 2 ? gamma + 1 : gamma;
     hipLaunchKernelGGL(middle_accept_kernel, dim3(1), dim3(SAMP_THREADS), 0, (hipStream_t)stream, p, q_d, tokens, ubuf, cursor,
                        1, n, gamma, V, out, limit);
+    TF_LAUNCH_CHECK();
+    return TF_OK;
+}
+
+// tf_middle_accept_cur for up to `depth` (1 or 2 today) successive positions n, n + 2 decided from ONE verify (see
+// middle_accept2_kernel): q1 / q3 are the draft rows the tokens at n + 1 / n + 3 were drawn from.  Every row and token index
+// a stage touches lies inside the gamma + 1 rows of p: n + 2 (depth - 1) + 1 <= gamma.  out: 5 + 3 (depth - 1) entries.
+extern "C" int tf_middle_accept2_cur(const float* p, const float* q1, const float* q3, int64_t* tokens, int tokens_len,
+                                     const float* ubuf, int64_t* cursor, int n, int gamma, int V, int depth, int64_t* out,
+                                     void* stream) {
+    if (!p || !q1 || !tokens || !ubuf || !cursor || !out || n < 0 || V < 1 || tokens_len < gamma + 1) return TF_EINVAL;
+    if (depth < 1 || depth > 2 || (depth == 2 && !q3) || n + 2 * (depth - 1) + 1 > gamma) return TF_EINVAL;
+    const int limit = tokens_len >= gamma + 2 ? gamma + 1 : gamma;
+    MidDraftRows qs = {};
+    qs.q[0] = q1;
+    qs.q[1] = q3;
+    hipLaunchKernelGGL(middle_accept2_kernel, dim3(1), dim3(SAMP_THREADS), 0, (hipStream_t)stream, p, qs, tokens, ubuf, cursor,
+                       n, gamma, V, depth, out, limit);
     TF_LAUNCH_CHECK();
     return TF_OK;
 }

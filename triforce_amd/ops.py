@@ -1667,6 +1667,81 @@ def middle_accept_cur(p, q_d, tokens, ubuf, cursor, n, gamma, out):
                                              int(gamma), V, _ptr(out), _stream()), "tf_middle_accept_cur")
 
 
+MID2_RECORD = 8       # (acc1, b1, d1, cursor at entry, stage2_ran, acc2, b2, d2): the record of a depth-2 middle_accept2_cur
+
+
+def middle_accept2_cur(p, q1, q3, tokens, ubuf, cursor, n, gamma, out, depth=2):
+    """Positions n and (when stage 1 accepts and its follow-up equals the guess in tokens[n + 2]) n + 2 of Middle_Spec decided
+    from ONE verify's rows ``p`` (tf_middle_accept2_cur): q1 / q3 are the draft rows tokens[n + 1] /
+    tokens[n + 3] were drawn from with ubuf[cursor], ubuf[cursor + 3]; cursor += 3 or 6; out[8] <- (acc1, b1, d1, cursor at
+    entry, stage2_ran, acc2, b2, d2).  CPU tensors: the torch restatement below (the tests' oracle)."""
+    V = p.shape[-1]
+    assert p.dtype == torch.float32 and p.is_contiguous() and p.shape[0] >= gamma + 1
+    assert q1.dtype == torch.float32 and q1.numel() == V and (depth == 1 or (q3.dtype == torch.float32 and q3.numel() == V))
+    assert tokens.dtype == torch.int64 and tokens.is_contiguous() and tokens.numel() >= gamma + 1
+    assert depth in (1, 2) and 0 <= n and n + 2 * (depth - 1) + 1 <= gamma and out.dtype == torch.int64
+    assert out.numel() >= 5 + 3 * (depth - 1) and ubuf.dtype == torch.float32 and cursor.dtype == torch.int64
+    if not p.is_cuda:
+        return middle_accept2_host(p, q1, q3, tokens, ubuf, cursor, n, gamma, out, depth)
+    _dev(p, q1, q3, tokens, ubuf, cursor)
+    _dev_or_pinned(out)
+    hip.check(hip.lib().tf_middle_accept2_cur(_ptr(p), _ptr(q1), _ptr(q3), _ptr(tokens), tokens.numel(), _ptr(ubuf), _ptr(cursor),
+                                              int(n), int(gamma), V, int(depth), _ptr(out), _stream()), "tf_middle_accept2_cur")
+
+
+def _invcdf_host(probs, u):
+    """block_sample<false> in torch: the first index of non-zero mass whose inclusive cumulative sum exceeds u * total (the
+    last non-zero index when rounding takes u * total past the end)."""
+    c = torch.cumsum(probs, 0)
+    hit = ((probs > 0) & (c > u * c[-1])).nonzero()
+    if hit.numel():
+        return int(hit[0])
+    nz = (probs > 0).nonzero()
+    return int(nz[-1]) if nz.numel() else 0
+
+
+def middle_accept_host(p, q_d, tokens, ubuf, cursor, n, gamma, out):
+    """tf_middle_accept_cur restated in torch for CPU tensors (same reads, same writes, same record)."""
+    at = int(cursor[0])
+    d = int(tokens[n + 1])
+    ratio = p[n, d] / q_d[d]                                   # (0 / 0 = NaN: every comparison with it is False -> rejected)
+    m = ratio if bool(ratio != ratio) else torch.clamp(ratio, max=1.0)
+    acc = int(bool(ubuf[at + 1] < m))
+    b = _invcdf_host(p[n + acc], ubuf[at + 2])
+    limit = gamma + 1 if tokens.numel() >= gamma + 2 else gamma
+    if n + 1 + acc <= limit:
+        tokens[n + 1 + acc] = b
+    cursor[0] = at + 3
+    out[:4] = torch.tensor([acc, b, d, at], dtype=torch.int64)
+
+
+def middle_accept2_host(p, q1, q3, tokens, ubuf, cursor, n, gamma, out, depth=2):
+    """tf_middle_accept2_cur restated in torch for CPU tensors: a loop over stages, each one the single-stage arithmetic of
+    middle_accept_host at position n + 2 s with the uniforms behind cursor + 3 s; the token and the cursor are written once,
+    for the last stage that ran."""
+    at = int(cursor[0])
+    limit = gamma + 1 if tokens.numel() >= gamma + 2 else gamma
+    stages, qs = [], (q1, q3)
+    for s in range(depth):
+        pos = n + 2 * s
+        d = int(tokens[pos + 1])
+        ratio = p[pos, d] / qs[s][d]
+        m = ratio if bool(ratio != ratio) else torch.clamp(ratio, max=1.0)
+        acc = int(bool(ubuf[at + 3 * s + 1] < m))
+        b = _invcdf_host(p[pos + acc], ubuf[at + 3 * s + 2])
+        stages.append((acc, b, d))
+        if not (s + 1 < depth and acc == 1 and b == int(tokens[pos + 2])):
+            break
+    acc, b, _ = stages[-1]
+    if pos + 1 + acc <= limit:
+        tokens[pos + 1 + acc] = b
+    cursor[0] = at + 3 * len(stages)
+    rec = list(stages[0]) + [at, len(stages) - 1]
+    for s in range(1, depth):
+        rec += list(stages[s]) if s < len(stages) else [0, 0, 0]
+    out[:len(rec)] = torch.tensor(rec, dtype=torch.int64)
+
+
 def accept_chain_cur(p, q, tokens, ubuf, cursor, g2, inclusive, eos_token_id, out):
     """accept_chain over ubuf[cursor ...]; cursor += the numbers consumed (out[3])."""
     _dev(p, q, tokens, ubuf, cursor)

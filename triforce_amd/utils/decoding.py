@@ -136,6 +136,53 @@ class _Record:
 INNER_GRAPH = __import__("os").environ.get("TRIFORCE_INNER_GRAPH", "1") != "0"
 
 
+class LookaheadPolicy:
+    """When the inner loop replays the lookahead form of an iteration.  A lookahead replay costs two draft
+    steps more than a plain one and saves a whole retrieval verify when its guess hits, so it pays while the hit rate stays
+    above ``break_even`` (measured at capture: utils/graph_infer._InnerGraphs).  Over the last WINDOW lookahead replays: a hit
+    rate below break_even switches to the plain graphs for the next REST logical iterations, then the form is probed again.
+    The policy sees only decisions of the token path, so a run is reproducible; and it changes no token either way."""
+
+    WINDOW, REST = 32, 128
+
+    def __init__(self, break_even):
+        self.break_even = float(break_even)
+        self.recent, self.rest = [], 0
+        self.switched_off = 0                      # times a window fell below break_even
+
+    def on(self):
+        return self.rest == 0
+
+    def replayed(self, hit):
+        """A lookahead replay was issued; ``hit``: it decided two iterations."""
+        self.recent.append(1 if hit else 0)
+        if len(self.recent) > self.WINDOW:
+            self.recent.pop(0)
+        if len(self.recent) == self.WINDOW and sum(self.recent) / self.WINDOW < self.break_even:
+            self.rest, self.recent = self.REST, []
+            self.switched_off += 1
+
+    def passed(self, iterations):
+        """``iterations`` logical inner iterations ran on the plain graphs while the policy was off."""
+        self.rest = max(0, self.rest - int(iterations))
+
+
+class _Lookahead:
+    """What Middle_Spec keeps about the lookahead form between calls: the policy and the replay counters (on _SpecBuffers)."""
+
+    def __init__(self, break_even):
+        self.policy = LookaheadPolicy(break_even)
+        self.verify_replays = self.lookahead_replays = self.lookahead_hits = 0
+
+
+def lookahead_fits(rng, depth=2):
+    """The lookahead form reads the uniforms of ``depth`` iterations behind the cursor.  The plain path would refill the
+    stream's block between two iterations when the second one's three numbers did not fit (UniformSource._room): reading
+    ahead across that point would take other numbers than the plain path, and with them other tokens.  So: only when all
+    3 * depth numbers lie inside the current block."""
+    return rng.pos + 3 * depth <= rng.block
+
+
 _MAILBOX_OK = {}
 
 
@@ -182,7 +229,8 @@ class _SpecBuffers:
         self.spec_rows = torch.empty(gamma + 2, vocab, dtype=torch.float32, device=device)
         self.rows_generation = None                # lifetime token of static (un-copied) retrieval-verify rows
         mailbox = bool(mailbox) and _mailbox_supported(device)
-        self.mid_out = _Record(device, 4, mailbox)
+        self.mid_out = _Record(device, ops.MID2_RECORD, mailbox)      # 4 entries of a plain iteration, 8 of a lookahead one
+        self.lookahead = None                      # _Lookahead of the runner whose inner graphs have the lookahead form
         self.chain_out = _Record(device, 4, mailbox)
         self.pos_base = torch.arange(gamma + 1, dtype=torch.long, device=device).unsqueeze(0)
         # host -> device token lists go through one pinned staging row (a pageable source makes the copy synchronous)
@@ -260,26 +308,46 @@ def Middle_Spec(next_token, graph_engine, gamma, verbose, tokenizer, rng=None, b
     # read of the previous accept record and the next launch — the one place where host time is GPU idle time)
     replay_draft = getattr(graph_engine, "replay_draft", None) if (noclone and buffers.shared_inputs) else None
     flat = vt.view(-1)
+    look = buffers.lookahead if (inner is not None and inner.look) else None
     while inner is not None and n < gamma:
         # one launch, one read: [draft step n, draw, retrieval verify, accept test + follow-up draw] is ONE hipGraph whose
         # kernels take their three uniforms from the stream's device cursor and advance it
-        rng.cursor_tensor(3)
         rec = buffers.mid_out
-        rec.arm(4)
-        p = inner.replay(n)
-        acc, b, d, at = rec.read(4)                                           # the one host read of this step
-        rng.advanced_on_device(3, at)
-        drafted += 1
-        if acc:                                                               # decoding.py:193-209
-            ids += [d, b]
-            accepted += 1
-            n += 2
-        else:                                                                 # decoding.py:211-220
-            ids.append(b)
-            n += 1
-        if verbose:
-            for t, colour in (((d, "green"), (b, "blue")) if acc else ((b, "red"),)):
-                spec_stream(t, tokenizer, colour)
+        # the lookahead form: this replay also decides the NEXT iteration when its guess of b is right
+        ahead = look is not None and n in inner.look and lookahead_fits(rng) and look.policy.on()
+        if ahead:
+            rng.cursor_tensor(6)
+            rec.arm(8)
+            p = inner.replay(n, lookahead=True)
+            acc, b, d, at, ran2, acc2, b2, d2 = rec.read(8)                   # the one host read of these one or two steps
+            rng.advanced_on_device(6 if ran2 else 3, at)
+            decided = ((acc, b, d), (acc2, b2, d2)) if ran2 else ((acc, b, d),)
+            look.lookahead_replays += 1
+            look.lookahead_hits += 1 if ran2 else 0
+            look.policy.replayed(ran2)
+        else:
+            rng.cursor_tensor(3)
+            rec.arm(4)
+            p = inner.replay(n)
+            acc, b, d, at = rec.read(4)                                       # the one host read of this step
+            rng.advanced_on_device(3, at)
+            decided = ((acc, b, d),)
+            if look is not None:
+                look.policy.passed(1)
+        if look is not None:
+            look.verify_replays += 1
+        for acc, b, d in decided:                  # each one exactly an iteration of the plain loop
+            drafted += 1
+            if acc:                                                           # decoding.py:193-209
+                ids += [d, b]
+                accepted += 1
+                n += 2
+            else:                                                             # decoding.py:211-220
+                ids.append(b)
+                n += 1
+            if verbose:
+                for t, colour in (((d, "green"), (b, "blue")) if acc else ((b, "red"),)):
+                    spec_stream(t, tokenizer, colour)
     if inner is not None:
         # row i of the LAST replay's static output is the retrieval model's distribution after tokens 0..i (see below)
         buffers.rows_generation = graph_engine.verify_generation()
@@ -409,9 +477,12 @@ class TriForceRunner:
                 and hasattr(graph_engine, "inner_graphs"):
             self.inner = graph_engine.inner_graphs(gamma, self.rng, self.bufs.mid_out.tensor)   # captured here, not in a step
             self.bufs.inner_for = (self.inner, self.rng) if self.inner is not None else None
+        # the lookahead form of the inner iterations: policy + counters live with the buffers Middle_Spec is handed
+        self.bufs.lookahead = _Lookahead(self.inner.break_even) if (self.inner is not None and self.inner.look) else None
         self.resample_count = self.accepted_count = self.target_sample_count = self.draft_count = 0
         self.n = 0
-        self.inner_iters = 0          # Middle_Spec iterations = 68M draft calls = retrieval-verify replays
+        self.inner_iters = 0          # LOGICAL Middle_Spec iterations (decisions); the lookahead form decides up to two per
+        #                               retrieval-verify replay: stats()['verify_replays'] counts the replays
         self.emitted, self.counts, self.acc_rate_middle_list = [], [], []
         self.next_token, self.last_reason = None, None
         # extend(): the ids of the full cache's rows — ``history`` (1, n) as of the last prefill() / extend(), ``_fed`` the rows
@@ -803,6 +874,11 @@ class TriForceRunner:
             assert len(extra["logprobs"]) == len(self.emitted)
         if self.prompt_logprobs is not None:
             extra["prompt_logprobs"] = self.prompt_logprobs.float().cpu()
+        look = self.bufs.lookahead
+        # retrieval-verify replays the inner loop issued (0 when it does not run on the inner-iteration graphs' lookahead
+        # form: then every inner iteration is one replay), how many carried the lookahead, how many of those decided two
+        extra.update(verify_replays=look.verify_replays if look else 0, lookahead_replays=look.lookahead_replays if look else 0,
+                     lookahead_hits=look.lookahead_hits if look else 0)
         return dict(**extra, acceptance_rate=acceptance_rate, tokens_per_s=self.n / seconds, tokens=self.emitted, n=self.n,
                     counts=self.counts, accepted=self.accepted_count, drafted=self.draft_count,
                     avg_tokens=acceptance_rate * self.gamma, resampled=self.resample_count,

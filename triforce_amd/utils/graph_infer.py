@@ -293,18 +293,62 @@ class _InnerGraphs:
             graph, p = _capture(run, (), self.pool, 2)
             self.graphs.append(graph)
             self.p.append(p)
+        # The LOOKAHEAD form of position n <= gamma - 3: the draft runs two steps ahead — a guess of the
+        # follow-up token, drawn with the uniform the follow-up itself will use, goes to row n + 2 and a draft token behind it to
+        # row n + 3 of the SAME verify block (rows that otherwise hold PAD) — and tf_middle_accept2_cur decides position n and,
+        # when the guess was right, position n + 2 as well: one retrieval verify for two inner iterations.  Same pool; each
+        # graph has its own static p and its own draft rows q1 / q3.
+        self.look, self.look_p = {}, {}
+        self.break_even = None                                 # s* = (lookahead replay - plain replay) / plain replay, measured below
+        if _InnerGraphs.lookahead_wanted(gamma, record):
+            for n in range(gamma - 2):
+                def run2(n=n):
+                    q1 = eng.draft_run(input_ids=ge.tok_buf[:, :n + 1], gamma_offset=n, **kw)
+                    ops.sample_inverse_cdf_cur(q1, rng.buf, rng.cursor, 0, flat[n + 1:n + 2])
+                    q2 = eng.draft_run(input_ids=ge.tok_buf[:, :n + 2], gamma_offset=n + 1, **kw)
+                    ops.sample_inverse_cdf_cur(q2, rng.buf, rng.cursor, 2, flat[n + 2:n + 3])       # the guess: coupled draw
+                    q3 = eng.draft_run(input_ids=ge.tok_buf[:, :n + 3], gamma_offset=n + 2, **kw)
+                    ops.sample_inverse_cdf_cur(q3, rng.buf, rng.cursor, 3, flat[n + 3:n + 4])
+                    p = eng.model_verify(input_ids=ge.tok_buf[:, :gamma + 1], position_ids=ge.pos_buf, **kw)
+                    ops.middle_accept2_cur(p, q1, q3, flat, rng.buf, rng.cursor, n, gamma, record)
+                    return p
+
+                self.look[n], self.look_p[n] = _capture(run2, (), self.pool, 2)
+            self.break_even = self._measure_break_even(rng)
         torch.cuda.synchronize()
         rng.device_cursor = False                              # the warm-up passes advanced the device copy
 
     @staticmethod
+    def lookahead_wanted(gamma, record):
+        return os.environ.get("TRIFORCE_INNER_LOOKAHEAD", "1") != "0" and record.numel() >= ops.MID2_RECORD and gamma >= 3
+
+    def _measure_break_even(self, rng, reps=3):
+        """Replay time of the plain and the lookahead graph of position 0 over the scratch state of the warm-up passes (zero
+        tokens, the caches as capture left them; a replay's cost does not depend on them) -> the skip probability above
+        which the lookahead form pays."""
+        def timed(graph):
+            rng.cursor.fill_(0)
+            graph.replay()
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(reps):
+                graph.replay()
+            e.record()
+            e.synchronize()
+            return s.elapsed_time(e) / reps
+        self.plain_ms, self.look_ms = timed(self.graphs[0]), timed(self.look[0])
+        return max(0.0, (self.look_ms - self.plain_ms) / self.plain_ms)
+
+    @staticmethod
     def key_of(ge, gamma, rng, record):
         return (gamma, id(rng), rng.buf.data_ptr(), rng.cursor.data_ptr(), record.data_ptr(), ge.tok_buf.data_ptr(),
-                id(ge.engine.kv_cache), id(ge.engine.graph_cache), id(ge.engine.draft_cache))
+                id(ge.engine.kv_cache), id(ge.engine.graph_cache), id(ge.engine.draft_cache),
+                _InnerGraphs.lookahead_wanted(gamma, record))
 
-    def replay(self, n):
-        self.graphs[n].replay()
+    def replay(self, n, lookahead=False):
+        (self.look[n] if lookahead else self.graphs[n]).replay()
         self.generation += 1
-        return self.p[n]
+        return self.look_p[n] if lookahead else self.p[n]
 
 
 def draft_run_capture_graph(engine: InferenceEngine, gamma_offset: int = 0, mempool=None, n_warmups: int = 3, probs=False,
