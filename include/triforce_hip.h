@@ -583,6 +583,16 @@ int tf_accept_chain_cur(const float* p, const float* q, const int64_t* tokens, c
  *   did not run, every entry written.  n + 2 (depth - 1) + 1 <= gamma; same store order and stream contract as above. */
 int tf_middle_accept2_cur(const float* p, const float* q1, const float* q3, int64_t* tokens, int tokens_len, const float* ubuf,
                           int64_t* cursor, int n, int gamma, int V, int depth, int64_t* out, void* stream);
+/* tf_middle_accept_n_cur: the N-stage form of tf_middle_accept2_cur, depth 1 .. 4 successive inner positions
+ *   n, n + 2, n + 4, .. decided from ONE retrieval verify by the same kernel.  One draft row per stage: tokens[n + 2s + 1] ~ q1,
+ *   q3, q5, q7 with ubuf[c + 3s]; tokens[n + 2s] (s >= 1) a guess of stage s - 1's follow-up token drawn with ubuf[c + 3(s-1) + 2].
+ *   Stage s runs iff every earlier stage accepted and its follow-up equals the guess; it uses ubuf[c + 3s + 1], ubuf[c + 3s + 2].
+ *   Only the last stage that ran writes its follow-up token; *cursor = c + 3 x stages run.  out[5 + 3 (depth - 1)] = (acc, b, d, c,
+ *   further stages run, then (acc, b, d) per further stage, zeros for a stage that did not run), every entry written; out_len is
+ *   the room behind `out`.  n + 2 (depth - 1) + 1 <= gamma; a non-null row for every stage up to depth; rows beyond may be NULL. */
+int tf_middle_accept_n_cur(const float* p, const float* q1, const float* q3, int64_t* tokens, int tokens_len, const float* ubuf,
+                           int64_t* cursor, int n, int gamma, int V, int depth, int64_t* out, void* stream, const float* q5,
+                           const float* q7, int out_len);
 int tf_accept_chain_step(const float* p, const float* q, int64_t* tok_buf, int tok_len, const float* ubuf, int64_t* cursor,
                          int g2, int V, int inclusive, int64_t eos_token_id, int64_t pad, const int32_t* s_src, int nsets,
                          int64_t* pos_a, int n_pos_a, int32_t* slot_a, int32_t* sk_a, int qlen_a, int64_t* pos_b, int n_pos_b,

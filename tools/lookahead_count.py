@@ -14,7 +14,14 @@ are compared with the recorded (acc, b) after the run.  The tool then walks ever
 would (a hit skips the next replay; lookahead only at n <= gamma - 3) and projects the gain from the measured stage
 latencies:   hits x retrieval_verify_us - lookahead replays x 2 x (draft_step_us + draw_us)   per step.
 
-    python tools/lookahead_count.py [profiles/lookahead_hit_rate.jsonl] [--steps 200] [bench.py workload flags]
+Depth 3: the same recorded iterations are also walked as a loop of depth <= 3 would run them
+(`walk_depth`: a replay at n <= gamma - 5 decides up to three iterations while every guess holds), and the replays per step by
+form, the third decisions per step and the net saving over depth 2,
+    skipped replays x retrieval_verify_us - additional draft steps x (draft_step_us + draw_us)   per step,
+go to profiles/lookahead3_hit_rate.jsonl with the per-step record [n, accepted, guess hit] of every iteration.
+
+    python tools/lookahead_count.py [profiles/lookahead_hit_rate.jsonl] [--depth3-out profiles/lookahead3_hit_rate.jsonl]
+                                    [--steps 200] [bench.py workload flags]
 """
 import json
 import os
@@ -44,12 +51,75 @@ def walk(steps, gamma, key):
     return replays, looks, hits
 
 
+def walk_depth(steps, gamma, key, max_depth=3):
+    """The recorded iterations walked as a loop of lookahead depth <= max_depth would run them.  
+
+    `steps` is a list of steps, each a list of iterations `{"n": position, key: the follow-up guess was right (and d accepted)}`
+    in the order the plain loop ran them.  A replay at position n takes the largest depth D <= max_depth with
+    n + 2 (D - 1) + 1 <= gamma; stage s + 1 of it runs iff stage s hit, and every stage that ran decides one recorded
+    iteration.  Returns counts over all steps: replays by depth chosen, decisions by stage reached, draft steps (2 D - 1 per
+    replay) and the logical iterations decided.
+    """
+    by_depth = {d: 0 for d in range(1, max_depth + 1)}
+    decided = {d: 0 for d in range(1, max_depth + 1)}      # replays that decided exactly d iterations
+    draft_steps = iterations = 0
+    for its in steps:
+        i = 0
+        while i < len(its):
+            n = its[i]["n"]
+            depth = 1
+            while depth < max_depth and n + 2 * depth + 1 <= gamma:
+                depth += 1
+            by_depth[depth] += 1
+            draft_steps += 2 * depth - 1
+            ran = 1
+            while ran < depth and its[i + ran - 1][key] and i + ran < len(its):
+                ran += 1
+            decided[ran] += 1
+            iterations += ran
+            i += ran
+    return {"replays": sum(by_depth.values()), "replays_by_depth": by_depth, "decided": decided,
+            "draft_steps": draft_steps, "iterations": iterations}
+
+
+def project_depth3(steps, gamma, key, rv_us, draft_us, draw_us):
+    """Depth 3 against depth 2 over the same recorded iterations: replays per step by form, third decisions, net saving."""
+    k = max(len(steps), 1)
+    w2, w3 = walk_depth(steps, gamma, key, 2), walk_depth(steps, gamma, key, 3)
+    skipped = w2["replays"] - w3["replays"]
+    more_drafts = w3["draft_steps"] - w2["draft_steps"]
+    return {"depth2": {"replays_per_step": round(w2["replays"] / k, 4), "draft_steps_per_step": round(w2["draft_steps"] / k, 4)},
+            "depth3": {"replays_per_step": round(w3["replays"] / k, 4), "draft_steps_per_step": round(w3["draft_steps"] / k, 4),
+                       "replays_per_step_by_form": {"depth3": round(w3["replays_by_depth"][3] / k, 4),
+                                                    "depth2": round(w3["replays_by_depth"][2] / k, 4),
+                                                    "plain": round(w3["replays_by_depth"][1] / k, 4)},
+                       "third_decisions_per_step": round(w3["decided"][3] / k, 4),
+                       "third_decisions_per_depth3_replay": round(w3["decided"][3] / max(w3["replays_by_depth"][3], 1), 4)},
+            "skipped_replays_per_step": round(skipped / k, 4), "more_draft_steps_per_step": round(more_drafts / k, 4),
+            "projected_net_saving_us_per_step": round((skipped * rv_us - more_drafts * (draft_us + draw_us)) / k, 1),
+            "marginal_break_even_third_rate": round(2 * (draft_us + draw_us) / rv_us, 4)}
+
+
+def measured_step_ms():
+    """Median ms per step of the depth-2 form's 200-step bench runs (profiles/lookahead_bench.jsonl), the gate's denominator."""
+    path = os.path.join(ROOT, "profiles", "lookahead_bench.jsonl")
+    if not os.path.exists(path):
+        return None
+    runs = [json.loads(line) for line in open(path) if line.strip()]
+    ms = sorted(r["ms_per_step"] for r in runs if r.get("build") == "change" and r.get("run", "").startswith("series-"))
+    return ms[len(ms) // 2] if ms else None
+
+
 def main():
-    os.environ["TRIFORCE_INNER_LOOKAHEAD"] = "0"          # the count rides on the PLAIN inner graphs: one decision per replay
+    os.environ["TRIFORCE_INNER_LOOKAHEAD"] = "0"        # the count rides on the PLAIN inner graphs: one decision per replay
     argv = sys.argv[1:]
     out_path = os.path.join(ROOT, "profiles", "lookahead_hit_rate.jsonl")
     if argv and not argv[0].startswith("--"):
         out_path, argv = argv[0], argv[1:]
+    out3_path = os.path.join(ROOT, "profiles", "lookahead3_hit_rate.jsonl")
+    if "--depth3-out" in argv:
+        k = argv.index("--depth3-out")
+        out3_path, argv = argv[k + 1], argv[:k] + argv[k + 2:]
     if "--steps" not in argv:
         argv += ["--steps", "200"]
     args = bench.parse(argv + ["--warmup", "5"] if "--warmup" not in argv else argv)
@@ -138,6 +208,20 @@ def main():
     with open(out_path, "a") as f:
         f.write(json.dumps(res) + "\n")
     print(json.dumps(res), flush=True)
+
+    # depth 3 against depth 2 over the same recorded iterations, priced from this run's own latencies
+    res3 = {"what": "the recorded inner iterations walked as a depth-3 lookahead loop would run them (tools/lookahead_count.py)",
+            "weights": wlabel, "steps": args.steps, "warmup": args.warmup, "gamma": gamma, "inner_iterations": iters,
+            "stage_latency_us": stages, "draw_us": round(draw_us, 1), "guess": "coupled"}
+    res3.update(project_depth3(steps, gamma, "hit_coupled", rv, stages["draft_step_us"], draw_us))
+    step_ms = measured_step_ms()
+    if step_ms:
+        res3["measured_step_ms"] = step_ms
+        res3["projected_net_saving_fraction_of_step"] = round(res3["projected_net_saving_us_per_step"] / (step_ms * 1e3), 4)
+    res3["iterations_by_step"] = [[[it["n"], it["acc"], int(it["hit_coupled"])] for it in its] for its in steps]   # [n, acc, hit]
+    with open(out3_path, "a") as f:
+        f.write(json.dumps(res3) + "\n")
+    print(json.dumps({k: v for k, v in res3.items() if k != "iterations_by_step"}), flush=True)
 
 
 if __name__ == "__main__":

@@ -665,19 +665,40 @@ extern "C" int tf_middle_accept_cur(const float* p, const float* q_d, int64_t* t
 // tf_middle_accept_cur for up to `depth` (1 or 2 today) successive positions n, n + 2 decided from ONE verify (see
 // middle_accept2_kernel): q1 / q3 are the draft rows the tokens at n + 1 / n + 3 were drawn from.  Every row and token index
 // a stage touches lies inside the gamma + 1 rows of p: n + 2 (depth - 1) + 1 <= gamma.  out: 5 + 3 (depth - 1) entries.
-extern "C" int tf_middle_accept2_cur(const float* p, const float* q1, const float* q3, int64_t* tokens, int tokens_len,
-                                     const float* ubuf, int64_t* cursor, int n, int gamma, int V, int depth, int64_t* out,
-                                     void* stream) {
-    if (!p || !q1 || !tokens || !ubuf || !cursor || !out || n < 0 || V < 1 || tokens_len < gamma + 1) return TF_EINVAL;
-    if (depth < 1 || depth > 2 || (depth == 2 && !q3) || n + 2 * (depth - 1) + 1 > gamma) return TF_EINVAL;
-    const int limit = tokens_len >= gamma + 2 ? gamma + 1 : gamma;
+// The one launch of middle_accept2_kernel behind both entries: q[s] is the draft row of stage s (q1, q3, q5, q7).
+static int launch_middle_accept_n(const float* p, const float* const* q, int max_depth, int64_t* tokens, int tokens_len,
+                                  const float* ubuf, int64_t* cursor, int n, int gamma, int V, int depth, int64_t* out,
+                                  void* stream) {
+    if (!p || !tokens || !ubuf || !cursor || !out || n < 0 || V < 1 || tokens_len < gamma + 1) return TF_EINVAL;
+    if (depth < 1 || depth > max_depth || n + 2 * (depth - 1) + 1 > gamma) return TF_EINVAL;
     MidDraftRows qs = {};
-    qs.q[0] = q1;
-    qs.q[1] = q3;
+    for (int s = 0; s < depth; ++s) {
+        if (!q[s]) return TF_EINVAL;
+        qs.q[s] = q[s];
+    }
+    const int limit = tokens_len >= gamma + 2 ? gamma + 1 : gamma;
     hipLaunchKernelGGL(middle_accept2_kernel, dim3(1), dim3(SAMP_THREADS), 0, (hipStream_t)stream, p, qs, tokens, ubuf, cursor,
                        n, gamma, V, depth, out, limit);
     TF_LAUNCH_CHECK();
     return TF_OK;
+}
+
+extern "C" int tf_middle_accept2_cur(const float* p, const float* q1, const float* q3, int64_t* tokens, int tokens_len,
+                                     const float* ubuf, int64_t* cursor, int n, int gamma, int V, int depth, int64_t* out,
+                                     void* stream) {
+    const float* q[MID_MAX_DEPTH] = {q1, q3, nullptr, nullptr};
+    return launch_middle_accept_n(p, q, 2, tokens, tokens_len, ubuf, cursor, n, gamma, V, depth, out, stream);
+}
+
+// The N-stage entry: depth 1 .. MID_MAX_DEPTH successive positions n, n + 2, n + 4, .. decided from ONE
+// verify, one draft row per stage (q1, q3, q5, q7: the rows tokens[n + 1], [n + 3], [n + 5], [n + 7] were drawn from; rows past
+// `depth` may be null).  out_len is the record's room: at least 5 + 3 (depth - 1) entries, every one of them written.
+extern "C" int tf_middle_accept_n_cur(const float* p, const float* q1, const float* q3, int64_t* tokens, int tokens_len,
+                                      const float* ubuf, int64_t* cursor, int n, int gamma, int V, int depth, int64_t* out,
+                                      void* stream, const float* q5, const float* q7, int out_len) {
+    if (depth < 1 || depth > MID_MAX_DEPTH || out_len < 5 + 3 * (depth - 1)) return TF_EINVAL;
+    const float* q[MID_MAX_DEPTH] = {q1, q3, q5, q7};
+    return launch_middle_accept_n(p, q, MID_MAX_DEPTH, tokens, tokens_len, ubuf, cursor, n, gamma, V, depth, out, stream);
 }
 
 extern "C" int tf_accept_chain_cur(const float* p, const float* q, const int64_t* tokens, const float* ubuf, int64_t* cursor,

@@ -91,6 +91,7 @@ SIGNATURES = {
     "tf_sample_inverse_cdf_cur": (_i32, [_vp, _vp, _vp, _i32, _vp, _i32, _vp]),
     "tf_middle_accept_cur": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "tf_middle_accept2_cur": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "tf_middle_accept_n_cur": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32]),
     "tf_accept_chain_step": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _vp, _i32,
                                     _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     "tf_accept_chain_cur": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp]),

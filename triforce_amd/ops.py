@@ -1689,6 +1689,42 @@ def middle_accept2_cur(p, q1, q3, tokens, ubuf, cursor, n, gamma, out, depth=2):
                                               int(n), int(gamma), V, int(depth), _ptr(out), _stream()), "tf_middle_accept2_cur")
 
 
+MID_MAX_DEPTH = 4     # the stage loop's limit in csrc/sampling.hip
+
+
+def mid_record_len(depth):
+    """Entries of the record of a depth-`depth` accept: (acc, b, d, cursor at entry, further stages run) + (acc, b, d) per further stage."""
+    return 5 + 3 * (depth - 1)
+
+
+MID3_RECORD = mid_record_len(3)     # 11
+
+
+def middle_accept_n_cur(p, qs, tokens, ubuf, cursor, n, gamma, out, depth=None):
+    """Up to `depth` (default len(qs), <= MID_MAX_DEPTH) successive positions n, n + 2, .. of Middle_Spec decided from ONE
+    verify's rows ``p`` (tf_middle_accept_n_cur).  ``qs`` holds one draft row per stage (q1, q3, q5, ..: the
+    rows tokens[n + 1], tokens[n + 3], .. were drawn from with ubuf[cursor + 3 s]); stage s runs iff every earlier stage
+    accepted and its follow-up equals the guess in tokens[n + 2 s].  cursor += 3 x stages run; out[5 + 3 (depth - 1)] <- the
+    record, every entry written.  CPU tensors: the torch restatement below (the tests' oracle)."""
+    qs = list(qs)
+    depth = len(qs) if depth is None else int(depth)
+    V = p.shape[-1]
+    assert p.dtype == torch.float32 and p.is_contiguous() and p.shape[0] >= gamma + 1
+    assert 1 <= depth <= MID_MAX_DEPTH and len(qs) >= depth and 0 <= n and n + 2 * (depth - 1) + 1 <= gamma
+    assert all(q is not None and q.dtype == torch.float32 and q.numel() == V for q in qs[:depth]), "one draft row per stage"
+    assert tokens.dtype == torch.int64 and tokens.is_contiguous() and tokens.numel() >= gamma + 1
+    assert out.dtype == torch.int64 and out.numel() >= mid_record_len(depth)
+    assert ubuf.dtype == torch.float32 and cursor.dtype == torch.int64
+    if not p.is_cuda:
+        return middle_accept_n_host(p, qs, tokens, ubuf, cursor, n, gamma, out, depth)
+    _dev(p, tokens, ubuf, cursor, *qs[:depth])
+    _dev_or_pinned(out)
+    q = [_ptr(qs[s]) if s < depth else None for s in range(MID_MAX_DEPTH)]
+    hip.check(hip.lib().tf_middle_accept_n_cur(_ptr(p), q[0], q[1], _ptr(tokens), tokens.numel(), _ptr(ubuf), _ptr(cursor), int(n),
+                                               int(gamma), V, depth, _ptr(out), _stream(), q[2], q[3], out.numel()),
+              "tf_middle_accept_n_cur")
+
+
 def _invcdf_host(probs, u):
     """block_sample<false> in torch: the first index of non-zero mass whose inclusive cumulative sum exceeds u * total (the
     last non-zero index when rounding takes u * total past the end)."""
@@ -1716,12 +1752,17 @@ def middle_accept_host(p, q_d, tokens, ubuf, cursor, n, gamma, out):
 
 
 def middle_accept2_host(p, q1, q3, tokens, ubuf, cursor, n, gamma, out, depth=2):
-    """tf_middle_accept2_cur restated in torch for CPU tensors: a loop over stages, each one the single-stage arithmetic of
+    """tf_middle_accept2_cur restated in torch for CPU tensors (the two-row form of middle_accept_n_host)."""
+    return middle_accept_n_host(p, (q1, q3), tokens, ubuf, cursor, n, gamma, out, depth)
+
+
+def middle_accept_n_host(p, qs, tokens, ubuf, cursor, n, gamma, out, depth):
+    """tf_middle_accept_n_cur restated in torch for CPU tensors: a loop over stages, each one the single-stage arithmetic of
     middle_accept_host at position n + 2 s with the uniforms behind cursor + 3 s; the token and the cursor are written once,
     for the last stage that ran."""
     at = int(cursor[0])
     limit = gamma + 1 if tokens.numel() >= gamma + 2 else gamma
-    stages, qs = [], (q1, q3)
+    stages = []
     for s in range(depth):
         pos = n + 2 * s
         d = int(tokens[pos + 1])

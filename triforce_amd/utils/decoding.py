@@ -167,12 +167,45 @@ class LookaheadPolicy:
         self.rest = max(0, self.rest - int(iterations))
 
 
-class _Lookahead:
-    """What Middle_Spec keeps about the lookahead form between calls: the policy and the replay counters (on _SpecBuffers)."""
+class LookaheadDepthPolicy:
+    """Depth 3 against depth 2.  A depth-3 replay costs two draft steps more than a depth-2 one and saves
+    a further retrieval verify when it decides a THIRD iteration, so it pays while the rate of third decisions per depth-3
+    replay stays above ``break_even`` (the marginal cost measured at capture, as a fraction of a plain replay).  Over the last
+    WINDOW depth-3 replays: a rate below break_even drops to depth 2 for the next REST logical iterations, then depth 3 is
+    probed again.  Like LookaheadPolicy it sees only decisions of the token path and changes no token."""
+
+    WINDOW, REST = 32, 128
 
     def __init__(self, break_even):
+        self.break_even = float(break_even)
+        self.recent, self.rest = [], 0
+        self.switched_down = 0                     # times a window fell below break_even
+
+    def on(self):
+        return self.rest == 0
+
+    def replayed(self, third):
+        """A depth-3 replay was issued; ``third``: it decided three iterations."""
+        self.recent.append(1 if third else 0)
+        if len(self.recent) > self.WINDOW:
+            self.recent.pop(0)
+        if len(self.recent) == self.WINDOW and sum(self.recent) / self.WINDOW < self.break_even:
+            self.rest, self.recent = self.REST, []
+            self.switched_down += 1
+
+    def passed(self, iterations):
+        """``iterations`` logical inner iterations were decided by replays of depth <= 2."""
+        self.rest = max(0, self.rest - int(iterations))
+
+
+class _Lookahead:
+    """What Middle_Spec keeps about the lookahead form between calls: the policies and the replay counters (on _SpecBuffers)."""
+
+    def __init__(self, break_even, break_even3=None):
         self.policy = LookaheadPolicy(break_even)
-        self.verify_replays = self.lookahead_replays = self.lookahead_hits = 0
+        self.depth_policy = LookaheadDepthPolicy(break_even3) if break_even3 is not None else None
+        self.verify_replays = self.lookahead_replays = self.lookahead_hits = self.lookahead_third = 0
+        self.depth3_replays = 0
 
 
 def lookahead_fits(rng, depth=2):
@@ -229,7 +262,7 @@ class _SpecBuffers:
         self.spec_rows = torch.empty(gamma + 2, vocab, dtype=torch.float32, device=device)
         self.rows_generation = None                # lifetime token of static (un-copied) retrieval-verify rows
         mailbox = bool(mailbox) and _mailbox_supported(device)
-        self.mid_out = _Record(device, ops.MID2_RECORD, mailbox)      # 4 entries of a plain iteration, 8 of a lookahead one
+        self.mid_out = _Record(device, ops.MID3_RECORD, mailbox)      # 4 entries of a plain iteration, 8 / 11 of a lookahead one
         self.lookahead = None                      # _Lookahead of the runner whose inner graphs have the lookahead form
         self.chain_out = _Record(device, 4, mailbox)
         self.pos_base = torch.arange(gamma + 1, dtype=torch.long, device=device).unsqueeze(0)
@@ -313,18 +346,29 @@ def Middle_Spec(next_token, graph_engine, gamma, verbose, tokenizer, rng=None, b
         # one launch, one read: [draft step n, draw, retrieval verify, accept test + follow-up draw] is ONE hipGraph whose
         # kernels take their three uniforms from the stream's device cursor and advance it
         rec = buffers.mid_out
-        # the lookahead form: this replay also decides the NEXT iteration when its guess of b is right
-        ahead = look is not None and n in inner.look and lookahead_fits(rng) and look.policy.on()
-        if ahead:
-            rng.cursor_tensor(6)
-            rec.arm(8)
-            p = inner.replay(n, lookahead=True)
-            acc, b, d, at, ran2, acc2, b2, d2 = rec.read(8)                   # the one host read of these one or two steps
-            rng.advanced_on_device(6 if ran2 else 3, at)
-            decided = ((acc, b, d), (acc2, b2, d2)) if ran2 else ((acc, b, d),)
+        # the lookahead form (DESIGN sections 24, 25): this replay also decides the NEXT iteration(s) while its guesses of b are
+        # right.  The largest depth whose rows and uniforms fit, then the two policies.
+        depth = 1
+        if look is not None and n in inner.look and lookahead_fits(rng) and look.policy.on():
+            depth = 2
+            if n in inner.look3 and lookahead_fits(rng, 3) and look.depth_policy.on():
+                depth = 3
+        if depth > 1:
+            k = ops.mid_record_len(depth)
+            rng.cursor_tensor(3 * depth)
+            rec.arm(k)
+            p = inner.replay(n, lookahead=depth)
+            r = rec.read(k)                                                   # the one host read of these one to three steps
+            ran = 1 + r[4]
+            rng.advanced_on_device(3 * ran, r[3])
+            decided = (tuple(r[0:3]),) + tuple(tuple(r[5 + 3 * s:8 + 3 * s]) for s in range(ran - 1))
             look.lookahead_replays += 1
-            look.lookahead_hits += 1 if ran2 else 0
-            look.policy.replayed(ran2)
+            look.lookahead_hits += 1 if ran >= 2 else 0
+            look.policy.replayed(ran >= 2)
+            if depth == 3:
+                look.depth3_replays += 1
+                look.lookahead_third += 1 if ran == 3 else 0
+                look.depth_policy.replayed(ran == 3)
         else:
             rng.cursor_tensor(3)
             rec.arm(4)
@@ -334,6 +378,8 @@ def Middle_Spec(next_token, graph_engine, gamma, verbose, tokenizer, rng=None, b
             decided = ((acc, b, d),)
             if look is not None:
                 look.policy.passed(1)
+        if depth < 3 and look is not None and look.depth_policy is not None:
+            look.depth_policy.passed(len(decided))
         if look is not None:
             look.verify_replays += 1
         for acc, b, d in decided:                  # each one exactly an iteration of the plain loop
@@ -478,7 +524,8 @@ class TriForceRunner:
             self.inner = graph_engine.inner_graphs(gamma, self.rng, self.bufs.mid_out.tensor)   # captured here, not in a step
             self.bufs.inner_for = (self.inner, self.rng) if self.inner is not None else None
         # the lookahead form of the inner iterations: policy + counters live with the buffers Middle_Spec is handed
-        self.bufs.lookahead = _Lookahead(self.inner.break_even) if (self.inner is not None and self.inner.look) else None
+        self.bufs.lookahead = _Lookahead(self.inner.break_even, self.inner.break_even3) \
+            if (self.inner is not None and self.inner.look) else None
         self.resample_count = self.accepted_count = self.target_sample_count = self.draft_count = 0
         self.n = 0
         self.inner_iters = 0          # LOGICAL Middle_Spec iterations (decisions); the lookahead form decides up to two per
@@ -878,7 +925,10 @@ class TriForceRunner:
         # retrieval-verify replays the inner loop issued (0 when it does not run on the inner-iteration graphs' lookahead
         # form: then every inner iteration is one replay), how many carried the lookahead, how many of those decided two
         extra.update(verify_replays=look.verify_replays if look else 0, lookahead_replays=look.lookahead_replays if look else 0,
-                     lookahead_hits=look.lookahead_hits if look else 0)
+                     lookahead_hits=look.lookahead_hits if look else 0,
+                     # depth 3: replays of that form, and how many of them decided a third iteration
+                     lookahead_depth3_replays=look.depth3_replays if look else 0,
+                     lookahead_third=look.lookahead_third if look else 0)
         return dict(**extra, acceptance_rate=acceptance_rate, tokens_per_s=self.n / seconds, tokens=self.emitted, n=self.n,
                     counts=self.counts, accepted=self.accepted_count, drafted=self.draft_count,
                     avg_tokens=acceptance_rate * self.gamma, resampled=self.resample_count,

@@ -315,40 +315,82 @@ class _InnerGraphs:
 
                 self.look[n], self.look_p[n] = _capture(run2, (), self.pool, 2)
             self.break_even = self._measure_break_even(rng)
+        # The DEPTH-3 form of position n <= gamma - 5: section 24's step applied once more.  Five draft steps
+        # (draws with offsets 0, 3, 6; coupled guesses of the two follow-ups with offsets 2 and 5) fill rows n + 1 .. n + 5 of the
+        # verify block, and tf_middle_accept_n_cur decides positions n, n + 2 and n + 4 from the one verify while every guess
+        # holds.  The depth-2 and plain graphs stay for the positions and refill cases depth 3 does not fit.
+        self.look3, self.look3_p = {}, {}
+        self.break_even3 = None                                # (depth-3 replay - depth-2 replay) / plain replay, measured below
+        if self.look and _InnerGraphs.lookahead_depth(gamma, record) >= 3:
+            for n in range(gamma - 4):
+                def run3(n=n):
+                    qs = []
+                    for k, off in enumerate((0, 2, 3, 5, 6)):          # draft(n + k) -> tok[n + k + 1] with u[c + off]
+                        q = eng.draft_run(input_ids=ge.tok_buf[:, :n + k + 1], gamma_offset=n + k, **kw)
+                        ops.sample_inverse_cdf_cur(q, rng.buf, rng.cursor, off, flat[n + k + 1:n + k + 2])
+                        qs.append(q)
+                    p = eng.model_verify(input_ids=ge.tok_buf[:, :gamma + 1], position_ids=ge.pos_buf, **kw)
+                    ops.middle_accept_n_cur(p, qs[0::2], flat, rng.buf, rng.cursor, n, gamma, record, depth=3)
+                    return p
+
+                self.look3[n], self.look3_p[n] = _capture(run3, (), self.pool, 2)
+            self.break_even3 = self._measure_break_even3(rng)
         torch.cuda.synchronize()
         rng.device_cursor = False                              # the warm-up passes advanced the device copy
+
+    @staticmethod
+    def lookahead_depth(gamma, record):
+        """The deepest lookahead form to capture: TRIFORCE_INNER_LOOKAHEAD_DEPTH (default 3; 2 = the depth-2 form alone), as
+        far as the record's room and gamma allow."""
+        if not _InnerGraphs.lookahead_wanted(gamma, record):
+            return 1
+        cap = int(os.environ.get("TRIFORCE_INNER_LOOKAHEAD_DEPTH", "3"))
+        return 3 if (cap >= 3 and record.numel() >= ops.MID3_RECORD and gamma >= 5) else 2
 
     @staticmethod
     def lookahead_wanted(gamma, record):
         return os.environ.get("TRIFORCE_INNER_LOOKAHEAD", "1") != "0" and record.numel() >= ops.MID2_RECORD and gamma >= 3
 
+    @staticmethod
+    def _timed(graph, rng, reps):
+        rng.cursor.fill_(0)
+        graph.replay()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(reps):
+            graph.replay()
+        e.record()
+        e.synchronize()
+        return s.elapsed_time(e) / reps
+
     def _measure_break_even(self, rng, reps=3):
         """Replay time of the plain and the lookahead graph of position 0 over the scratch state of the warm-up passes (zero
         tokens, the caches as capture left them; a replay's cost does not depend on them) -> the skip probability above
         which the lookahead form pays."""
-        def timed(graph):
-            rng.cursor.fill_(0)
-            graph.replay()
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            for _ in range(reps):
-                graph.replay()
-            e.record()
-            e.synchronize()
-            return s.elapsed_time(e) / reps
+        timed = lambda graph: self._timed(graph, rng, reps)
         self.plain_ms, self.look_ms = timed(self.graphs[0]), timed(self.look[0])
         return max(0.0, (self.look_ms - self.plain_ms) / self.plain_ms)
+
+    def _measure_break_even3(self, rng, reps=3):
+        """The marginal cost of depth 3 over depth 2 at position 0, as a fraction of a plain replay: the rate of third
+        decisions per depth-3 replay above which depth 3 pays (a third decision saves about one plain replay)."""
+        timed = lambda graph: self._timed(graph, rng, reps)
+        plain_ms, look_ms, self.look3_ms = timed(self.graphs[0]), timed(self.look[0]), timed(self.look3[0])
+        return max(0.0, (self.look3_ms - look_ms) / plain_ms)
 
     @staticmethod
     def key_of(ge, gamma, rng, record):
         return (gamma, id(rng), rng.buf.data_ptr(), rng.cursor.data_ptr(), record.data_ptr(), ge.tok_buf.data_ptr(),
                 id(ge.engine.kv_cache), id(ge.engine.graph_cache), id(ge.engine.draft_cache),
-                _InnerGraphs.lookahead_wanted(gamma, record))
+                _InnerGraphs.lookahead_depth(gamma, record))
 
     def replay(self, n, lookahead=False):
-        (self.look[n] if lookahead else self.graphs[n]).replay()
+        """Replay the graph of position n: the plain one, or the lookahead form of depth `lookahead` (True = 2)."""
+        depth = 2 if lookahead is True else max(1, int(lookahead))
+        graph, p = ((self.graphs, self.p), (self.look, self.look_p), (self.look3, self.look3_p))[depth - 1]
+        graph[n].replay()
         self.generation += 1
-        return self.look_p[n] if lookahead else self.p[n]
+        return p[n]
 
 
 def draft_run_capture_graph(engine: InferenceEngine, gamma_offset: int = 0, mempool=None, n_warmups: int = 3, probs=False,
