@@ -276,42 +276,53 @@ class _M:
         self.config, self.device = config, torch.device(DEV)
 
 
+@pytest.mark.parametrize("rc_fp8", [False, True], ids=["fp16rc", "fp8rc"])
 @pytest.mark.parametrize("kv_fp8", [False, True], ids=["fp16kv", "fp8kv"])
-def test_tail_plan_replays_after_seq_len_advanced(kv_fp8):
-    """RetrievalCache.update_graph_cache over a resident full cache: one launch plan, replayed as the tail grows; and the
-    single-layer refresh of a rebuild, which takes the unplanned call."""
+def test_tail_plan_replays_after_seq_len_advanced(kv_fp8, rc_fp8):
+    """RetrievalCache.update_graph_cache over a resident full cache, all four (full tier, retrieval tier) pairs: one launch
+    plan, replayed as the tail grows (codes -> fp16 rows has no plan: values only); and the single-layer refresh of a rebuild,
+    which takes the unplanned call.  An fp16 retrieval cache holds the full cache's fp16 rows, or the deq of its codes, bit for
+    bit; an FP8 one the full cache's codes, or the quantizer's host restatement of its fp16 rows."""
     from triforce_amd.models.cache import FlashSimpleCache, RetrievalCache
     ops = _ops()
     L, H, P, B = 3, 2, 64, 32
     m = _M(L, H)
     kv = FlashSimpleCache(m, P + B, kv_dtype="fp8" if kv_fp8 else "fp16")
-    rc = RetrievalCache(m, max_budget=B, prefill=P, chunk_size=8, gamma=6, kv_dtype="fp8")
+    rc = RetrievalCache(m, max_budget=B, prefill=P, chunk_size=8, gamma=6, kv_dtype="fp8" if rc_fp8 else "fp16")
     k, v = _planes((L, H, P + B, D), seed=70)
     if kv_fp8:
         for l in range(L):
             ops.kv_quant_rows(k[l], v[l], *kv.layer_codes(l), 0)
-        want = (kv.kc, kv.vc, kv.ke, kv.ve)
     else:
         kv.k.copy_(k)
         kv.v.copy_(v)
+    if not rc_fp8 and kv_fp8:                                        # rows [0, P + 31) of kv.dequantize(l, P + 31), per layer
+        deq = [kv.dequantize(l, P + 31) for l in range(L)]
+        want = tuple(torch.stack([d[i] for d in deq]) for i in range(2))
+    elif not rc_fp8:
+        want = (kv.k, kv.v)
+    elif kv_fp8:
+        want = (kv.kc, kv.vc, kv.ke, kv.ve)
+    else:
         want = (*ops.kv_quantize_ref(k)[:2], *ops.kv_quantize_ref(v)[:2])
         want = (want[0], want[2], want[1], want[3])
+    held = (rc.kc, rc.vc, rc.ke, rc.ve) if rc_fp8 else (rc.k[:, :, :B], rc.v[:, :, :B])
     plans = []
     for g in (5, 12, 31):
         kv.seq_len = P + g
         rc.update_graph_cache(kv)
         torch.cuda.synchronize()
-        plans.append(rc._tail_plan[1])
-        for got, w in zip((rc.kc, rc.vc, rc.ke, rc.ve), want):
+        plans.append(rc._tail_plan[1] if rc_fp8 or not kv_fp8 else None)
+        for got, w in zip(held, want):
             assert torch.equal(_bits(got[:, :, B - g:]), _bits(w[:, :, P:P + g])), g
-    assert plans[0] is plans[1] is plans[2]
-    assert int(_bits(rc.kc[:, :, 0]).max()) == 0                     # row 0: never in a tail of <= 31 rows
+    assert plans[0] is plans[1] is plans[2] and (plans[0] is None) == (kv_fp8 and not rc_fp8)
+    assert int(_bits(held[0][:, :, 0]).max()) == 0                   # row 0: never in a tail of <= 31 rows
     rc.reset()
     kv.seq_len = P + 7
     rc._copy_tail(kv, slice(1, 2))
     torch.cuda.synchronize()
-    assert torch.equal(_bits(rc.kc[1, :, B - 7:]), _bits(want[0][1, :, P:P + 7]))
-    assert int(_bits(rc.kc[0]).max()) == 0 and int(_bits(rc.kc[2]).max()) == 0
+    assert torch.equal(_bits(held[0][1, :, B - 7:]), _bits(want[0][1, :, P:P + 7]))
+    assert int(_bits(held[0][0]).max()) == 0 and int(_bits(held[0][2]).max()) == 0
     kv.seq_len = P + B + 1
     with pytest.raises(IndexError, match="retrieval budget"):
         rc.update_graph_cache(kv)

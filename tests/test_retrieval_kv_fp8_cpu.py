@@ -269,3 +269,74 @@ def test_wrappers_refuse_host_tensors():
     with pytest.raises(hip.TriforceHipError):
         ops.kv_quant_rows_pair(rows.unsqueeze(0), rows.unsqueeze(0), kc.unsqueeze(0), kc.unsqueeze(0), ke.unsqueeze(0),
                                ke.unsqueeze(0), 0, 0, 4)
+
+
+# ---- the tail refresh's launches -----------------------------------------------------------------------------------------
+def test_tail_refresh_launches_for_the_four_tier_pairs(monkeypatch):
+    """RetrievalCache._copy_tail over (full tier, retrieval tier): which wrapper it calls, with which rows and which storage.
+    Host tensors: nothing is planned, every refresh is one recorded call."""
+    from triforce_amd.models import cache as C
+    L, H, B, P, T = 3, 2, 32, 64, 96
+
+    class M(_Model):
+        class config(_Cfg):
+            num_key_value_heads = num_attention_heads = H
+            hidden_size = H * 128
+            num_hidden_layers = L
+
+    calls = []
+
+    def copy(src_k, src_v, dst_k, dst_v, src_t0, dst_t0, n):
+        calls.append(("copy", (src_k, src_v), None, (dst_k, dst_v), src_t0, dst_t0, n))
+
+    def dequant(src_k, src_v, exp_k, exp_v, dst_k, dst_v, src_t0, dst_t0, n):
+        calls.append(("dequant", (src_k, src_v), (exp_k, exp_v), (dst_k, dst_v), src_t0, dst_t0, n))
+
+    def quant(src_k, src_v, dst_kc, dst_vc, dst_ke, dst_ve, src_t0, dst_t0, n, src_exp=None):
+        calls.append(("quant", (src_k, src_v), src_exp, (dst_kc, dst_vc, dst_ke, dst_ve), src_t0, dst_t0, n))
+
+    monkeypatch.setattr(C.ops, "kv_copy_rows_pair", copy)
+    monkeypatch.setattr(C.ops, "kv_dequant_rows_pair", dequant)
+    monkeypatch.setattr(C.ops, "kv_quant_rows_pair", quant)
+    operation = {("fp16", "fp16"): "copy", ("fp8", "fp16"): "dequant", ("fp16", "fp8"): "quant", ("fp8", "fp8"): "quant"}
+
+    def ptrs(ts):
+        return [t.data_ptr() for t in ts]
+
+    for full, tier in operation:
+        kv = C.FlashSimpleCache(M(), T, kv_dtype=full)
+        rc = C.RetrievalCache(M(), max_budget=B, prefill=P, chunk_size=8, gamma=6, kv_dtype=tier)
+        src_all = (kv.kc, kv.vc) if full == "fp8" else (kv.k, kv.v)
+        exp_all = (kv.ke, kv.ve) if full == "fp8" else None
+        dst_all = (rc.kc, rc.vc, rc.ke, rc.ve) if tier == "fp8" else (rc.k, rc.v)
+        for g in (5, 31):
+            kv.seq_len = P + g
+            for layers, refresh in ((slice(0, L), lambda: rc.update_graph_cache(kv)),
+                                    (slice(1, 2), lambda: rc._copy_tail(kv, slice(1, 2)))):
+                del calls[:]
+                refresh()
+                assert len(calls) == 1, (full, tier, g, layers)
+                op, src, src_exp, dst, src_t0, dst_t0, n = calls[0]
+                assert op == operation[full, tier], (full, tier)
+                assert (src_t0, dst_t0, n) == (P, B - g, g), (full, tier, g)
+                assert ptrs(src) == ptrs(t[layers] for t in src_all) and all(t.shape[0] == layers.stop - layers.start for t in src)
+                assert ptrs(dst) == ptrs(t[layers] for t in dst_all) and all(t.shape[0] == layers.stop - layers.start for t in dst)
+                assert (src_exp is None) == (exp_all is None), (full, tier)
+                if exp_all is not None:
+                    assert ptrs(src_exp) == ptrs(t[layers] for t in exp_all)
+                    assert all(t.shape[0] == layers.stop - layers.start for t in src_exp)
+        kv.seq_len = P + B + 1
+        del calls[:]
+        with pytest.raises(IndexError, match="retrieval budget"):
+            rc.update_graph_cache(kv)
+        with pytest.raises(IndexError, match="retrieval budget"):
+            rc._copy_tail(kv, slice(1, 2))
+        assert not calls
+
+    # an FP8 full cache says what its rows are: codes, with their exponent bytes
+    kv = C.FlashSimpleCache(M(), T, kv_dtype="fp8")
+    k, v, first_row, exp = kv.tail_source(slice(1, 3), P)
+    assert first_row == P and ptrs((k, v, *exp)) == ptrs((kv.kc[1:3], kv.vc[1:3], kv.ke[1:3], kv.ve[1:3]))
+    assert k.dtype == torch.float8_e4m3fn and exp[0].dtype == torch.uint8 and k.shape[0] == exp[0].shape[0] == 2
+    k, v, first_row, exp = C.FlashSimpleCache(M(), T, kv_dtype="fp16").tail_source(slice(1, 3), P)
+    assert exp is None and first_row == P and k.dtype == torch.float16 and k.shape[0] == 2

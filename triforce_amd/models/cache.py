@@ -26,14 +26,7 @@ KV_CACHE_ENV = "TRIFORCE_KV_CACHE"
 
 def kv_cache_dtype(override=None):
     """"fp16" or "fp8": ``override`` if given, else TRIFORCE_KV_CACHE.  fp8 needs the fused decode layer (TRIFORCE_FUSE=all)."""
-    v = override if override is not None else os.environ.get(KV_CACHE_ENV, "fp16")
-    v = str(v).strip().lower() or "fp16"
-    if v not in ("fp16", "fp8"):
-        raise ValueError(f"{KV_CACHE_ENV}={v!r}: expected fp16 or fp8")
-    if v == "fp8" and ops.FUSE_MODE != "all":
-        raise ValueError(f"{KV_CACHE_ENV}=fp8 needs the fused decode layer (TRIFORCE_FUSE=all, got {ops.FUSE_MODE!r}): "
-                         "the FP8 attention exists only in that form")
-    return v
+    return ops.fp16_or_fp8(KV_CACHE_ENV, override, "the FP8 attention exists only in that form")
 
 
 # TRIFORCE_RETRIEVAL_INDEX=1: RetrievalCache keeps the fp16 chunk means of the covered region (csrc/retrieval.hip "chunk-mean
@@ -60,30 +53,27 @@ RETRIEVAL_KV_ENV = "TRIFORCE_RETRIEVAL_KV"
 
 def retrieval_kv_dtype(override=None):
     """"fp16" or "fp8": ``override`` if given, else TRIFORCE_RETRIEVAL_KV.  fp8 needs the fused decode layer (TRIFORCE_FUSE=all)."""
-    v = override if override is not None else os.environ.get(RETRIEVAL_KV_ENV, "fp16")
-    v = str(v).strip().lower() or "fp16"
-    if v not in ("fp16", "fp8"):
-        raise ValueError(f"{RETRIEVAL_KV_ENV}={v!r}: expected fp16 or fp8")
-    if v == "fp8" and ops.FUSE_MODE != "all":
-        raise ValueError(f"{RETRIEVAL_KV_ENV}=fp8 needs the fused decode layer (TRIFORCE_FUSE=all, got {ops.FUSE_MODE!r}): "
-                         "the attention over codes + fp16 spec rows exists only in that form")
-    return v
+    return ops.fp16_or_fp8(RETRIEVAL_KV_ENV, override, "the attention over codes + fp16 spec rows exists only in that form")
+
+
+def _refuse_tier(dtype, env, home, what):
+    """The caches without an FP8 form: refuse the knob instead of ignoring it.  ``home``: the one cache that implements it."""
+    if dtype() == "fp8":
+        raise NotImplementedError(f"{env}=fp8 is implemented for the single-GPU {home} only, not for {what}")
 
 
 def _refuse_retrieval_fp8(what):
-    if retrieval_kv_dtype() == "fp8":
-        raise NotImplementedError(f"{RETRIEVAL_KV_ENV}=fp8 is implemented for the single-GPU retrieval cache (RetrievalCache) "
-                                  f"only, not for {what}")
+    _refuse_tier(retrieval_kv_dtype, RETRIEVAL_KV_ENV, "retrieval cache (RetrievalCache)", what)
 
 
 def _refuse_fp8(what):
-    if kv_cache_dtype() == "fp8":
-        raise NotImplementedError(f"{KV_CACHE_ENV}=fp8 is implemented for the single-GPU resident cache (FlashSimpleCache) "
-                                  f"only, not for {what}")
+    _refuse_tier(kv_cache_dtype, KV_CACHE_ENV, "resident cache (FlashSimpleCache)", what)
 
 
 class Cache:
     """Base class (reference models/cache.py:6-17)."""
+
+    fp8 = False                                       # True: the rows are FP8 codes (CodedRows), there is no .k / .v
 
     def update(self, key_states, value_states, layer_idx) -> Tuple[torch.Tensor, torch.Tensor]:
         raise NotImplementedError("Make sure to implement `update` in a subclass.")
@@ -116,6 +106,60 @@ def _rows(x):
     return x[0] if x.dim() == 4 else x
 
 
+class CodedRows:
+    """K / V rows in the FP8 row format (include/triforce_hip.h "FP8 KV CACHE"), the one place that spells it out: e4m3fn codes
+    ``kc`` / ``vc`` [L][H][T][D] and one exponent byte per row ``ke`` / ``ve`` [L][H][T]; an empty row is zero codes under
+    the smallest exponent.  The caches that hold one bind the four tensors under the same names."""
+
+    def __init__(self, L, H, T, D, device, knob):
+        if D != 128:                                  # the kernels over codes exist for this width only
+            raise NotImplementedError(f"{knob}=fp8 needs head_dim 128 (got {D}): the FP8 row format and its attention are "
+                                      "built for that width")
+        self.kc = torch.zeros(L, H, T, D, dtype=torch.float8_e4m3fn, device=device)
+        self.vc = torch.zeros(L, H, T, D, dtype=torch.float8_e4m3fn, device=device)
+        self.ke = torch.full((L, H, T), ops.KV_FP8_EMIN + 127, dtype=torch.uint8, device=device)
+        self.ve = torch.full((L, H, T), ops.KV_FP8_EMIN + 127, dtype=torch.uint8, device=device)
+
+    def nbytes(self):
+        return self.kc.nbytes + self.vc.nbytes + self.ke.nbytes + self.ve.nbytes
+
+    def reset(self):
+        for codes, exp in ((self.kc, self.ke), (self.vc, self.ve)):
+            codes.view(torch.uint8).zero_()
+            exp.fill_(ops.KV_FP8_EMIN + 127)
+
+    def layer(self, i):
+        """(k codes, v codes, k exponents, v exponents) views of layer ``i``, (H,T,D) and (H,T); of a slice of layers (the
+        same indexing under the name ``layers``), (n,H,T,D) and (n,H,T)."""
+        return self.kc[i], self.vc[i], self.ke[i], self.ve[i]
+
+    layers = layer
+
+    def dequant_into(self, layers, k_out, v_out, src_t0, dst_t0, n):
+        """Rows [dst_t0, dst_t0 + n) of the fp16 views k_out / v_out (n layers,H,T',D) = deq of rows [src_t0, src_t0 + n)."""
+        ops.kv_dequant_rows_pair(*self.layers(layers), k_out, v_out, src_t0, dst_t0, n)
+
+
+def _refuse_k_v(cls, knob, use):
+    """The __getattr__ of a cache class that may hold codes (only reached for missing attributes): .k / .v of an FP8 cache, fp16
+    storage that does not exist, get an explanation instead of a bare name."""
+    def __getattr__(self, name):
+        if name in ("k", "v") and self.fp8:
+            raise AttributeError(f"{cls}.{name}: the cache holds FP8 codes ({knob}=fp8), there is no fp16 storage to index; "
+                                 f"use {use} or dequantize(layer)")
+        raise AttributeError(name)
+    return __getattr__
+
+
+def _hold_coded_rows(cache, T, knob):
+    """Give ``cache`` a CodedRows of T rows per head as ``coded``, the store's tensors under their own names (plain attributes:
+    the forward reads them every layer), the reference-shaped views of the codes, and ``fp8``."""
+    c = cache.coded = CodedRows(cache.layers, cache.num_heads, T, cache.head_dim, cache.device, knob)
+    cache.kc, cache.vc, cache.ke, cache.ve = c.kc, c.vc, c.ke, c.ve
+    cache.key_cache, cache.value_cache = _ref_view(c.kc), _ref_view(c.vc)
+    cache.fp8 = True
+
+
 class FlashSimpleCache(Cache):
     """Full KV cache of the target model (reference cache.py:20-61).
 
@@ -123,8 +167,6 @@ class FlashSimpleCache(Cache):
     ``ve`` [L][H][T]; ``.k`` / ``.v`` do not exist then.  Fresh decode-sized rows pass through the fp16 staging ``stage_k`` /
     ``stage_v`` [H][32][D]; prefill chunks and the retrieval build read one dequantized layer in ``scratch_k`` / ``scratch_v``
     [H][T][D]."""
-
-    fp8 = False
 
     def __init__(self, model, max_budget=1024, kv_dtype=None) -> None:
         self.seq_len = 0
@@ -135,39 +177,23 @@ class FlashSimpleCache(Cache):
         self.scores = []
         if kv_cache_dtype(kv_dtype) == "fp8":
             _refuse_gqa(model.config, f"{KV_CACHE_ENV}=fp8 (the FP8 KV cache)")
-            self._init_fp8()
+            H, T, D = self.num_heads, max_budget, self.head_dim
+            _hold_coded_rows(self, T, KV_CACHE_ENV)
+            self.stage_k = torch.zeros(H, ops.SKINNY_MAX_ROWS, D, dtype=torch.float16, device=self.device)
+            self.stage_v = torch.zeros(H, ops.SKINNY_MAX_ROWS, D, dtype=torch.float16, device=self.device)
+            self.scratch_k = torch.zeros(H, T, D, dtype=torch.float16, device=self.device)
+            self.scratch_v = torch.zeros(H, T, D, dtype=torch.float16, device=self.device)
             return
         self.k, self.v = _alloc(self.layers, self.num_heads, max_budget, self.head_dim, self.device)
         self.key_cache, self.value_cache = _ref_view(self.k), _ref_view(self.v)
 
-    def _init_fp8(self):
-        L, H, T, D = self.layers, self.num_heads, self.max_budget, self.head_dim
-        assert D == 128, f"{KV_CACHE_ENV}=fp8 needs head_dim 128 (got {D})"
-        self.fp8 = True
-        f8 = torch.float8_e4m3fn
-        self.kc = torch.zeros(L, H, T, D, dtype=f8, device=self.device)
-        self.vc = torch.zeros(L, H, T, D, dtype=f8, device=self.device)
-        self.ke = torch.full((L, H, T), ops.KV_FP8_EMIN + 127, dtype=torch.uint8, device=self.device)
-        self.ve = torch.full((L, H, T), ops.KV_FP8_EMIN + 127, dtype=torch.uint8, device=self.device)
-        self.stage_k = torch.zeros(H, ops.SKINNY_MAX_ROWS, D, dtype=torch.float16, device=self.device)
-        self.stage_v = torch.zeros(H, ops.SKINNY_MAX_ROWS, D, dtype=torch.float16, device=self.device)
-        self.scratch_k = torch.zeros(H, T, D, dtype=torch.float16, device=self.device)
-        self.scratch_v = torch.zeros(H, T, D, dtype=torch.float16, device=self.device)
-        self.key_cache, self.value_cache = _ref_view(self.kc), _ref_view(self.vc)
-
-    def __getattr__(self, name):
-        # only reached for missing attributes: .k / .v of an FP8 cache (fp16 storage that does not exist)
-        if name in ("k", "v") and self.__dict__.get("fp8", False):
-            raise AttributeError(f"FlashSimpleCache.{name}: the cache holds FP8 codes ({KV_CACHE_ENV}=fp8), there is no fp16 "
-                                 f"storage to index; use kc / vc / ke / ve or dequantize(layer)")
-        raise AttributeError(name)
+    __getattr__ = _refuse_k_v("FlashSimpleCache", KV_CACHE_ENV, "kc / vc / ke / ve")
 
     def nbytes(self):
         """Device bytes of the cache storage (FP8: codes, exponents, staging and layer scratch)."""
         if not self.fp8:
             return self.k.nbytes + self.v.nbytes
-        return sum(t.nbytes for t in (self.kc, self.vc, self.ke, self.ve, self.stage_k, self.stage_v, self.scratch_k,
-                                      self.scratch_v))
+        return self.coded.nbytes() + sum(t.nbytes for t in (self.stage_k, self.stage_v, self.scratch_k, self.scratch_v))
 
     def dequantize(self, layer, rows=None):
         """(k, v): fresh (H, rows, D) fp16 tensors of deq(K), deq(V) of ``layer``, rows [0, rows) (default seq_len)."""
@@ -177,19 +203,17 @@ class FlashSimpleCache(Cache):
         H, D = self.num_heads, self.head_dim
         k = torch.empty(1, H, n, D, dtype=torch.float16, device=self.device)
         v = torch.empty_like(k)
-        ops.kv_dequant_rows_pair(self.kc[layer:layer + 1], self.vc[layer:layer + 1], self.ke[layer:layer + 1],
-                                 self.ve[layer:layer + 1], k, v, 0, 0, n)
+        self.coded.dequant_into(slice(layer, layer + 1), k, v, 0, 0, n)
         return k[0], v[0]
 
     def scratch_layer(self, layer, rows):
         """FP8: dequantize rows [0, rows) of ``layer`` into the layer scratch and return its (H,T,D) views."""
-        ops.kv_dequant_rows_pair(self.kc[layer:layer + 1], self.vc[layer:layer + 1], self.ke[layer:layer + 1],
-                                 self.ve[layer:layer + 1], self.scratch_k.unsqueeze(0), self.scratch_v.unsqueeze(0), 0, 0, rows)
+        self.coded.dequant_into(slice(layer, layer + 1), self.scratch_k.unsqueeze(0), self.scratch_v.unsqueeze(0), 0, 0, rows)
         return self.scratch_k, self.scratch_v
 
     def layer_codes(self, layer):
         """FP8: (k codes, v codes, k exponents, v exponents) of ``layer``: (H,T,D) and (H,T) views."""
-        return self.kc[layer], self.vc[layer], self.ke[layer], self.ve[layer]
+        return self.coded.layer(layer)
 
     def print_status(self):
         print("[Full Cache] Cached:", self.seq_len, "| Budget:", self.max_budget)
@@ -197,10 +221,7 @@ class FlashSimpleCache(Cache):
     def reset(self):
         self.seq_len = 0
         if self.fp8:
-            for t in (self.kc, self.vc):
-                t.view(torch.uint8).zero_()
-            self.ke.fill_(ops.KV_FP8_EMIN + 127)
-            self.ve.fill_(ops.KV_FP8_EMIN + 127)
+            self.coded.reset()
             return
         self.k.zero_()
         self.v.zero_()
@@ -211,8 +232,11 @@ class FlashSimpleCache(Cache):
         return self.k[layer_idx], self.v[layer_idx]
 
     def tail_source(self, layers, prefill):
-        """(k, v, first_row) holding the generated-token rows [prefill, seq_len) of `layers` on the device."""
-        return self.k[layers], self.v[layers], prefill
+        """(k, v, first_row, exp) holding the generated-token rows [prefill, seq_len) of `layers` on the device: fp16 rows and
+        ``exp`` None, or codes and ``exp`` = their (k, v) exponent bytes."""
+        if self.fp8:
+            return self.kc[layers], self.vc[layers], prefill, (self.ke[layers], self.ve[layers])
+        return self.k[layers], self.v[layers], prefill, None
 
     def append_slot(self, layer_idx, n):
         """Slot where the fused RoPE+append kernel writes this layer's n new rows; seq_len advances
@@ -290,7 +314,7 @@ class OffloadingFlashSimpleCache(Cache):
 
     def tail_source(self, layers, prefill):
         assert self.tail_base == prefill, "OffloadingFlashSimpleCache.set_tail(prefill, capacity) must be called first"
-        return self.tail_k[layers], self.tail_v[layers], 0
+        return self.tail_k[layers], self.tail_v[layers], 0, None
 
     # -- streaming protocol driven by the model forward ---------------------------------------
     def _fetch(self, layer_idx):
@@ -350,7 +374,7 @@ class RetrievalCache(Cache):
     an FP8 full cache, quantized from an fp16 one); the gamma + 1 rows of a spec forward stay fp16 in ``spec_k`` / ``spec_v``
     [L][H][gamma + 1][D]; ``.k`` / ``.v`` do not exist then."""
 
-    fp8 = False
+    _tail_plan = None                                 # (source key, launch plan, source first row) of the per-step refresh
 
     def __init__(self, model, max_budget=1024, prefill=1024, chunk_size=8, gamma=6, index=None, kv_dtype=None) -> None:
         self.chunk_size = chunk_size
@@ -368,7 +392,8 @@ class RetrievalCache(Cache):
         self.q_heads = model.config.num_attention_heads       # > num_heads: grouped-query, selection per KV head
         if retrieval_kv_dtype(kv_dtype) == "fp8":
             _refuse_gqa(model.config, f"{RETRIEVAL_KV_ENV}=fp8 (the FP8 retrieval cache)")
-            self._init_fp8()
+            _hold_coded_rows(self, max_budget, RETRIEVAL_KV_ENV)
+            self.spec_k, self.spec_v = _alloc(self.layers, self.num_heads, gamma + 1, self.head_dim, self.device)
         else:
             self.k, self.v = _alloc(self.layers, self.num_heads, self.real_budget, self.head_dim, self.device)
             self.key_cache, self.value_cache = _ref_view(self.k), _ref_view(self.v)
@@ -378,32 +403,13 @@ class RetrievalCache(Cache):
         self.use_index = retrieval_index(index)
         self.index, self.indexed_chunks = None, [0] * self.layers
 
-    def _init_fp8(self):
-        L, H, T, D = self.layers, self.num_heads, self.max_budget, self.head_dim
-        if D != 128:
-            raise NotImplementedError(f"{RETRIEVAL_KV_ENV}=fp8 needs head_dim 128 (got {D}): the FP8 row format and its "
-                                      "attention are built for that width")
-        self.fp8 = True
-        f8 = torch.float8_e4m3fn
-        self.kc = torch.zeros(L, H, T, D, dtype=f8, device=self.device)
-        self.vc = torch.zeros(L, H, T, D, dtype=f8, device=self.device)
-        self.ke = torch.full((L, H, T), ops.KV_FP8_EMIN + 127, dtype=torch.uint8, device=self.device)
-        self.ve = torch.full((L, H, T), ops.KV_FP8_EMIN + 127, dtype=torch.uint8, device=self.device)
-        self.spec_k, self.spec_v = _alloc(L, H, self.gamma + 1, D, self.device)
-        self.key_cache, self.value_cache = _ref_view(self.kc), _ref_view(self.vc)
-
-    def __getattr__(self, name):
-        # only reached for missing attributes: .k / .v of an FP8 retrieval cache (fp16 storage that does not exist)
-        if name in ("k", "v") and self.__dict__.get("fp8", False):
-            raise AttributeError(f"RetrievalCache.{name}: the cache holds FP8 codes ({RETRIEVAL_KV_ENV}=fp8), there is no fp16 "
-                                 f"storage to index; use kc / vc / ke / ve, spec_k / spec_v or dequantize(layer)")
-        raise AttributeError(name)
+    __getattr__ = _refuse_k_v("RetrievalCache", RETRIEVAL_KV_ENV, "kc / vc / ke / ve, spec_k / spec_v")
 
     def nbytes(self):
         """Device bytes of the K / V storage (FP8: codes, exponents and the fp16 spec rows)."""
         if not self.fp8:
             return self.k.nbytes + self.v.nbytes
-        return sum(t.nbytes for t in (self.kc, self.vc, self.ke, self.ve, self.spec_k, self.spec_v))
+        return self.coded.nbytes() + self.spec_k.nbytes + self.spec_v.nbytes
 
     def dequantize(self, layer):
         """(k, v): fresh (H, real_budget, D) fp16 tensors of what the spec forward's attention reads in ``layer``: deq of the
@@ -413,14 +419,13 @@ class RetrievalCache(Cache):
         H, D, B = self.num_heads, self.head_dim, self.max_budget
         k = torch.empty(1, H, self.real_budget, D, dtype=torch.float16, device=self.device)
         v = torch.empty_like(k)
-        ops.kv_dequant_rows_pair(self.kc[layer:layer + 1], self.vc[layer:layer + 1], self.ke[layer:layer + 1],
-                                 self.ve[layer:layer + 1], k, v, 0, 0, B)
+        self.coded.dequant_into(slice(layer, layer + 1), k, v, 0, 0, B)
         k[0, :, B:], v[0, :, B:] = self.spec_k[layer], self.spec_v[layer]
         return k[0], v[0]
 
     def layer_codes(self, layer):
         """FP8: (k codes, v codes, k exponents, v exponents) of ``layer``: (H,max_budget,D) and (H,max_budget) views."""
-        return self.kc[layer], self.vc[layer], self.ke[layer], self.ve[layer]
+        return self.coded.layer(layer)
 
     def reanchor(self, new_prefill):
         """Move the covered region to rows [0, new_prefill): the tail then starts there.  Moves no data — the caller follows
@@ -465,7 +470,7 @@ class RetrievalCache(Cache):
         assert 1 == q.shape[0], "query_states should be 1 for init"
         # grouped-query: one selection per KV head from the group's mean query; multi-head: q itself
         q = ops.group_mean_query(q[0], self.num_heads).unsqueeze(0)
-        if getattr(kv_cache, "fp8", False):           # FP8 cache: score / select / gather over the dequantized prefill rows
+        if kv_cache.fp8:                              # FP8 cache: score / select / gather over the dequantized prefill rows
             src_k, src_v = kv_cache.scratch_layer(layer_idx, self.prefill)
         else:
             src_k, src_v = kv_cache.layer_kv(layer_idx)
@@ -481,7 +486,7 @@ class RetrievalCache(Cache):
         idx = ops.retrieval_topk(scores, self.select_sets)
         if not self.fp8:
             ops.retrieval_gather(src_k, src_v, idx, self.k[layer_idx], self.v[layer_idx], self.chunk_size)
-        elif getattr(kv_cache, "fp8", False):         # codes -> codes: the middle tier reads the deq the target reads
+        elif kv_cache.fp8:                            # codes -> codes: the middle tier reads the deq the target reads
             kc, vc, ke, ve = kv_cache.layer_codes(layer_idx)
             ops.retrieval_gather_fp8(kc, vc, idx, *self.layer_codes(layer_idx), self.chunk_size, src_exp=(ke, ve))
         else:
@@ -490,47 +495,40 @@ class RetrievalCache(Cache):
         if layer_idx == self.layers - 1:
             self.init_graph = True
 
-    def _copy_tail_fp8(self, kv_cache, layers, g):
-        """The tail refresh into codes: copied from an FP8 full cache, quantized from fp16 rows."""
-        dst = (self.kc[layers], self.vc[layers], self.ke[layers], self.ve[layers])
-        if getattr(kv_cache, "fp8", False):
-            src = (kv_cache.kc[layers], kv_cache.vc[layers])
-            src_exp, t0 = (kv_cache.ke[layers], kv_cache.ve[layers]), self.prefill
-        else:
-            src_k, src_v, t0 = kv_cache.tail_source(layers, self.prefill)
-            src, src_exp = (src_k, src_v), None
-        if layers == slice(0, self.layers) and self.kc.is_cuda and type(kv_cache) is FlashSimpleCache:
-            # the per-step refresh over the resident cache: fixed tensors -> a launch plan, as in _copy_tail
-            key = (id(kv_cache), src[0].data_ptr())
-            plan = getattr(self, "_tail_plan", None)
-            if plan is None or plan[0] != key:
-                plan = self._tail_plan = (key, ops.KvQuantPairPlan(*src, *dst, src_exp=src_exp), t0)
-            plan[1](plan[2], self.max_budget - g, g)
-            return
-        ops.kv_quant_rows_pair(*src, *dst, t0, self.max_budget - g, g, src_exp=src_exp)
-
     def _copy_tail(self, kv_cache, layers):
+        """Rows [max_budget - g, max_budget) of ``layers`` = the g generated rows of ``kv_cache``.  What the source holds
+        (tail_source) and what this cache holds select the operation:
+            fp16 rows -> fp16 rows   copied       (ops.kv_copy_rows_pair)
+            codes     -> fp16 rows   dequantized  (CodedRows.dequant_into; never planned)
+            fp16 rows -> codes       quantized    (ops.kv_quant_rows_pair)
+            codes     -> codes       copied with their exponent bytes (ops.kv_quant_rows_pair, src_exp)"""
         g = kv_cache.seq_len - self.prefill
         if g > self.max_budget:
             raise IndexError(f"generated tail ({g}) exceeds the retrieval budget ({self.max_budget})")
+        d0 = self.max_budget - g
+        # the per-step refresh over all layers: the same tensors every step -> a launch plan; only for the resident cache,
+        # whose storage never moves (the offloading cache re-allocates its tail mirror)
+        planned = layers == slice(0, self.layers) and self.key_cache.is_cuda and type(kv_cache) is FlashSimpleCache
+        if planned:
+            key, plan = (id(kv_cache), kv_cache.key_cache.data_ptr()), self._tail_plan
+            if plan is not None and plan[0] == key:
+                plan[1](plan[2], d0, g)
+                return
+        src_k, src_v, t0, src_exp = kv_cache.tail_source(layers, self.prefill)
+        if src_exp is not None and not self.fp8:
+            kv_cache.coded.dequant_into(layers, self.k[layers], self.v[layers], t0, d0, g)
+            return
         if self.fp8:
-            return self._copy_tail_fp8(kv_cache, layers, g)
-        if getattr(kv_cache, "fp8", False):           # FP8 cache: the generated rows are dequantized into the retrieval cache
-            ops.kv_dequant_rows_pair(kv_cache.kc[layers], kv_cache.vc[layers], kv_cache.ke[layers], kv_cache.ve[layers],
-                                     self.k[layers], self.v[layers], self.prefill, self.max_budget - g, g)
-            return
-        whole = layers == slice(0, self.layers)
-        if whole and self.k.is_cuda and type(kv_cache) is FlashSimpleCache:
-            # the per-step refresh over all layers: the same tensors every step -> a launch plan (ops.KvCopyPairPlan); only for
-            # the resident cache, whose storage never moves (the offloading cache re-allocates its tail mirror)
-            plan = getattr(self, "_tail_plan", None)
-            if plan is None or plan[0] != (id(kv_cache), kv_cache.k.data_ptr()):
-                src_k, src_v, t0 = kv_cache.tail_source(layers, self.prefill)
-                plan = self._tail_plan = ((id(kv_cache), kv_cache.k.data_ptr()), ops.KvCopyPairPlan(src_k, src_v, self.k, self.v), t0)
-            plan[1](plan[2], self.max_budget - g, g)
-            return
-        src_k, src_v, t0 = kv_cache.tail_source(layers, self.prefill)
-        ops.kv_copy_rows_pair(src_k, src_v, self.k[layers], self.v[layers], t0, self.max_budget - g, g)
+            dst, how = self.coded.layers(layers), {"src_exp": src_exp}
+            plan_of, run = ops.KvQuantPairPlan, ops.kv_quant_rows_pair
+        else:
+            dst, how = (self.k[layers], self.v[layers]), {}
+            plan_of, run = ops.KvCopyPairPlan, ops.kv_copy_rows_pair
+        if planned:
+            self._tail_plan = (key, plan_of(src_k, src_v, *dst, **how), t0)
+            self._tail_plan[1](t0, d0, g)
+        else:
+            run(src_k, src_v, *dst, t0, d0, g, **how)
 
     def update_graph_cache(self, kv_cache=None):
         self._copy_tail(kv_cache, slice(0, self.layers))
@@ -552,10 +550,7 @@ class RetrievalCache(Cache):
 
     def reset(self):
         if self.fp8:
-            for t in (self.kc, self.vc):
-                t.view(torch.uint8).zero_()
-            self.ke.fill_(ops.KV_FP8_EMIN + 127)
-            self.ve.fill_(ops.KV_FP8_EMIN + 127)
+            self.coded.reset()
             self.spec_k.zero_()
             self.spec_v.zero_()
         else:
@@ -730,6 +725,8 @@ class DistributedSimpleCache(Cache):
 class DistributedKVCacheBuffer:
     """Device staging buffer for one offloaded layer (reference cache.py:353-383)."""
 
+    fp8 = False                                       # fp16 rows (not a Cache subclass: says so itself)
+
     def __init__(self, config, max_budget=1024, device=None) -> None:
         self.config = config
         self.max_budget = max_budget
@@ -759,6 +756,8 @@ class DistributedRetrievalCache:
     """Per-rank retrieval cache, always in HBM (reference cache.py:485-584).  Differences from the
     single-GPU class that the reference has and we keep: reset() clears init_graph, and building twice
     without a reset raises (cache.py:519-520,577-580)."""
+
+    fp8 = False                                       # fp16 rows, also in DistributedRetrievalCache_Seqouia
 
     def __init__(self, config, max_budget=1024, device=None, prefill=1024, chunk_size=8, gamma=6) -> None:
         _refuse_retrieval_fp8("DistributedRetrievalCache (the tensor-parallel and Sequoia engines)")

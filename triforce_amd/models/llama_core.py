@@ -66,13 +66,7 @@ RETRIEVAL_WEIGHTS_ENV = "TRIFORCE_RETRIEVAL_WEIGHTS"
 def retrieval_weights():
     """TRIFORCE_RETRIEVAL_WEIGHTS: ``fp16`` (default) or ``fp8`` — the weights the target's retrieval-cache (spec) forward
     streams.  Read when a target model is built; fp8 needs the fused decode layer (TRIFORCE_FUSE=all)."""
-    v = os.environ.get(RETRIEVAL_WEIGHTS_ENV, "fp16").strip().lower() or "fp16"
-    if v not in ("fp16", "fp8"):
-        raise ValueError(f"{RETRIEVAL_WEIGHTS_ENV}={v!r}: expected fp16 or fp8")
-    if v == "fp8" and ops.FUSE_MODE != "all":
-        raise ValueError(f"{RETRIEVAL_WEIGHTS_ENV}=fp8 needs the fused decode layer (TRIFORCE_FUSE=all, got {ops.FUSE_MODE!r}): "
-                         "the FP8 kernels exist only in that form")
-    return v
+    return ops.fp16_or_fp8(RETRIEVAL_WEIGHTS_ENV, None, "the FP8 kernels exist only in that form")
 
 
 class CausalLMOutput:

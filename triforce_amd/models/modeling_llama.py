@@ -129,7 +129,7 @@ class LlamaForCausalLM:
         assert fused or dev_len is None, "the captured full-cache forward needs the fused decode kernels"
         # FP8 retrieval cache (TRIFORCE_RETRIEVAL_KV=fp8): the spec forward's attention reads codes, then the
         # fp16 rows this forward appends, in one launch
-        rkv8 = spec and getattr(graph_cache, "fp8", False)
+        rkv8 = spec and graph_cache.fp8
         if rkv8 and not fused:
             raise RuntimeError(f"the FP8 retrieval cache needs the fused decode layer ({q_len} rows)")
         # the fused layer keeps residual stream / attention output / SwiGLU output k-octet-major (ops.Act): the GEMMs' B
@@ -186,7 +186,7 @@ class LlamaForCausalLM:
         rows [0, slot).  A captured forward (dev_len) appends at a slot the device holds and is sized by the capacity."""
         if spec_cache is not None:                      # :226-227  retrieval-cache forward
             assert q_len == spec_cache.gamma + 1, "spec forward takes exactly gamma+1 tokens (cache.py:184-189)"
-            if getattr(spec_cache, "fp8", False):       # FP8 retrieval cache: the views are its fp16 spec rows alone
+            if spec_cache.fp8:                          # FP8 retrieval cache: the views are its fp16 spec rows alone
                 return (*spec_cache.layer_kv(i), 0, spec_cache.real_budget, None)
             return (*spec_cache.layer_kv(i), spec_cache.spec_slot, spec_cache.real_budget, None)
         if dev_len is not None:                         # captured full-cache forward: lengths live on the device
@@ -194,7 +194,7 @@ class LlamaForCausalLM:
         else:                                           # :228-238  full-cache forward
             slot = kv_cache.append_slot(i, q_len)
             sk = slot + q_len
-        if not getattr(kv_cache, "fp8", False):
+        if not kv_cache.fp8:
             return (*kv_cache.layer_kv(i), slot, sk, None)
         kl, vl = (kv_cache.stage_k, kv_cache.stage_v) if fused else kv_cache.scratch_layer(i, slot)
         return kl, vl, slot, sk, kv_cache.layer_codes(i)

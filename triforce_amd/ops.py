@@ -64,6 +64,18 @@ def fuse_mode():
 FUSE_MODE = fuse_mode()
 
 
+def fp16_or_fp8(env, override, why):
+    """The value of an fp16|fp8 storage knob: ``override`` if given, else the environment variable ``env`` (default fp16).
+    fp8 needs the fused decode layer (FUSE_MODE, read at the call); ``why`` is the reason clause that ends that message."""
+    v = override if override is not None else _os.environ.get(env, "fp16")
+    v = str(v).strip().lower() or "fp16"
+    if v not in ("fp16", "fp8"):
+        raise ValueError(f"{env}={v!r}: expected fp16 or fp8")
+    if v == "fp8" and FUSE_MODE != "all":
+        raise ValueError(f"{env}=fp8 needs the fused decode layer (TRIFORCE_FUSE=all, got {FUSE_MODE!r}): {why}")
+    return v
+
+
 def pack_weight(w):
     """[N, K] fp16 -> MFMA-operand order [N/16][K/32][4 (g)][16 (i)][8]: one 16x32 tile = one contiguous KiB."""
     N, K = w.shape
