@@ -517,6 +517,24 @@ int tf_topp_probs(const float* logits, float* probs, int rows, int V, float temp
  * TF_EINVAL: NULL pointer, rows < 1, V < 1, !(temperature > 0), !(top_p > 0), top_k < 1.  TF_ERANGE: V > 32768. */
 int tf_topk_topp_probs(const float* logits, float* probs, int rows, int V, float temperature, int top_k, float top_p,
                        void* stream);
+/* tf_topp_probs_large / tf_topk_topp_probs_large (csrc/topp_large.hip): the two normalisers above for
+ * vocabularies up to 262 144 (Z < 2^58 still fits the 64-bit sums), 1 <= rows <= 32, any V (also V % 4 != 0), any 4-byte-aligned
+ * base, contiguous rows.  The numerics are EXACTLY those stated for tf_topp_probs and tf_topk_topp_probs — the same helpers
+ * decide every bit — so for V <= 32768 the output is BIT-IDENTICAL to the kernel of the same name without _large.  One workgroup
+ * of 1 024 threads per row; the row (x, then e) and the candidates of the select stream through `ws` instead of living in LDS.
+ *   ws   >= TF_TOPP_LARGE_WS_BYTES(rows, V) bytes of device scratch, 16-byte aligned: per row the x / e values and the candidate
+ *        list, each padded to whole slabs of 4 096 entries (a macro, not a call: the size is pure arithmetic on the shape).  It
+ *        carries no state between launches (nothing to zero, graph replays may run back to back); launches that share one ws
+ *        must be ordered against each other (one stream, or a graph's edges).
+ * No host synchronisation and no allocation: capturable in a hipGraph.  All gates come before anything launches:
+ * TF_EINVAL: NULL pointer (ws included) or misaligned ws, rows < 1, rows > 32, V < 1, !(temperature > 0), !(top_p > 0),
+ * top_k < 1.  TF_ERANGE: V > 262144.  TF_ENOSPC: ws_bytes too small.  top_k >= V is tf_topp_probs_large bit for bit. */
+#define TF_TOPP_LARGE_MAX_VOCAB 262144
+#define TF_TOPP_LARGE_WS_BYTES(rows, V) ((int64_t)(rows) * ((((int64_t)(V) + 4095) >> 12) * 4096 * 2) * 4)
+int tf_topp_probs_large(const float* logits, float* probs, int rows, int V, float temperature, float top_p, void* ws,
+                        int64_t ws_bytes, void* stream);
+int tf_topk_topp_probs_large(const float* logits, float* probs, int rows, int V, float temperature, int top_k, float top_p,
+                             void* ws, int64_t ws_bytes, void* stream);
 int tf_sample_inverse_cdf(const float* probs, const float* u, int64_t* token_out, int V, void* stream);
 int tf_accept_chain(const float* p, const float* q, const int64_t* tokens, const float* uniforms,
                     int g2, int V, int inclusive, int64_t eos_token_id, int64_t* out, void* stream);

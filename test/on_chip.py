@@ -8,6 +8,7 @@ import sys
 sys.path.append(os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 
 from triforce_amd.models.cache import FlashSimpleCache, RetrievalCache, StreamingLLMEvictionCache  # noqa: E402
+from triforce_amd.models import zoo  # noqa: E402
 from triforce_amd.models.modeling_llama import LlamaForCausalLM  # noqa: E402
 from triforce_amd.models.modeling_llama_68m import LlamaForCausalLM as LlamaForCausalLM_68M  # noqa: E402
 from triforce_amd.utils import cli  # noqa: E402
@@ -80,7 +81,7 @@ def main():
     args = cli.parse("on_chip")
     cli.target_config(args.target)
     target = cli.load_causal_lm(LlamaForCausalLM, args.weights, args.target, DEVICE)
-    draft = cli.load_causal_lm(LlamaForCausalLM_68M, cli.draft_weights(args), "llama-68M", DEVICE)
+    draft = cli.load_causal_lm(LlamaForCausalLM_68M, cli.draft_weights(args), zoo.draft_for(args.target), DEVICE)
     tokenizer, prompts = cli.load_prompts(args, target.config.vocab_size)
     sampling = dict(top_k=args.top_k, top_p=args.top_p, temperature=args.temp)
     print_config(draft, target, args.prefill, args.gen_len, args.gamma, file_path=args.file, method="TriForce",

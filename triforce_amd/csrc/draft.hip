@@ -24,6 +24,8 @@ __global__ __launch_bounds__(256) void draft_embed_kernel(const h16* __restrict_
 }
 
 static inline int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+// above tf_topp_probs' 32 768 entries the chain's final top-p is tf_topp_probs_large, whose workspace is the last piece of ws
+static inline bool draft_large_vocab(const TfDraftModel* m) { return m->vocab > 32768 && m->vocab <= TF_TOPP_LARGE_MAX_VOCAB; }
 
 extern "C" int64_t tf_draft_forward_ws_bytes(const TfDraftModel* m, int n) {
     if (!m || n < 1) return 0;
@@ -33,7 +35,8 @@ extern "C" int64_t tf_draft_forward_ws_bytes(const TfDraftModel* m, int n) {
          + align256((int64_t)n * hid * 2)            // q    [n][H][D]
          + align256((int64_t)n * hid * 2)            // a    attention output
          + align256((int64_t)n * I * 2)              // act  SwiGLU output
-         + align256((hid / 16) * 32 * 4);            // ss   sum-of-squares hand-off
+         + align256((hid / 16) * 32 * 4)             // ss   sum-of-squares hand-off
+         + (draft_large_vocab(m) ? align256(TF_TOPP_LARGE_WS_BYTES(1, m->vocab)) : 0);   // the streaming top-p's row
 }
 
 extern "C" int tf_draft_forward_68m(const TfDraftModel* m, const TfDraftCache* c, const int64_t* ids, int n, int slot0,
@@ -52,7 +55,8 @@ extern "C" int tf_draft_forward_68m(const TfDraftModel* m, const TfDraftCache* c
     h16* q = reinterpret_cast<h16*>(p);             p += align256((int64_t)n * hid * 2);
     h16* a = reinterpret_cast<h16*>(p);             p += align256((int64_t)n * hid * 2);
     h16* act = reinterpret_cast<h16*>(p);           p += align256((int64_t)n * I * 2);
-    float* ss = reinterpret_cast<float*>(p);
+    float* ss = reinterpret_cast<float*>(p);        p += align256((hid / 16) * 32 * 4);
+    void* topp_ws = p;                              // draft_large_vocab(m) only
     hipStream_t st = (hipStream_t)stream;
 
     hipLaunchKernelGGL(draft_embed_kernel, dim3(n), dim3(96), 0, st, (const h16*)m->embed, ids, x, pos, n, hid, V, slot0);
@@ -76,7 +80,10 @@ extern "C" int tf_draft_forward_68m(const TfDraftModel* m, const TfDraftCache* c
     rc = tf_skinny_gemm_ex(m->lm_head, x, hid, m->norm, m->eps, ss, nullptr, 0, nullptr, logits_out, V, n, V, hid, 1,
                            stream);
     if (rc) return rc;
-    if (probs_out)                                   // only the last row is sampled from (graph_infer.py:57)
+    if (probs_out && draft_large_vocab(m))           // only the last row is sampled from (graph_infer.py:57)
+        return tf_topp_probs_large(logits_out + (int64_t)(n - 1) * V, probs_out, 1, V, temperature, top_p, topp_ws,
+                                   TF_TOPP_LARGE_WS_BYTES(1, V), stream);
+    if (probs_out)
         return tf_topp_probs(logits_out + (int64_t)(n - 1) * V, probs_out, 1, V, temperature, top_p, stream);
     return TF_OK;
 }

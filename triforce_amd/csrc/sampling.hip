@@ -10,6 +10,15 @@
 #include "common.h"
 
 #define SAMP_THREADS 1024
+// One workgroup on `stream`: the kernel's LARGE instance above 32 768 entries (block_sample's streamed slices), else the
+// instance whose slices live in registers.
+#define SAMP_LAUNCH(kern, V, ...)                                                                                          \
+    do {                                                                                                                   \
+        if ((V) > SAMP_THREADS * 32)                                                                                       \
+            hipLaunchKernelGGL(kern<true>, dim3(1), dim3(SAMP_THREADS), 0, (hipStream_t)stream, __VA_ARGS__);              \
+        else                                                                                                               \
+            hipLaunchKernelGGL(kern<false>, dim3(1), dim3(SAMP_THREADS), 0, (hipStream_t)stream, __VA_ARGS__);             \
+    } while (0)
 
 struct SampleShared {
     float wave_tot[SAMP_THREADS / 64];
@@ -18,9 +27,28 @@ struct SampleShared {
     float total;
 };
 
+// value(i .. i + 3) for a 16-byte group of the streamed form (zeros when the group lies past the slice's end)
+template <bool RESID>
+__device__ __forceinline__ f32x4 block_sample_load4(const float* __restrict__ p, const float* __restrict__ q, int i, int i1) {
+    f32x4 a = {0.f, 0.f, 0.f, 0.f};
+    if (i < i1) {
+        a = *reinterpret_cast<const f32x4*>(p + i);
+        if (RESID) {
+            const f32x4 b = *reinterpret_cast<const f32x4*>(q + i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { a[e] -= b[e]; a[e] = a[e] > 0.f ? a[e] : 0.f; }
+        }
+    }
+    return a;
+}
+
 // value(i) = RESID ? max(p[i]-q[i],0) : p[i];  returns the first index whose inclusive cumulative
 // sum exceeds u * total; all threads of the block get the result.
-template <bool RESID>
+// LARGE (the kernels' instances for V > 32768): a slice of 33 - 256 entries does not fit registers, so the
+// slice is STREAMED twice with 16-byte loads, four in flight (V % 4 == 0, aligned bases; else element by element as ever).  The
+// per-thread order of the additions is the sequential one in every path, so all paths give the same token bit for bit.
+// LARGE = false is the code as it was: those instances compile to the same instructions as before the large ones existed.
+template <bool RESID, bool LARGE>
 __device__ int block_sample(const float* __restrict__ p, const float* __restrict__ q, int V, float u,
                             SampleShared* sh) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -31,11 +59,30 @@ __device__ int block_sample(const float* __restrict__ p, const float* __restrict
     const int seg = (((V + SAMP_THREADS - 1) / SAMP_THREADS) + 3) & ~3;
     const int i0 = tid * seg, i1 = min(V, i0 + seg);
     float val[MAXSEG];
-    const bool vec = seg <= MAXSEG && (V % 4) == 0 && ((reinterpret_cast<uintptr_t>(p) & 15) == 0) &&
+    const bool vec = !LARGE && seg <= MAXSEG && (V % 4) == 0 && ((reinterpret_cast<uintptr_t>(p) & 15) == 0) &&
                      (!RESID || (reinterpret_cast<uintptr_t>(q) & 15) == 0);
+    const bool stream = LARGE && (V % 4) == 0 && ((reinterpret_cast<uintptr_t>(p) & 15) == 0) &&
+                        (!RESID || (reinterpret_cast<uintptr_t>(q) & 15) == 0);
     float local = 0.f;
     int my_last_nz = -1;
-    if (vec) {
+    if (LARGE && stream) {
+        // i0, seg and V are multiples of 4: every 16-byte group lies wholly inside [i0, i1) or wholly outside
+        for (int i = i0; i < i1; i += 16) {
+            f32x4 a[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) a[k] = block_sample_load4<RESID>(p, q, i + 4 * k, i1);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (i + 4 * k < i1) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        local += a[k][e];
+                        if (a[k][e] > 0.f) my_last_nz = i + 4 * k + e;
+                    }
+                }
+            }
+        }
+    } else if (vec) {
 #pragma unroll
         for (int s4 = 0; s4 < MAXSEG; s4 += 4) {
             const int i = i0 + s4;
@@ -88,7 +135,24 @@ __device__ int block_sample(const float* __restrict__ p, const float* __restrict
     // with non-zero mass whose inclusive cumulative sum exceeds the target (robust to the small
     // disagreement between the tree-scanned prefixes and the sequential in-segment sums).
     float c = wave_prefix + (inc - local);
-    if (vec) {
+    if (LARGE && stream) {
+        bool found = false;
+        for (int i = i0; i < i1 && !found; i += 16) {
+            f32x4 a[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) a[k] = block_sample_load4<RESID>(p, q, i + 4 * k, i1);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (!found && i + 4 * k < i1) {
+                        c += a[k][e];
+                        if (a[k][e] > 0.f && c > target) { atomicMin(&sh->first_idx, i + 4 * k + e); found = true; }
+                    }
+                }
+            }
+        }
+    } else if (vec) {
         bool found = false;
 #pragma unroll
         for (int s = 0; s < MAXSEG; ++s) {
@@ -129,13 +193,14 @@ __device__ __forceinline__ const float* cur_uniforms(const float* uniforms, cons
 __device__ __forceinline__ void st_agent_i64(int64_t* p, int64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void drain_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
+template <bool LARGE>
 __global__ __launch_bounds__(SAMP_THREADS) void sample_kernel(const float* __restrict__ probs,
                                                               const float* __restrict__ u, const int64_t* cursor, int off,
                                                               int64_t* __restrict__ token_out, int V) {
     __shared__ SampleShared sh;
     int64_t at;
     const float* uu = cur_uniforms(u, cursor, &at) + off;
-    const int t = block_sample<false>(probs, nullptr, V, *uu, &sh);
+    const int t = block_sample<false, LARGE>(probs, nullptr, V, *uu, &sh);
     if (threadIdx.x == 0) *token_out = (int64_t)t;
 }
 
@@ -155,6 +220,7 @@ struct ChainStep {
     int nsets;
 };
 
+template <bool LARGE>
 __global__ __launch_bounds__(SAMP_THREADS) void accept_chain_kernel(
     const float* __restrict__ p, const float* __restrict__ q, const int64_t* __restrict__ tokens,
     const float* __restrict__ uniforms_base, int64_t* cursor, int g2, int V, int inclusive, int64_t eos,
@@ -194,9 +260,9 @@ __global__ __launch_bounds__(SAMP_THREADS) void accept_chain_kernel(
     if (reason == 2) {
         next = eos;
     } else if (reason == 0) {
-        next = block_sample<true>(p + (int64_t)count * V, q + (int64_t)count * V, V, uniforms[examined], &sh);
+        next = block_sample<true, LARGE>(p + (int64_t)count * V, q + (int64_t)count * V, V, uniforms[examined], &sh);
     } else {
-        next = block_sample<false>(p + (int64_t)g2 * V, nullptr, V, uniforms[examined], &sh);
+        next = block_sample<false, LARGE>(p + (int64_t)g2 * V, nullptr, V, uniforms[examined], &sh);
     }
     if (cs.tok && tid < 64) {
         // pass tokens: tok[0 .. count] stay; tok[count + 1] = the resampled / bonus token (PAD after an accepted eos); PAD up to
@@ -231,16 +297,18 @@ __global__ __launch_bounds__(SAMP_THREADS) void accept_chain_kernel(
 // follow-up draw with u[1] from row n + 1 (accepted) or row n (rejected) of the retrieval model's rows.  The ONE place this
 // arithmetic is written: middle_accept_kernel and every stage of middle_accept2_kernel call it, so they agree by construction.
 struct MidDecision { int acc, b; };
+template <bool LARGE>
 __device__ __forceinline__ MidDecision middle_decide(const float* __restrict__ p, const float* __restrict__ q_d, int64_t d,
                                                      const float* __restrict__ u, int n, int V, SampleShared* sh) {
     const float ratio = p[(int64_t)n * V + d] / q_d[d];
     const float m = (ratio != ratio) ? ratio : fminf(1.0f, ratio);
     MidDecision r;
     r.acc = (u[0] < m) ? 1 : 0;
-    r.b = block_sample<false>(p + (int64_t)(n + r.acc) * V, nullptr, V, u[1], sh);
+    r.b = block_sample<false, LARGE>(p + (int64_t)(n + r.acc) * V, nullptr, V, u[1], sh);
     return r;
 }
 
+template <bool LARGE>
 __global__ __launch_bounds__(SAMP_THREADS) void middle_accept_kernel(
     const float* __restrict__ p, const float* __restrict__ q_d, int64_t* __restrict__ tokens,
     const float* __restrict__ uniforms_base, int64_t* cursor, int uoff, int n, int gamma, int V, int64_t* __restrict__ out,
@@ -249,7 +317,7 @@ __global__ __launch_bounds__(SAMP_THREADS) void middle_accept_kernel(
     int64_t at;
     const float* uniforms = cur_uniforms(uniforms_base, cursor, &at) + uoff;
     const int64_t d = tokens[n + 1];
-    const MidDecision dec = middle_decide(p, q_d, d, uniforms, n, V, &sh);
+    const MidDecision dec = middle_decide<LARGE>(p, q_d, d, uniforms, n, V, &sh);
     const int acc = dec.acc, b = dec.b;
     if (threadIdx.x == 0) {
         // first what the next chain reads on the device (write-through, drained), then the record the host waits for
@@ -278,6 +346,7 @@ __global__ __launch_bounds__(SAMP_THREADS) void middle_accept_kernel(
 #define MID_MAX_DEPTH 4
 struct MidDraftRows { const float* q[MID_MAX_DEPTH]; };
 
+template <bool LARGE>
 __global__ __launch_bounds__(SAMP_THREADS) void middle_accept2_kernel(
     const float* __restrict__ p, MidDraftRows qs, int64_t* __restrict__ tokens, const float* __restrict__ uniforms_base,
     int64_t* cursor, int n, int gamma, int V, int depth, int64_t* __restrict__ out, int write_limit) {
@@ -290,7 +359,7 @@ __global__ __launch_bounds__(SAMP_THREADS) void middle_accept2_kernel(
     for (int s = 0; s < depth; ++s) {
         pos = n + 2 * s;
         const int64_t d = tokens[pos + 1];
-        dec = middle_decide(p, qs.q[s], d, u + 3 * s + 1, pos, V, &sh);
+        dec = middle_decide<LARGE>(p, qs.q[s], d, u + 3 * s + 1, pos, V, &sh);
         ran = s + 1;
         if (threadIdx.x == 0) {
             s_rec[3 * s] = dec.acc;
@@ -598,7 +667,7 @@ extern "C" int tf_sample_without_replacement(const float* logits, const void* ra
 
 extern "C" int tf_sample_inverse_cdf(const float* probs, const float* u, int64_t* token_out, int V, void* stream) {
     if (!probs || !u || !token_out || V < 1) return TF_EINVAL;
-    hipLaunchKernelGGL(sample_kernel, dim3(1), dim3(SAMP_THREADS), 0, (hipStream_t)stream, probs, u, (const int64_t*)nullptr, 0,
+    SAMP_LAUNCH(sample_kernel, V, probs, u, (const int64_t*)nullptr, 0,
                        token_out, V);
     TF_LAUNCH_CHECK();
     return TF_OK;
@@ -607,7 +676,7 @@ extern "C" int tf_sample_inverse_cdf(const float* probs, const float* u, int64_t
 extern "C" int tf_accept_chain(const float* p, const float* q, const int64_t* tokens, const float* uniforms, int g2,
                                int V, int inclusive, int64_t eos_token_id, int64_t* out, void* stream) {
     if (!p || !q || !tokens || !uniforms || !out || g2 < 1 || g2 > 63 || V < 1) return TF_EINVAL;
-    hipLaunchKernelGGL(accept_chain_kernel, dim3(1), dim3(SAMP_THREADS), 0, (hipStream_t)stream, p, q, tokens,
+    SAMP_LAUNCH(accept_chain_kernel, V, p, q, tokens,
                        uniforms, (int64_t*)nullptr, g2, V, inclusive, eos_token_id, out, ChainStep{});
     TF_LAUNCH_CHECK();
     return TF_OK;
@@ -616,7 +685,7 @@ extern "C" int tf_accept_chain(const float* p, const float* q, const int64_t* to
 extern "C" int tf_middle_accept(const float* p, const float* q_d, int64_t* tokens, const float* uniforms, int n,
                                 int gamma, int V, int64_t* out, void* stream) {
     if (!p || !q_d || !tokens || !uniforms || !out || n < 0 || n >= gamma || V < 1) return TF_EINVAL;
-    hipLaunchKernelGGL(middle_accept_kernel, dim3(1), dim3(SAMP_THREADS), 0, (hipStream_t)stream, p, q_d, tokens,
+    SAMP_LAUNCH(middle_accept_kernel, V, p, q_d, tokens,
                        uniforms, (int64_t*)nullptr, 0, n, gamma, V, out, gamma);
     TF_LAUNCH_CHECK();
     return TF_OK;
@@ -646,7 +715,7 @@ extern "C" int tf_mid_record_tokens(const int64_t* rec, int64_t* tokens, int tok
 extern "C" int tf_sample_inverse_cdf_cur(const float* probs, const float* ubuf, const int64_t* cursor, int off,
                                          int64_t* token_out, int V, void* stream) {
     if (!probs || !ubuf || !cursor || !token_out || V < 1 || off < 0) return TF_EINVAL;
-    hipLaunchKernelGGL(sample_kernel, dim3(1), dim3(SAMP_THREADS), 0, (hipStream_t)stream, probs, ubuf, cursor, off, token_out, V);
+    SAMP_LAUNCH(sample_kernel, V, probs, ubuf, cursor, off, token_out, V);
     TF_LAUNCH_CHECK();
     return TF_OK;
 }
@@ -656,7 +725,7 @@ extern "C" int tf_middle_accept_cur(const float* p, const float* q_d, int64_t* t
     if (!p || !q_d || !tokens || !ubuf || !cursor || !out || n < 0 || n >= gamma || V < 1 || tokens_len < gamma + 1) return TF_EINVAL;
     // a token buffer with room for it also receives the follow-up token of the LAST position (index gamma + 1)
     const int limit = tokens_len >= gamma + 2 ? gamma + 1 : gamma;
-    hipLaunchKernelGGL(middle_accept_kernel, dim3(1), dim3(SAMP_THREADS), 0, (hipStream_t)stream, p, q_d, tokens, ubuf, cursor,
+    SAMP_LAUNCH(middle_accept_kernel, V, p, q_d, tokens, ubuf, cursor,
                        1, n, gamma, V, out, limit);
     TF_LAUNCH_CHECK();
     return TF_OK;
@@ -677,7 +746,7 @@ static int launch_middle_accept_n(const float* p, const float* const* q, int max
         qs.q[s] = q[s];
     }
     const int limit = tokens_len >= gamma + 2 ? gamma + 1 : gamma;
-    hipLaunchKernelGGL(middle_accept2_kernel, dim3(1), dim3(SAMP_THREADS), 0, (hipStream_t)stream, p, qs, tokens, ubuf, cursor,
+    SAMP_LAUNCH(middle_accept2_kernel, V, p, qs, tokens, ubuf, cursor,
                        n, gamma, V, depth, out, limit);
     TF_LAUNCH_CHECK();
     return TF_OK;
@@ -704,7 +773,7 @@ extern "C" int tf_middle_accept_n_cur(const float* p, const float* q1, const flo
 extern "C" int tf_accept_chain_cur(const float* p, const float* q, const int64_t* tokens, const float* ubuf, int64_t* cursor,
                                    int g2, int V, int inclusive, int64_t eos_token_id, int64_t* out, void* stream) {
     if (!p || !q || !tokens || !ubuf || !cursor || !out || g2 < 1 || g2 > 63 || V < 1) return TF_EINVAL;
-    hipLaunchKernelGGL(accept_chain_kernel, dim3(1), dim3(SAMP_THREADS), 0, (hipStream_t)stream, p, q, tokens, ubuf, cursor,
+    SAMP_LAUNCH(accept_chain_kernel, V, p, q, tokens, ubuf, cursor,
                        g2, V, inclusive, eos_token_id, out, ChainStep{});
     TF_LAUNCH_CHECK();
     return TF_OK;
@@ -727,7 +796,7 @@ extern "C" int tf_accept_chain_step(const float* p, const float* q, int64_t* tok
     cs.tok = tok_buf, cs.pad = pad, cs.s_src = s_src, cs.nsets = nsets;
     cs.pos[0] = pos_a, cs.slot[0] = slot_a, cs.sk[0] = sk_a, cs.n_pos[0] = n_pos_a, cs.qlen[0] = qlen_a;
     cs.pos[1] = pos_b, cs.slot[1] = slot_b, cs.sk[1] = sk_b, cs.n_pos[1] = n_pos_b, cs.qlen[1] = qlen_b;
-    hipLaunchKernelGGL(accept_chain_kernel, dim3(1), dim3(SAMP_THREADS), 0, (hipStream_t)stream, p, q, tok_buf + 1, ubuf, cursor,
+    SAMP_LAUNCH(accept_chain_kernel, V, p, q, tok_buf + 1, ubuf, cursor,
                        g2, V, inclusive, eos_token_id, out, cs);
     TF_LAUNCH_CHECK();
     return TF_OK;
@@ -752,218 +821,7 @@ extern "C" int tf_accept_chain_step(const float* p, const float* q, int64_t* tok
 // (The first version decided one bit of the boundary per block-wide reduction — 12 reductions of 16 waves, then a
 // single-wave finish — behind a 132 KiB LDS staging of the row: 50 us per call, every draft step and every verify.)
 // ------------------------------------------------------------------------------------------------
-#define TOPP_THREADS 1024
-#define TOPP_SLABS 8                       // 16-byte slabs per thread: 8 * 4 * 1024 = 32768 entries
-#define TOPP_EPT (4 * TOPP_SLABS)
-#define TOPP_BINS 1024
-#define TOPP_HB(b) ((b) + ((b) >> 4))      // one pad slot per 16 bins: the scan's 16-bins-per-lane reads spread over banks
-#define TOPP_FIX_SHIFT 40                  // masses in units of 2^-40 (row total < 2^15 * 2^40)
-
-struct ToppShared {
-    unsigned long long hist[TOPP_BINS + TOPP_BINS / 16];
-    unsigned cnt[TOPP_BINS + TOPP_BINS / 16];
-    float red[TOPP_THREADS / 64];
-    int red_i[TOPP_THREADS / 64];
-    unsigned long long S, tau, nkeep, zk;
-    unsigned long long zpart[TOPP_THREADS / 64];   // per-wave sums of all masses: Z does not come from the histogram
-    unsigned ties;
-    int digit;                                     // >= 0 boundary bin, -1 keep everything, -2 boundary below the candidate cut
-    unsigned krem;                                 // top-k select: rank still looked for inside the current prefix
-    int kdigit;                                    //               the bin the last count scan named
-};
-
-__device__ __forceinline__ float block_max_1024(float v, float* sm, int tid) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((tid & 63) == 0) sm[tid >> 6] = v;
-    __syncthreads();
-    float t = sm[0];
-#pragma unroll
-    for (int w = 1; w < TOPP_THREADS / 64; ++w) t = fmaxf(t, sm[w]);
-    return t;
-}
-
-// floor(e * 2^40) for 0 <= e <= 1 straight from the bit pattern (monotone in e; 0 below 2^-40)
-__device__ __forceinline__ unsigned long long topp_fix(float e) {
-    const unsigned b = __float_as_uint(e);
-    const int ex = (int)(b >> 23);
-    const unsigned long long man = (unsigned long long)((b & 0x7FFFFFu) | 0x800000u);
-    const int sh = ex - (127 + 23 - TOPP_FIX_SHIFT);
-    if (ex == 0 || sh <= -24) return 0ull;
-    return sh >= 0 ? (man << sh) : (man >> (-sh));
-}
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o, 64);
-        const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o, 64);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
-
-// hist[digit] += m for the active lanes of a wave (wave-uniform call).  When more than 8 lanes are active and all of
-// them name the same bin (degenerate rows: huge tie groups) the wave adds ONE pre-summed value instead of serialising up
-// to 64 same-address atomics.
-__device__ __forceinline__ void topp_hist_add(ToppShared* sh, bool active, int digit, unsigned long long m, bool count) {
-    const unsigned long long act = __ballot(active);
-    if (!act) return;
-    const int first = __ffsll((long long)act) - 1;
-    const int dref = __shfl(digit, first, 64);
-    if (__popcll(act) > 8 && __all(!active || digit == dref)) {
-        const unsigned long long tot = wave_sum_u64(active ? m : 0ull);
-        if ((int)(threadIdx.x & 63) == first) {
-            atomicAdd(&sh->hist[TOPP_HB(dref)], tot);
-            if (count) atomicAdd(&sh->cnt[TOPP_HB(dref)], (unsigned)__popcll(act));
-        }
-    } else if (active) {
-        atomicAdd(&sh->hist[TOPP_HB(digit)], m);
-        if (count) atomicAdd(&sh->cnt[TOPP_HB(digit)], 1u);
-    }
-}
-
-// One wavefront scans the histogram from the top: lane l owns bins [16l, 16l+16).  Names the bin d with
-//   S(d) <= tau < S(d) + mass(d),   S(d) = base + mass of the bins above d
-// (sh->digit, sh->S = S(d)); no such bin (tau >= total: top_p >= 1) -> digit = -1.  The first round also fixes
-// tau = floor(top_p * Z); the last round resolves the ties at the boundary pattern: the j-th tie (index order) is
-// kept iff S + j * m <= tau.  Clears the bins it read for the next round.
-__device__ __forceinline__ void topp_scan(ToppShared* sh, int lane, bool first_round, bool last_round, float top_p) {
-    unsigned long long h[16];
-    unsigned long long tot = 0ull;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        h[k] = sh->hist[TOPP_HB(16 * lane + k)];
-        sh->hist[TOPP_HB(16 * lane + k)] = 0ull;
-        tot += h[k];
-    }
-    unsigned long long inc = tot;                                   // inclusive suffix sum over the lanes
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned lo = (unsigned)__shfl_down((int)(unsigned)inc, o, 64);
-        const unsigned hi = (unsigned)__shfl_down((int)(unsigned)(inc >> 32), o, 64);
-        if (lane + o < 64) inc += ((unsigned long long)hi << 32) | lo;
-    }
-    unsigned long long base, tau, Z = 0ull;
-    if (first_round) {
-#pragma unroll
-        for (int w = 0; w < TOPP_THREADS / 64; ++w) Z += sh->zpart[w];          // exact integers: any order
-        const double t = (double)top_p * (double)Z;
-        tau = (t >= 18446744073709549568.0) ? ~0ull : __double2ull_rd(t);
-        base = 0ull;
-        if (lane == 0) {
-            sh->tau = tau;
-            sh->zk = Z;
-        }
-    } else {
-        base = sh->S;
-        tau = sh->tau;
-    }
-    unsigned long long S = base + (inc - tot);
-    int found = -1;
-    unsigned long long Sf = 0ull, hf = 0ull;
-#pragma unroll
-    for (int k = 15; k >= 0; --k) {
-        if (found < 0 && h[k] != 0ull && S <= tau && tau - S < h[k]) {
-            found = k;
-            Sf = S;
-            hf = h[k];
-        }
-        S += h[k];
-    }
-    const unsigned long long hit = __ballot(found >= 0);
-    if (!hit) {
-        // nothing crossed: tau >= Z (top_p >= 1: keep everything) — or, first round only, the crossing lies among the
-        // entries the candidate cut left out of the histogram (cannot happen for the cut topp_probs_kernel derives)
-        if (lane == 0) sh->digit = (first_round && tau < Z) ? -2 : -1;
-    } else if (found >= 0) {
-        sh->digit = 16 * lane + found;
-        sh->S = Sf;
-        if (last_round) {
-            const unsigned T = sh->cnt[TOPP_HB(16 * lane + found)];
-            const unsigned long long m = hf / (unsigned long long)T;      // all ties share one pattern, hence one mass
-            unsigned long long nk = (tau - Sf) / m + 1ull;
-            if (nk > (unsigned long long)T) nk = T;
-            sh->ties = T;
-            sh->nkeep = nk;
-            sh->zk = Sf + nk * m;
-        }
-    }
-    if (last_round) {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) sh->cnt[TOPP_HB(16 * lane + k)] = 0u;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Top-k in front of the top-p select (tf_topk_topp_probs; reference utils/sampling.py:16-19: kth = topk(x, min(k, V))[-1],
-// every x < kth masked to -inf — every entry TIED with the k-th value survives).  kth is found by a 3-round radix select
-// (11 + 11 + 10 bits) over an order-preserving 32-bit key of x = l / T, on COUNT histograms in LDS: integers, so the
-// result does not depend on the order in which the atomics land.  The 2 048 count bins live in ToppShared::hist viewed as
-// 32-bit words (the mass histogram is not in use yet, and is left all-zero for it); lane l of the scanning wave owns bins
-// [32 l, 32 l + 32), one pad word per 32 bins keeps the lanes' reads on different banks.
-// ------------------------------------------------------------------------------------------------
-#define TOPK_BINS 2048
-#define TOPK_HB(b) ((b) + ((b) >> 5))
-#define TOPK_WORDS (TOPK_BINS + TOPK_BINS / 32)
-static_assert(TOPK_WORDS <= 2 * (TOPP_BINS + TOPP_BINS / 16), "the count histogram must fit in ToppShared::hist");
-
-// bigger float -> bigger key; -0.0 and +0.0 share one key (they compare equal)
-__device__ __forceinline__ unsigned topk_key(float x) {
-    unsigned b = __float_as_uint(x);
-    if (b == 0x80000000u) b = 0u;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-// cnt[digit] += 1 for the active lanes of a wave (wave-uniform call); a wave whose active lanes all name one bin (tie groups,
-// the narrow exponent range of a row of logits) adds its lane count once
-__device__ __forceinline__ void topk_cnt_add(unsigned* cnt, bool active, int digit) {
-    const unsigned long long act = __ballot(active);
-    if (!act) return;
-    const int first = __ffsll((long long)act) - 1;
-    const int dref = __shfl(digit, first, 64);
-    if (__popcll(act) > 8 && __all(!active || digit == dref)) {
-        if ((int)(threadIdx.x & 63) == first) atomicAdd(&cnt[TOPK_HB(dref)], (unsigned)__popcll(act));
-    } else if (active) {
-        atomicAdd(&cnt[TOPK_HB(digit)], 1u);
-    }
-}
-
-// One wavefront scans the count histogram from the top and names the bin d that holds the krem-th largest entry:
-//   above(d) < krem <= above(d) + cnt(d),   above(d) = entries in the bins above d
-// (sh->kdigit = d, sh->krem = krem - above(d): the rank inside the bin).  Clears the bins it read.
-__device__ __forceinline__ void topk_scan(ToppShared* sh, unsigned* cnt, int lane) {
-    unsigned h[32];
-    unsigned tot = 0u;
-#pragma unroll
-    for (int k = 0; k < 32; ++k) {
-        h[k] = cnt[TOPK_HB(32 * lane + k)];
-        cnt[TOPK_HB(32 * lane + k)] = 0u;
-        tot += h[k];
-    }
-    unsigned inc = tot;                                             // inclusive suffix sum over the lanes
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned n = (unsigned)__shfl_down((int)inc, o, 64);
-        if (lane + o < 64) inc += n;
-    }
-    const unsigned krem = sh->krem;
-    unsigned above = inc - tot;
-    int found = -1;
-    unsigned af = 0u;
-#pragma unroll
-    for (int k = 31; k >= 0; --k) {
-        if (found < 0 && above < krem && krem - above <= h[k]) {
-            found = k;
-            af = above;
-        }
-        above += h[k];
-    }
-    if (found >= 0) {                                               // exactly one lane: 1 <= krem <= entries counted
-        sh->kdigit = 32 * lane + found;
-        sh->krem = krem - af;
-    }
-}
+#include "topp_select.h"                    // ToppShared, topp_fix, topk_key and the histogram scans: shared with csrc/topp_large.hip
 
 // TOPK = false: tf_topp_probs.  TOPK = true: tf_topk_topp_probs — the same select over the survivors of the top-k filter.
 template <bool TOPK>

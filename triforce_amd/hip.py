@@ -173,6 +173,10 @@ SIGNATURES["tf_rope_append_gqa"] = (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _
 SIGNATURES["tf_token_logprobs"] = (_i32, [_vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp])
 SIGNATURES["tf_token_logprobs_ids"] = (_i32, [_vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp])
 
+# top-p / top-k + top-p for vocabularies up to 262 144 (include/triforce_hip.h)
+SIGNATURES["tf_topp_probs_large"] = (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _vp, _i64, _vp])
+SIGNATURES["tf_topk_topp_probs_large"] = (_i32, [_vp, _vp, _i32, _i32, _f32, _i32, _f32, _vp, _i64, _vp])
+
 ABI_VERSION = 1
 _lib = None
 

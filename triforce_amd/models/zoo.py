@@ -34,6 +34,15 @@ CONFIGS = {
                      num_key_value_heads=2, max_position_embeddings=131072, rms_norm_eps=1e-6,
                      rope_scaling=dict(type="yarn", factor=16.0, original_max_position_embeddings=256),
                      _name_or_path="tiny-yarn-gqa-target"),
+    # the tiny target and the 68M-shaped draft with the Llama-3 vocabulary (128 256 entries).  No trained
+    # draft of that vocabulary exists offline: both are random-init shapes
+    "tiny-v128k": dict(vocab_size=128256, hidden_size=256, intermediate_size=768, num_hidden_layers=2, num_attention_heads=2,
+                       max_position_embeddings=131072, rms_norm_eps=1e-6,
+                       rope_scaling=dict(type="yarn", factor=16.0, original_max_position_embeddings=256),
+                       _name_or_path="tiny-yarn-target-v128k"),
+    "llama-68M-v128k": dict(vocab_size=128256, hidden_size=768, intermediate_size=3072, num_hidden_layers=2,
+                            num_attention_heads=12, max_position_embeddings=2048, rms_norm_eps=1e-6,
+                            _name_or_path="llama-68m-shape-v128k"),
     # NousResearch/Yarn-Llama-2-70b-32k (grouped-query, 64 / 8 heads).  Written from memory of the model card: there is
     # no hub access offline, so these values are NOT checked against the published config.json
     "llama-70B-32K": dict(hidden_size=8192, intermediate_size=28672, num_hidden_layers=80, num_attention_heads=64,
@@ -47,6 +56,15 @@ def config(name):
     if name not in CONFIGS:
         raise NotImplementedError(f"unknown model {name!r}; known: {sorted(CONFIGS)}")
     return LlamaConfig.from_dict(CONFIGS[name])
+
+
+def draft_for(target_name):
+    """Name of the 68M-shaped draft that shares the named target's vocabulary (the draft proposes token ids of the target)."""
+    V = config(target_name).vocab_size
+    for name in ("llama-68M", "llama-68M-v128k"):
+        if config(name).vocab_size == V:
+            return name
+    raise NotImplementedError(f"no 68M-shaped draft with the {V}-entry vocabulary of {target_name!r}")
 
 
 def find_checkpoint(name):

@@ -1538,7 +1538,7 @@ def _topp_multi(device):
 
 
 def topp_probs(logits, temperature, top_p, panel_max=None):
-    """softmax(top_p_filter(logits / temperature)) for (rows, V) fp32 logits, V <= 32768 — one fused kernel: every row over 16
+    """softmax(top_p_filter(logits / temperature)) for (rows, V) fp32 logits, V <= 32768 (above: topp_probs_large) — one fused kernel: every row over 16
     workgroups with in-launch hand-offs (tf_topp_probs_multi) where the shape allows, else one workgroup per row
     (tf_topp_probs); bit-identical.  ``panel_max``: the per-panel row maxima the lm_head GEMM left (ops.linear(...,
     out_f32=True, ss_out=...)): the multi-workgroup form then skips its first hand-off."""
@@ -1563,7 +1563,7 @@ def topp_probs(logits, temperature, top_p, panel_max=None):
 
 
 def topk_topp_probs(logits, temperature, top_k, top_p):
-    """softmax(top_p_filter(top_k_filter(logits / temperature))) for (rows, V) fp32 logits, V <= 32768, top_k >= 1 — one fused
+    """softmax(top_p_filter(top_k_filter(logits / temperature))) for (rows, V) fp32 logits, V <= 32768 (above: topk_topp_probs_large), top_k >= 1 — one fused
     kernel, one workgroup per row (tf_topk_topp_probs): every entry tied with the k-th value survives the top-k filter, the
     rest is tf_topp_probs over the survivors; top_k >= V is tf_topp_probs bit for bit."""
     _dev(logits)
@@ -1572,6 +1572,80 @@ def topk_topp_probs(logits, temperature, top_k, top_p):
     hip.check(hip.lib().tf_topk_topp_probs(_ptr(logits), _ptr(probs), logits.shape[0], logits.shape[1], float(temperature),
                                            int(top_k), float(top_p), _stream()), "tf_topk_topp_probs")
     return probs
+
+
+# Vocabularies above TOPP_MAX_VOCAB: the same two normalisers with the row streamed through a workspace
+# instead of held in LDS.  TOPP_MAX_VOCAB stays the limit of everything else that says so (utils/SpecTree_TP.py gates the tree
+# sampler on it).
+TOPP_LARGE_MAX_VOCAB = 262144
+TOPP_LARGE_MAX_ROWS = 32
+_topp_large_state = {}
+
+
+def topp_large_ws_bytes(rows, V):
+    """TF_TOPP_LARGE_WS_BYTES(rows, V) of include/triforce_hip.h: per row the x / e values and the candidate list, each padded
+    to whole slabs of 4 096 entries."""
+    return int(rows) * (((int(V) + 4095) >> 12) * 4096 * 2) * 4
+
+
+def topp_route(V, top_p, is_device=True, dtype=torch.float32):
+    """Which normaliser utils.sampling.norm_logits takes for (rows, V) logits: "fused" (tf_topp_probs / tf_topk_topp_probs,
+    V <= TOPP_MAX_VOCAB), "large" (the _large forms, up to TOPP_LARGE_MAX_VOCAB) or "torch" (the sort restatement: CPU
+    tensors, other dtypes, top_p <= 0, larger vocabularies)."""
+    if not is_device or dtype != torch.float32 or not 0.0 < top_p:
+        return "torch"
+    if V <= TOPP_MAX_VOCAB:
+        return "fused"
+    return "large" if V <= TOPP_LARGE_MAX_VOCAB else "torch"
+
+
+def _topp_large_ws(device, rows, V):
+    """Workspace of the _large normalisers for this device: allocated (or grown) at a call OUTSIDE a capture — a graph's
+    warm-up passes always come first — and then kept, so a captured launch never allocates.  One per device: the launches of a
+    process are stream-ordered or synchronised against each other, as for _topp_multi."""
+    dev = torch.device(device)
+    key = torch.cuda.current_device() if dev.index is None else dev.index
+    need = topp_large_ws_bytes(rows, V)
+    bufs = _topp_large_state.setdefault(key, [])
+    if not bufs or bufs[-1].numel() < need:
+        if torch.cuda.is_current_stream_capturing():
+            raise hip.TriforceHipError(f"topp_probs_large: no workspace for ({rows}, {V}) on device {key} inside a capture "
+                                       "(run the call once outside the capture first)")
+        # sized for every row count this vocabulary can be called with; an outgrown buffer is kept, not freed: a captured
+        # graph may still replay launches that hold its address
+        bufs.append(torch.empty(topp_large_ws_bytes(TOPP_LARGE_MAX_ROWS, V), dtype=torch.uint8,
+                                device=torch.device("cuda", key)))
+    return bufs[-1]
+
+
+def _topp_large_call(logits, launch):
+    """probs for (rows, V) fp32 logits through ``launch(logits_ptr, probs_ptr, rows, V, ws_ptr, ws_bytes)``, at most
+    TOPP_LARGE_MAX_ROWS rows per launch (stream-ordered: they share the workspace)."""
+    _dev(logits)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()
+    probs = torch.empty_like(logits)
+    rows, V = logits.shape
+    ws = _topp_large_ws(logits.device, min(rows, TOPP_LARGE_MAX_ROWS), V)
+    for r0 in range(0, rows, TOPP_LARGE_MAX_ROWS):
+        n = min(TOPP_LARGE_MAX_ROWS, rows - r0)
+        launch(_ptr(logits[r0:r0 + n]), _ptr(probs[r0:r0 + n]), n, V, _ptr(ws), ws.numel())
+    return probs
+
+
+def topp_probs_large(logits, temperature, top_p):
+    """softmax(top_p_filter(logits / temperature)) for (rows, V) fp32 logits, V <= 262144 — tf_topp_probs_large: one workgroup
+    per row, the row streamed through a per-device workspace; bit-identical to topp_probs where both apply."""
+    L = hip.lib()
+    return _topp_large_call(logits, lambda lg, pr, n, V, ws, nb: hip.check(
+        L.tf_topp_probs_large(lg, pr, n, V, float(temperature), float(top_p), ws, nb, _stream()), "tf_topp_probs_large"))
+
+
+def topk_topp_probs_large(logits, temperature, top_k, top_p):
+    """topk_topp_probs for (rows, V) fp32 logits, V <= 262144, top_k >= 1 — tf_topk_topp_probs_large."""
+    L = hip.lib()
+    return _topp_large_call(logits, lambda lg, pr, n, V, ws, nb: hip.check(
+        L.tf_topk_topp_probs_large(lg, pr, n, V, float(temperature), int(top_k), float(top_p), ws, nb, _stream()),
+        "tf_topk_topp_probs_large"))
 
 
 # Rows of normalised hidden state that DecoderLayers.head scores per lm_head GEMM when it is asked for the prompt's

@@ -37,6 +37,11 @@ def norm_logits(logits: torch.Tensor, temperature=0.6, top_k=-1, top_p=0.9) -> t
     if logits.is_cuda and top_k > 0 and 0.0 < top_p and logits.shape[-1] <= ops.TOPP_MAX_VOCAB \
             and logits.dtype == torch.float32:
         return ops.topk_topp_probs(logits.contiguous(), temperature, top_k, top_p)   # the same kernel behind a top-k select
+    if ops.topp_route(logits.shape[-1], top_p, logits.is_cuda, logits.dtype) == "large":
+        # ops.TOPP_MAX_VOCAB < V <= ops.TOPP_LARGE_MAX_VOCAB: the same select with the row streamed through a workspace
+        if top_k > 0:
+            return ops.topk_topp_probs_large(logits.contiguous(), temperature, top_k, top_p)
+        return ops.topp_probs_large(logits.contiguous(), temperature, top_p)
     logits = logits / temperature
     logits = top_k_top_p_filter(logits, top_k=top_k, top_p=top_p)
     return F.softmax(logits, dim=-1)
