@@ -535,6 +535,28 @@ int tf_topp_probs_large(const float* logits, float* probs, int rows, int V, floa
                         int64_t ws_bytes, void* stream);
 int tf_topk_topp_probs_large(const float* logits, float* probs, int rows, int V, float temperature, int top_k, float top_p,
                              void* ws, int64_t ws_bytes, void* stream);
+/* tf_minp_probs / tf_minp_probs_large: the normalisers above with a MIN-P filter behind the top-p select
+ * (HF order: temperature -> top-k -> top-p -> min-p) — the target tier's sampling with min_p > 0.  top_k <= 0 or top_k >= V
+ * means no top-k filter; one entry serves both forms.  With x, the top-k survivors S, e_i = expf(x_i - max), the masses, Z, tau
+ * and the kept set K exactly as tf_topp_probs / tf_topk_topp_probs define them,
+ *   K' = { i in K : e_i >= min_p }   (compared in fp32; for non-negative floats a comparison of bit patterns),
+ * outputs e_i / Zk' on K' and 0 elsewhere, Zk' the exact integer sum of the 2^-40 fixed-point masses over K', converted as Zk
+ * is.  The row maximum has e = expf(0) = 1.0f exactly, so no normaliser enters the rule: a softmax over any masked set has the
+ * ratios p_i / p_max = e_i, hence the rule is HF's p_i >= min_p * p_max up to its float rounding.  Consequences, with ustar the
+ * boundary pattern of the top-p select and umin = bits(min_p):
+ *   umin <= ustar: min-p removes nothing and the output is BIT-IDENTICAL to the entry without min-p;
+ *   otherwise K' = { bits(e_i) >= umin }: the boundary ties are gone, Zk' takes one more exact reduction over the row;
+ *   min_p = 1.0 keeps exactly the entries equal to the row maximum: a unique maximum gives a one-hot row of exactly 1.0, equal
+ *   maxima share the mass.  A -inf logit is legal (mass 0); NaN is outside the contract.
+ * tf_minp_probs: V <= 32768, any rows.  tf_minp_probs_large: V <= 262144, rows <= 32, ws as for tf_topp_probs_large
+ * (TF_TOPP_LARGE_WS_BYTES); for V <= 32768 bit-identical to tf_minp_probs.  One workgroup of 1 024 threads per row, no state
+ * between launches, capturable.  All gates come before anything launches:
+ * TF_EINVAL: NULL pointer, rows < 1, V < 1, !(temperature > 0), !(top_p > 0), !(min_p > 0), min_p > 1 (_large: rows > 32, a NULL
+ * or misaligned ws).  TF_ERANGE: V above the entry's limit.  TF_ENOSPC: ws_bytes too small. */
+int tf_minp_probs(const float* logits, float* probs, int rows, int V, float temperature, int top_k, float top_p, float min_p,
+                  void* stream);
+int tf_minp_probs_large(const float* logits, float* probs, int rows, int V, float temperature, int top_k, float top_p,
+                        float min_p, void* ws, int64_t ws_bytes, void* stream);
 int tf_sample_inverse_cdf(const float* probs, const float* u, int64_t* token_out, int V, void* stream);
 int tf_accept_chain(const float* p, const float* q, const int64_t* tokens, const float* uniforms,
                     int g2, int V, int inclusive, int64_t eos_token_id, int64_t* out, void* stream);

@@ -33,7 +33,8 @@ def build_engine(args, target, draft):
     streaming = StreamingLLMEvictionCache(draft, start_size=16, recent_size=args.draft_cache_budget - 16 - args.gamma,
                                           gamma=args.gamma)
     engine = GraphInferenceEngine(target, full, retrieval, draft, streaming)
-    engine.initialize_cuda_graph(args.gamma, probs=True, temperature=args.temp, top_p=args.top_p, top_k=args.top_k)
+    engine.initialize_cuda_graph(args.gamma, probs=True, temperature=args.temp, top_p=args.top_p, top_k=args.top_k,
+                                 min_p=args.min_p)
     for c in (full, retrieval, streaming):
         c.print_status()
     return engine
@@ -87,6 +88,7 @@ def main():
     print_config(draft, target, args.prefill, args.gen_len, args.gamma, file_path=args.file, method="TriForce",
                  spec_args={"budget": args.budget, "chunk_size": args.chunk_size}, dataset=args.dataset, **sampling)
     engine = build_engine(args, target, draft)
+    sampling["min_p"] = args.min_p                   # (target tier only, like top_k; print_config has the reference's columns)
     print(colored(f"tokenized_prompts length: {len(prompts)}", "green"))
 
     def clip(p):

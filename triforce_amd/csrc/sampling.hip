@@ -824,10 +824,17 @@ extern "C" int tf_accept_chain_step(const float* p, const float* q, int64_t* tok
 #include "topp_select.h"                    // ToppShared, topp_fix, topk_key and the histogram scans: shared with csrc/topp_large.hip
 
 // TOPK = false: tf_topp_probs.  TOPK = true: tf_topk_topp_probs — the same select over the survivors of the top-k filter.
-template <bool TOPK>
+// MINP = true: tf_minp_probs — behind the select, K' = { i in K : e_i >= min_p }, compared as bit
+// patterns (the row maximum has e = expf(0) = 1.0f exactly, so e_i IS p_i / p_max and no normaliser enters the rule).  With
+// ustar the boundary pattern of the top-p select and umin = bits(min_p):
+//   umin <= ustar : min-p removes nothing; every value below is the one the MINP = false instance computes, bit for bit
+//   umin >  ustar (or top_p >= 1) : K' = { bits(e) >= umin }: no boundary ties are left to rank, and Zk' is one more exact
+//                   integer sum of topp_fix over the row in LDS (order-independent), converted as Zk is
+// min_p = 1.0f keeps exactly the entries equal to the row maximum.  Everything new sits under `if constexpr (MINP)`.
+template <bool TOPK, bool MINP>
 __device__ __forceinline__ void topp_probs_body(unsigned char* topp_smem, const float* __restrict__ logits,
                                                 float* __restrict__ probs, int V, float temperature, int top_k,
-                                                float top_p) {
+                                                float top_p, float min_p) {
     const int nslab = (V + 4095) >> 12;
     float* rowe = reinterpret_cast<float*>(topp_smem);
     ToppShared* sh = reinterpret_cast<ToppShared*>(topp_smem + (size_t)nslab * 4096 * sizeof(float));
@@ -1024,12 +1031,36 @@ __device__ __forceinline__ void topp_probs_body(unsigned char* topp_smem, const 
         ties = sh->ties;
         nkeep = sh->nkeep;
     }
-    const float Zk = (float)((double)sh->zk * (1.0 / 1099511627776.0));
+    unsigned long long zk = sh->zk;
+    bool minp_cut = false;                                       // min-p is the tighter filter (block-uniform)
+    unsigned umin = 0u;
+    if constexpr (MINP) {
+        umin = __float_as_uint(min_p);                           // 0 < min_p <= 1: patterns order like values
+        minp_cut = d1 < 0 || umin > ustar;
+        if (minp_cut) {
+            unsigned long long acc = 0ull;
+#pragma unroll 1
+            for (int s = 0; s < nslab; ++s) {
+                const f32x4 x = mine[1024 * s];
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (__float_as_uint(x[j]) >= umin) acc += topp_fix(x[j]);
+            }
+            const unsigned long long zw = wave_sum_u64(acc);
+            if (lane == 0) sh->zpart[wave] = zw;                 // (last read by the first scan, barriers ago)
+            __syncthreads();
+            zk = 0ull;
+#pragma unroll
+            for (int w = 0; w < TOPP_THREADS / 64; ++w) zk += sh->zpart[w];      // exact integers: any order
+        }
+    }
+    const float Zk = (float)((double)zk * (1.0 / 1099511627776.0));
     // kept: everything above the boundary pattern, and the first nkeep entries equal to it in INDEX order.  Usually
     // nkeep == ties (one entry carries the boundary value); otherwise the ties are ranked slab by slab with a
     // block-wide exclusive scan (block-uniform branch).
-    const bool rank_ties = d1 >= 0 && nkeep < (unsigned long long)ties;
-    const unsigned ulow = d1 < 0 ? 0u : (rank_ties ? ustar + 1u : ustar);      // patterns >= ulow stay unconditionally
+    const bool rank_ties = !(MINP && minp_cut) && d1 >= 0 && nkeep < (unsigned long long)ties;
+    const unsigned ulow = (MINP && minp_cut) ? umin                             // min-p: a plain threshold, no ties to rank
+                          : d1 < 0 ? 0u : (rank_ties ? ustar + 1u : ustar);     // patterns >= ulow stay unconditionally
     int basecnt = 0;
 #pragma unroll 1
     for (int s = 0; s < nslab; ++s) {
@@ -1086,14 +1117,23 @@ __global__ __launch_bounds__(TOPP_THREADS) void topp_probs_kernel(const float* _
     // dynamic LDS only (a static block in front would push the 16-byte row accesses off their alignment):
     // [ row: nslab * 4096 floats | ToppShared ]
     extern __shared__ __attribute__((aligned(16))) unsigned char topp_smem[];
-    topp_probs_body<false>(topp_smem, logits, probs, V, temperature, 0, top_p);
+    topp_probs_body<false, false>(topp_smem, logits, probs, V, temperature, 0, top_p, 0.f);
 }
 
 __global__ __launch_bounds__(TOPP_THREADS) void topk_topp_probs_kernel(const float* __restrict__ logits,
                                                                        float* __restrict__ probs, int V,
                                                                        float temperature, int top_k, float top_p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char topp_smem[];
-    topp_probs_body<true>(topp_smem, logits, probs, V, temperature, top_k, top_p);
+    topp_probs_body<true, false>(topp_smem, logits, probs, V, temperature, top_k, top_p, 0.f);
+}
+
+// tf_minp_probs: the two bodies above with the min-p threshold behind the select (TOPK as there)
+template <bool TOPK>
+__global__ __launch_bounds__(TOPP_THREADS) void minp_probs_kernel(const float* __restrict__ logits, float* __restrict__ probs,
+                                                                  int V, float temperature, int top_k, float top_p,
+                                                                  float min_p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char topp_smem[];
+    topp_probs_body<TOPK, true>(topp_smem, logits, probs, V, temperature, top_k, top_p, min_p);
 }
 
 static size_t topp_lds_bytes(int V) { return (size_t)((V + 4095) >> 12) * 4096 * sizeof(float) + sizeof(ToppShared); }
@@ -1135,4 +1175,33 @@ extern "C" int tf_topk_topp_probs(const float* logits, float* probs, int rows, i
                        probs, V, temperature, top_k, top_p);
     TF_LAUNCH_CHECK();
     return TF_OK;
+}
+
+// Temperature + top-k + top-p + min-p + softmax (include/triforce_hip.h has the contract).  top_k <= 0 or top_k >= V means no
+// top-k filter: the TOPK = false instance.
+template <bool TOPK>
+static int launch_minp_probs(const float* logits, float* probs, int rows, int V, float temperature, int top_k, float top_p,
+                             float min_p, void* stream) {
+    static bool attr_set[64] = {};                    // the dynamic-LDS opt-in, once per device
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return TF_EINVAL;
+    if (!attr_set[dev]) {
+        hipError_t e = hipFuncSetAttribute((const void*)minp_probs_kernel<TOPK>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)topp_lds_bytes(TOPP_THREADS * TOPP_EPT));
+        if (e != hipSuccess) return (int)e;
+        attr_set[dev] = true;
+    }
+    hipLaunchKernelGGL(minp_probs_kernel<TOPK>, dim3(rows), dim3(TOPP_THREADS), topp_lds_bytes(V), (hipStream_t)stream, logits,
+                       probs, V, temperature, top_k, top_p, min_p);
+    TF_LAUNCH_CHECK();
+    return TF_OK;
+}
+
+extern "C" int tf_minp_probs(const float* logits, float* probs, int rows, int V, float temperature, int top_k, float top_p,
+                             float min_p, void* stream) {
+    if (!logits || !probs || rows < 1 || V < 1 || !(temperature > 0.f) || !(top_p > 0.f) || !(min_p > 0.f) || min_p > 1.f)
+        return TF_EINVAL;
+    if (V > TOPP_THREADS * TOPP_EPT) return TF_ERANGE;
+    if (top_k >= 1 && top_k < V) return launch_minp_probs<true>(logits, probs, rows, V, temperature, top_k, top_p, min_p, stream);
+    return launch_minp_probs<false>(logits, probs, rows, V, temperature, 0, top_p, min_p, stream);
 }

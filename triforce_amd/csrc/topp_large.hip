@@ -62,10 +62,22 @@ __device__ __forceinline__ void tl_list_round(ToppLargeShared* sh, const float* 
     }
 }
 
-template <bool TOPK>
+// MINP = true: tf_minp_probs_large (the rule is stated at topp_probs_body, csrc/sampling.hip) — behind the
+// select, K' = { i in K : bits(e_i) >= umin = bits(min_p) }.  umin <= ustar changes nothing; otherwise Zk' is one more exact
+// integer sum: over the candidate list when umin is at or above the candidate cut (every kept entry with mass is in the list),
+// else over one more streamed pass of the row.  Everything new sits under `if constexpr (MINP)`.  The MINP instances and their
+// entry are compiled from this file by csrc/minp_large.hip (TOPP_LARGE_MINP_ENTRY): built next to them in one translation
+// unit, topp_large_kernel<true, false> came out with another schedule than it had before (the guard).
+// MinP is the pack (float) in the MINP instances and empty otherwise: the MINP = false instances keep the argument list, and with
+// it the instruction stream, they had before min-p existed.
+__device__ __forceinline__ float tl_min_p() { return 0.f; }
+__device__ __forceinline__ float tl_min_p(float min_p) { return min_p; }
+
+template <bool TOPK, bool MINP, typename... MinP>
 __global__ __launch_bounds__(TOPP_THREADS) void topp_large_kernel(const float* __restrict__ logits, float* __restrict__ probs,
                                                                   float* __restrict__ ws, int V, float temperature, int top_k,
-                                                                  float top_p) {
+                                                                  float top_p, MinP... min_p) {
+    static_assert(sizeof...(MinP) == (MINP ? 1 : 0), "min_p is an argument of the MINP instances only");
     __shared__ ToppLargeShared lsh;
     ToppShared* sh = &lsh.s;
     const int nslab = (V + 4095) >> 12;                                 // <= 64 slabs of 4 096 entries
@@ -209,12 +221,45 @@ __global__ __launch_bounds__(TOPP_THREADS) void topp_large_kernel(const float* _
         ties = sh->ties;
         nkeep = sh->nkeep;
     }
-    const float Zk = (float)((double)sh->zk * (1.0 / 1099511627776.0));
+    unsigned long long zk = sh->zk;
+    bool minp_cut = false;                                       // min-p is the tighter filter (block-uniform)
+    unsigned umin = 0u;
+    if constexpr (MINP) {
+        umin = __float_as_uint(tl_min_p(min_p...));              // 0 < min_p <= 1: patterns order like values
+        minp_cut = d1 < 0 || umin > ustar;
+        if (minp_cut) {
+            unsigned long long acc = 0ull;
+            if (umin >= cutpat) {                                // block-uniform: the list holds every entry with mass >= the cut
+                for (unsigned i = (unsigned)tid; i < nlist; i += TOPP_THREADS) {
+                    const float xv = list[i];
+                    if (__float_as_uint(xv) >= umin) acc += topp_fix(xv);
+                }
+            } else {
+                // umin below the cut: one more streamed pass.  (With the cut derived above, ustar >= cutpat, and top_p >= 1 has
+                // cutpat = 0: like digit == -2 this is the exact fallback, not a path any row takes.)
+#pragma unroll 1
+                for (int s = 0; s < nslab; ++s) {
+                    const f32x4 x = mine[1024 * s];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (__float_as_uint(x[j]) >= umin) acc += topp_fix(x[j]);
+                }
+            }
+            const unsigned long long zw = wave_sum_u64(acc);
+            if (lane == 0) sh->zpart[wave] = zw;                 // (last read by the first scan, barriers ago)
+            __syncthreads();
+            zk = 0ull;
+#pragma unroll
+            for (int w = 0; w < TOPP_THREADS / 64; ++w) zk += sh->zpart[w];      // exact integers: any order
+        }
+    }
+    const float Zk = (float)((double)zk * (1.0 / 1099511627776.0));
     // kept: everything above the boundary pattern, and the first nkeep entries equal to it in INDEX order.  Usually
     // nkeep == ties (one entry carries the boundary value); otherwise the ties are ranked slab by slab with a
     // block-wide exclusive scan (block-uniform branch).
-    const bool rank_ties = d1 >= 0 && nkeep < (unsigned long long)ties;
-    const unsigned ulow = d1 < 0 ? 0u : (rank_ties ? ustar + 1u : ustar);      // patterns >= ulow stay unconditionally
+    const bool rank_ties = !(MINP && minp_cut) && d1 >= 0 && nkeep < (unsigned long long)ties;
+    const unsigned ulow = (MINP && minp_cut) ? umin                             // min-p: a plain threshold, no ties to rank
+                          : d1 < 0 ? 0u : (rank_ties ? ustar + 1u : ustar);     // patterns >= ulow stay unconditionally
     int basecnt = 0;
 #pragma unroll 1
     for (int s = 0; s < nslab; ++s) {
@@ -277,11 +322,12 @@ static int topp_large_gates(const float* logits, const float* probs, int rows, i
     return TF_OK;
 }
 
+#ifndef TOPP_LARGE_MINP_ENTRY
 extern "C" int tf_topp_probs_large(const float* logits, float* probs, int rows, int V, float temperature, float top_p,
                                    void* ws, int64_t ws_bytes, void* stream) {
     const int rc = topp_large_gates(logits, probs, rows, V, temperature, top_p, ws, ws_bytes);
     if (rc) return rc;
-    hipLaunchKernelGGL(topp_large_kernel<false>, dim3(rows), dim3(TOPP_THREADS), 0, (hipStream_t)stream, logits, probs,
+    hipLaunchKernelGGL((topp_large_kernel<false, false>), dim3(rows), dim3(TOPP_THREADS), 0, (hipStream_t)stream, logits, probs,
                        static_cast<float*>(ws), V, temperature, 0, top_p);
     TF_LAUNCH_CHECK();
     return TF_OK;
@@ -294,8 +340,26 @@ extern "C" int tf_topk_topp_probs_large(const float* logits, float* probs, int r
     const int rc = topp_large_gates(logits, probs, rows, V, temperature, top_p, ws, ws_bytes);
     if (rc) return rc;
     if (top_k >= V) return tf_topp_probs_large(logits, probs, rows, V, temperature, top_p, ws, ws_bytes, stream);
-    hipLaunchKernelGGL(topp_large_kernel<true>, dim3(rows), dim3(TOPP_THREADS), 0, (hipStream_t)stream, logits, probs,
+    hipLaunchKernelGGL((topp_large_kernel<true, false>), dim3(rows), dim3(TOPP_THREADS), 0, (hipStream_t)stream, logits, probs,
                        static_cast<float*>(ws), V, temperature, top_k, top_p);
     TF_LAUNCH_CHECK();
     return TF_OK;
 }
+
+#else   // csrc/minp_large.hip: the MINP instances are built as a translation unit of their own
+// top_k <= 0 or top_k >= V means no top-k filter: the TOPK = false instance.
+extern "C" int tf_minp_probs_large(const float* logits, float* probs, int rows, int V, float temperature, int top_k,
+                                   float top_p, float min_p, void* ws, int64_t ws_bytes, void* stream) {
+    if (!(min_p > 0.f) || min_p > 1.f) return TF_EINVAL;
+    const int rc = topp_large_gates(logits, probs, rows, V, temperature, top_p, ws, ws_bytes);
+    if (rc) return rc;
+    if (top_k >= 1 && top_k < V)
+        hipLaunchKernelGGL((topp_large_kernel<true, true, float>), dim3(rows), dim3(TOPP_THREADS), 0, (hipStream_t)stream, logits, probs,
+                           static_cast<float*>(ws), V, temperature, top_k, top_p, min_p);
+    else
+        hipLaunchKernelGGL((topp_large_kernel<false, true, float>), dim3(rows), dim3(TOPP_THREADS), 0, (hipStream_t)stream, logits, probs,
+                           static_cast<float*>(ws), V, temperature, 0, top_p, min_p);
+    TF_LAUNCH_CHECK();
+    return TF_OK;
+}
+#endif

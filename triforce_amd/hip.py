@@ -177,6 +177,10 @@ SIGNATURES["tf_token_logprobs_ids"] = (_i32, [_vp, _i64, _vp, _i32, _i32, _vp, _
 SIGNATURES["tf_topp_probs_large"] = (_i32, [_vp, _vp, _i32, _i32, _f32, _f32, _vp, _i64, _vp])
 SIGNATURES["tf_topk_topp_probs_large"] = (_i32, [_vp, _vp, _i32, _i32, _f32, _i32, _f32, _vp, _i64, _vp])
 
+# min-p behind temperature / top-k / top-p on the target tier (include/triforce_hip.h)
+SIGNATURES["tf_minp_probs"] = (_i32, [_vp, _vp, _i32, _i32, _f32, _i32, _f32, _f32, _vp])
+SIGNATURES["tf_minp_probs_large"] = (_i32, [_vp, _vp, _i32, _i32, _f32, _i32, _f32, _f32, _vp, _i64, _vp])
+
 ABI_VERSION = 1
 _lib = None
 

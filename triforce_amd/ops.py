@@ -1648,6 +1648,28 @@ def topk_topp_probs_large(logits, temperature, top_k, top_p):
         "tf_topk_topp_probs_large"))
 
 
+def minp_probs(logits, temperature, top_k, top_p, min_p):
+    """softmax(min_p_filter(top_p_filter(top_k_filter(logits / temperature)))) for (rows, V) fp32 logits, V <= 32768 (above:
+    minp_probs_large), 0 < min_p <= 1 — tf_minp_probs, one workgroup per row: behind the select of topp_probs /
+    topk_topp_probs an entry stays iff e_i = expf(x_i - max) >= min_p.  top_k <= 0 or top_k >= V: no top-k filter.  Where
+    min-p removes nothing the output is topp_probs' / topk_topp_probs' (one workgroup per row) bit for bit."""
+    _dev(logits)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()
+    probs = torch.empty_like(logits)
+    hip.check(hip.lib().tf_minp_probs(_ptr(logits), _ptr(probs), logits.shape[0], logits.shape[1], float(temperature),
+                                      int(top_k), float(top_p), float(min_p), _stream()), "tf_minp_probs")
+    return probs
+
+
+def minp_probs_large(logits, temperature, top_k, top_p, min_p):
+    """minp_probs for (rows, V) fp32 logits, V <= 262144 — tf_minp_probs_large, the row streamed through the per-device
+    workspace of topp_probs_large; bit-identical to minp_probs where both apply."""
+    L = hip.lib()
+    return _topp_large_call(logits, lambda lg, pr, n, V, ws, nb: hip.check(
+        L.tf_minp_probs_large(lg, pr, n, V, float(temperature), int(top_k), float(top_p), float(min_p), ws, nb, _stream()),
+        "tf_minp_probs_large"))
+
+
 # Rows of normalised hidden state that DecoderLayers.head scores per lm_head GEMM when it is asked for the prompt's
 # log-probabilities: the fp32 logits block is SCORE_BLOCK_ROWS x V (131 MB at 32 000) instead of chunk x V (DESIGN section 23).
 SCORE_BLOCK_ROWS = 1024

@@ -66,6 +66,9 @@ SCRIPT_OWN = {
         ("--followup_len", int, 0, "tokens per follow-up question"),
         ("--top_k", int, -1, "top-k of the TARGET's sampling (first token, target verify, autoregressive baseline), as in the "
                              "reference; the two draft tiers never filter by top-k; -1 = off"),
+        ("--min_p", float, 0.0, "min-p of the TARGET's sampling, applied behind top-k / top-p: a token stays only if its "
+                                "probability is at least min_p times the most likely token's (0 < min_p <= 1); the two draft "
+                                "tiers never filter by it; 0 = off"),
         ("--reanchor_at", int, 0, "re-anchor the retrieval cache (fold the generated rows into the covered region and "
                                   "re-select) before its generated tail exceeds N rows, gamma + 2 <= N <= --budget: "
                                   "generation and follow-ups may then pass the budget; 0 = never"),

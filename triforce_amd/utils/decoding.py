@@ -34,8 +34,8 @@ def _eos(tokenizer):
 
 @torch.inference_mode()
 def Autoregressive(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, top_p=0.9, temperature=0.6, verbose=False,
-                   rng=None, return_tokens=False, logprobs=False):
-    """``logprobs``: also the log-probability (temperature 1, unfiltered: DESIGN section 23) of every emitted token, scored
+                   rng=None, return_tokens=False, logprobs=False, min_p=0.0):
+    """``min_p`` > 0: min-p behind top-k / top-p.  ``logprobs``: also the log-probability (temperature 1, unfiltered: DESIGN section 23) of every emitted token, scored
     on the device from the step's own logits -> (tokens / s, ids, logprobs)."""
     eng = graph_engine.engine
     device = eng.model.device
@@ -46,9 +46,10 @@ def Autoregressive(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, to
             raise NotImplementedError(refusal)
         lp = torch.empty(max_len + 1, dtype=torch.float32, device=device)
     rng = rng or UniformSource(device)
+    mp = _min_p_kw(min_p)
     eng.kv_cache.reset()
     logits = graph_engine.inference(input_ids=input_ids)
-    next_token = sample(norm_logits(logits[:, -1, :], temperature=temperature, top_k=top_k, top_p=top_p), rng=rng)
+    next_token = sample(norm_logits(logits[:, -1, :], temperature=temperature, top_k=top_k, top_p=top_p, **mp), rng=rng)
     if lp is not None:
         ops.token_logprobs(logits[:, -1, :], next_token.view(-1), out=lp[0:1])
     toks = [next_token]
@@ -59,7 +60,7 @@ def Autoregressive(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, to
         (lambda t: eng.model(input_ids=t, kv_cache=eng.kv_cache, graph_cache=None).logits)
     while n < max_len:      # no host sync inside the loop: the sampled token never leaves the device
         logits = step(next_token)
-        next_token = sample(norm_logits(logits[:, -1, :], temperature=temperature, top_k=top_k, top_p=top_p), rng=rng)
+        next_token = sample(norm_logits(logits[:, -1, :], temperature=temperature, top_k=top_k, top_p=top_p, **mp), rng=rng)
         toks.append(next_token)
         n += 1
         if lp is not None:                  # device targets, the step's own logits (a graph's static buffer until its next replay)
@@ -76,6 +77,11 @@ def Autoregressive(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, to
         if return_tokens:
             return n / (time2 - time1), ids
     return n / (time2 - time1)
+
+
+def _min_p_kw(min_p):
+    """``min_p`` for norm_logits only when the filter is on: without it the call is the one made before min-p existed."""
+    return dict(min_p=min_p) if min_p > 0 else {}
 
 
 def _logprobs_refusal(graph_engine, what):
@@ -474,7 +480,10 @@ class TriForceRunner:
 
     def __init__(self, tokenizer, graph_engine, gamma, top_k=-1, top_p=0.9, temperature=0.6, verbose=False, rng=None,
                  inclusive_accept=False, sync_record=None, rebuild_every=0, reanchor_at=0, logprobs=False,
-                 prompt_logprobs=False):
+                 prompt_logprobs=False, min_p=0.0):
+        # min_p: > 0 keeps a token of the TARGET's distribution (first token, target verify) only if its probability is at least
+        #              min_p times the most likely token's, behind top-k / top-p; the draft tiers stay unfiltered
+        self.min_p = float(min_p) if min_p > 0 else 0.0
         # logprobs: keep the log-probability (temperature 1, unfiltered: DESIGN section 23) of every emitted token, scored on the
         #              device from the logits of the verify that produced it — one launch per step, no host read before stats()
         # prompt_logprobs: prefill() also scores the prompt, log p(input_ids[i + 1] | input_ids[:i + 1]) for i = 0 .. n - 2
@@ -697,7 +706,8 @@ class TriForceRunner:
 
     @torch.inference_mode()
     def start(self, logits):
-        probs = norm_logits(logits[:, -1, :], temperature=self.temperature, top_k=self.top_k, top_p=self.top_p)
+        probs = norm_logits(logits[:, -1, :], temperature=self.temperature, top_k=self.top_k, top_p=self.top_p,
+                            **_min_p_kw(self.min_p))
         self.next_token = int(sample(probs, rng=self.rng))
         if self.verbose:
             spec_stream(self.next_token, self.tokenizer, "cyan")
@@ -727,7 +737,7 @@ class TriForceRunner:
         [next, t_1 .. t_g2]: the chain behind the last inner record is one graph replay, no set-up launch.  An eager or rebuild
         step still sets its verify up from the host."""
         ge = self.ge
-        if self.inner is None or self.sync_record is not None or self.inclusive_accept or not self._captured_top_k() \
+        if self.inner is None or self.sync_record is not None or self.inclusive_accept or not self._captured_filters() \
                 or (self.temperature, self.top_p) != (ge.sampling["temperature"], ge.sampling["top_p"]):
             return None
         return ge.verify_sets(self.gamma)
@@ -740,9 +750,29 @@ class TriForceRunner:
             return self.top_k <= 0
         return (captured if captured > 0 else -1) == (self.top_k if self.top_k > 0 else -1)
 
+    def _captured_min_p(self):
+        """The same for min-p: the engine's captured target verify applies THIS runner's min-p (an engine without ``min_p``
+        captured without one)."""
+        captured = getattr(self.ge, "min_p", None)
+        if captured is None:
+            return self.min_p <= 0
+        return (captured if captured > 0 else 0.0) == self.min_p
+
+    def _captured_filters(self):
+        """The captured target verify's top-k AND min-p are this runner's: what every fast route asks."""
+        return self._captured_top_k() and self._captured_min_p()
+
     def _top_k_kw(self):
         """``top_k`` for the verify entry points of an engine that takes one."""
         return {} if getattr(self.ge, "top_k", None) is None else dict(top_k=self.top_k)
+
+    def _filter_kw(self):
+        """``top_k`` / ``min_p`` for the verify entry points of an engine that takes them (one without the attribute gets the
+        filter through the eager norm_logits route: _captured_filters() keeps it off the fast routes)."""
+        kw = self._top_k_kw()
+        if getattr(self.ge, "min_p", None) is not None:
+            kw["min_p"] = self.min_p
+        return kw
 
     @torch.inference_mode()
     def step(self):
@@ -786,19 +816,20 @@ class TriForceRunner:
                 ge.sync_verify_lengths(gamma)                          # stale (first step, after an eager / rebuild step): one launch each
             tg = ge.target_graphs[len(ids)]
             probs, verify_tokens = tg.replay_in_place(), tg.ids
-        elif self._captured_top_k() and not rebuild and not eager and hasattr(ge, "verify_probs_ids") and len(ids) <= 32 \
-                and (fast := ge.verify_probs_ids(ids, self.temperature, self.top_p, **self._top_k_kw())) is not None:
+        elif self._captured_filters() and not rebuild and not eager and hasattr(ge, "verify_probs_ids") and len(ids) <= 32 \
+                and (fast := ge.verify_probs_ids(ids, self.temperature, self.top_p, **self._filter_kw())) is not None:
             # captured forward + temperature / top-p: ids, positions and lengths set by ONE launch (ids as kernel arguments)
             probs, verify_tokens = fast
         else:
             verify_tokens = bufs.to_device(ids)
-            if self._captured_top_k() and hasattr(ge, "verify_probs"):      # one hipGraph: forward + temperature / top-k / top-p
+            if self._captured_filters() and hasattr(ge, "verify_probs"):    # one hipGraph: forward + temperature / top-k / top-p
                 probs = ge.verify_probs(verify_tokens, self.temperature, self.top_p, rebuild_retrieval=rebuild, eager=eager,
-                                        **self._top_k_kw())
+                                        **self._filter_kw())
             else:
                 logits = ge.inference(input_ids=verify_tokens, rebuild_retrieval=True) if rebuild \
                     else (ge.inference(input_ids=verify_tokens, eager=True) if eager else ge.inference(input_ids=verify_tokens))
-                probs = norm_logits(logits[0], temperature=self.temperature, top_k=self.top_k, top_p=self.top_p)
+                probs = norm_logits(logits[0], temperature=self.temperature, top_k=self.top_k, top_p=self.top_p,
+                                    **_min_p_kw(self.min_p))
         if getattr(bufs, "rows_generation", None) is not None:
             # spec_rows is a view of the retrieval-verify graph's static output: nothing may have replayed that graph
             # between Middle_Spec's return and this read (the target verify above is a different graph)
@@ -939,12 +970,13 @@ class TriForceRunner:
 @torch.inference_mode()
 def TriForce(tokenizer, graph_engine, input_ids, gamma=4, max_len=256, top_k=-1, top_p=0.9, temperature=0.6, verbose=False,
              file_path=None, dataset=None, spec_args=None, rng=None, return_details=False, rebuild_every=0, reanchor_at=0,
-             logprobs=False, prompt_logprobs=False):
-    """``logprobs`` / ``prompt_logprobs``: ``return_details`` then carries ``logprobs`` — a list aligned
+             logprobs=False, prompt_logprobs=False, min_p=0.0):
+    """``min_p`` > 0: min-p on the target tier.
+    ``logprobs`` / ``prompt_logprobs``: ``return_details`` then carries ``logprobs`` — a list aligned
     with ``tokens`` — and ``prompt_logprobs`` — an fp32 host tensor of n - 1 values."""
     run = TriForceRunner(tokenizer, graph_engine, gamma, top_k, top_p, temperature, verbose, rng,
                          rebuild_every=rebuild_every, reanchor_at=reanchor_at, logprobs=logprobs,
-                         prompt_logprobs=prompt_logprobs)
+                         prompt_logprobs=prompt_logprobs, min_p=min_p)
     run.prefill(input_ids)
     eng, device = run.eng, run.device
     _sync(device)
@@ -979,10 +1011,10 @@ class TriForceSession:
     Every answer returns the runner's stats plus ``ttft`` — the seconds from the call to the first token of the answer."""
 
     def __init__(self, tokenizer, graph_engine, gamma=4, top_k=-1, top_p=0.9, temperature=0.6, verbose=False, rng=None,
-                 rebuild_every=0, reanchor_at=0, logprobs=False, prompt_logprobs=False):
+                 rebuild_every=0, reanchor_at=0, logprobs=False, prompt_logprobs=False, min_p=0.0):
         self.run = TriForceRunner(tokenizer, graph_engine, gamma, top_k, top_p, temperature, verbose, rng,
                                   rebuild_every=rebuild_every, reanchor_at=reanchor_at, logprobs=logprobs,
-                                  prompt_logprobs=prompt_logprobs)
+                                  prompt_logprobs=prompt_logprobs, min_p=min_p)
         self.ttft = None
 
     @property

@@ -28,9 +28,25 @@ def top_k_top_p_filter(logits: torch.Tensor, top_k: int = 0, top_p: float = 0.0)
     return logits
 
 
-def norm_logits(logits: torch.Tensor, temperature=0.6, top_k=-1, top_p=0.9) -> torch.Tensor:
-    """(rows, vocab) fp32 logits -> probabilities after temperature / top-k / top-p."""
+def _norm_logits_min_p(logits, temperature, top_k, top_p, min_p):
+    """norm_logits with min_p > 0 (HF order: temperature -> top-k -> top-p -> min-p): a token stays only if
+    its probability is at least min_p times the most likely token's.  fp32 device logits with top_p > 0 take the fused kernels
+    (ops.minp_probs / ops.minp_probs_large), everything else the torch restatement below."""
+    route = ops.topp_route(logits.shape[-1], top_p, logits.is_cuda, logits.dtype)
+    if route == "fused":
+        return ops.minp_probs(logits.contiguous(), temperature, top_k, top_p, min_p)
+    if route == "large":
+        return ops.minp_probs_large(logits.contiguous(), temperature, top_k, top_p, min_p)
+    probs = F.softmax(top_k_top_p_filter(logits / temperature, top_k=top_k, top_p=top_p), dim=-1)
+    probs = probs.masked_fill(probs < min_p * probs.amax(dim=-1, keepdim=True), 0.0)
+    return probs / probs.sum(dim=-1, keepdim=True)
+
+
+def norm_logits(logits: torch.Tensor, temperature=0.6, top_k=-1, top_p=0.9, min_p=0.0) -> torch.Tensor:
+    """(rows, vocab) fp32 logits -> probabilities after temperature / top-k / top-p (/ min-p when ``min_p`` > 0)."""
     assert logits.dim() == 2
+    if min_p > 0.0:
+        return _norm_logits_min_p(logits, temperature, top_k, top_p, min_p)
     if logits.is_cuda and top_k <= 0 and 0.0 < top_p and logits.shape[-1] <= ops.TOPP_MAX_VOCAB \
             and logits.dtype == torch.float32:
         return ops.topp_probs(logits.contiguous(), temperature, top_p)      # fused HIP kernel, no vocabulary sort
