@@ -122,6 +122,7 @@ def test_norm_logits_takes_the_large_kernels_and_never_sorts(monkeypatch):
     ops = _ops()
     dl = (LR.dense_row("sigma2.5", 128256, 3).unsqueeze(0)).to(DEV)
     want_p, want_k = ops.topp_probs_large(dl, 0.6, 0.9), ops.topk_topp_probs_large(dl, 0.6, 20, 0.9)
+    small = {V: _rows11(V, 5, 9)[:3].to(DEV) for V in (96, 32772)}       # (built here: _rows11 sorts)
 
     def boom(*a, **kw):
         raise AssertionError("the vocabulary was sorted")
@@ -132,6 +133,20 @@ def test_norm_logits_takes_the_large_kernels_and_never_sorts(monkeypatch):
     # more rows than one launch takes: split over launches, same rows
     many = dl.expand(40, -1).contiguous()
     assert torch.equal(norm_logits(many, temperature=0.6, top_k=-1, top_p=0.9), want_p.expand(40, -1))
+    # every kernel cell of the dispatch table is the wrapper it names, called directly: 3 rows at V = 96
+    # (fused) and at V = 32 772, the smallest multiple of 4 above the fused limit (large)
+    T, P = 0.8, 0.95
+    for V, large in [(96, ""), (32772, "_large")]:
+        lg = small[V]
+        for k in (-1, 5):
+            for m in (0.0, 0.1):
+                if m > 0:
+                    want = getattr(ops, "minp_probs" + large)(lg, T, k, P, m)
+                elif k > 0:
+                    want = getattr(ops, "topk_topp_probs" + large)(lg, T, k, P)
+                else:
+                    want = getattr(ops, "topp_probs" + large)(lg, T, P)
+                assert torch.equal(norm_logits(lg, temperature=T, top_k=k, top_p=P, min_p=m), want), (V, k, m)
 
 
 # ---- (d) block_sample above the limit -----------------------------------------------------------------------------------------

@@ -237,7 +237,7 @@ def test_g_captured_target_verify_applies_min_p_and_only_a_matching_runner_uses_
     g = _weights(large)[0]
     gamma, T, P, M = g["gamma"], 1.0, 1.0, 0.3
     ge = _engine(large, T, P, M)
-    assert ge.min_p == M and ge.top_k == -1 and "min_p" not in ge.sampling
+    assert ge.target_filters.min_p == M and ge.target_filters.top_k == -1 and "min_p" not in ge.sampling
     prompt = Hh.prompt_of(g).to(DEV)
     run = _runner(g, ge, M, T, P)
     assert run.inner is not None

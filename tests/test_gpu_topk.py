@@ -189,7 +189,7 @@ def test_captured_target_verify_applies_top_k_and_only_a_matching_runner_uses_it
     from triforce_amd.utils import graph_infer as Gm
     g, ge = engine20
     gamma, T, P, K = g["gamma"], 0.8, 0.95, 20
-    assert ge.top_k == K and "top_k" not in ge.sampling
+    assert ge.target_filters.top_k == K and "top_k" not in ge.sampling
     prompt = Hh.prompt_of(g).to(DEV)
     run = _runner(g, ge, K, T, P)
     assert run.inner is not None

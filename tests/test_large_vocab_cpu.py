@@ -105,6 +105,17 @@ def test_routing_predicate_picks_fused_large_or_torch():
     assert ops.topp_route(40000, 0.9, True, f32) == "large"
 
 
+def test_per_device_state_is_keyed_by_the_resolved_device_index(monkeypatch):
+    """The control block of tf_topp_probs_multi and the workspace of the _large forms are kept per device under one key: a
+    tensor on plain "cuda" belongs to the current device, not to device 0."""
+    from triforce_amd import ops
+    monkeypatch.setattr(torch.cuda, "current_device", lambda: 1)
+    assert ops._device_key("cuda") == ops._device_key("cuda:1") == ops._device_key(torch.device("cuda", 1)) == 1
+    assert ops._device_key("cuda:0") == 0 != ops._device_key("cuda")
+    monkeypatch.setattr(torch.cuda, "current_device", lambda: 0)
+    assert ops._device_key("cuda") == ops._device_key("cuda:0") == 0 and ops._device_key("cuda:1") == 1
+
+
 def test_norm_logits_routes_by_the_predicate(monkeypatch):
     """norm_logits hands fp32 device logits to the op the predicate names, with or without top-k, and everything else to the
     torch restatement.  (A stand-in tensor class reports ``is_cuda``: the real kernels run in tests/test_gpu_large_vocab.py.)"""

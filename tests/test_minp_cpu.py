@@ -135,6 +135,46 @@ def test_min_p_zero_is_the_call_without_the_keyword(monkeypatch):
     assert not calls and torch.is_tensor(out)                       # top_p <= 0: the torch restatement
 
 
+def test_filters_normalise_once_and_compare_by_field():
+    from triforce_amd.utils.sampling import Filters
+    assert Filters(.6, .9, 0, -1.0) == Filters(.6, .9, -1, 0.0) == Filters(.6, .9)
+    assert hash(Filters(.6, .9, 0, -1.0)) == hash(Filters(.6, .9)) and len({Filters(.6, .9, -5), Filters(.6, .9, 0, -0.0)}) == 1
+    f = Filters(.6, .9, -7, -0.5)
+    assert (f.temperature, f.top_p, f.top_k, f.min_p) == (.6, .9, -1, 0.0)
+    for other in (Filters(.7, .9), Filters(.6, .8), Filters(.6, .9, 5), Filters(.6, .9, min_p=.1), Filters(.6, .9, 5, .1)):
+        assert other != Filters(.6, .9)
+    assert [Filters(.6, .9, k, m).target_only for k, m in [(-1, 0.0), (0, -1.0), (5, 0.0), (-1, 0.1), (5, 0.1)]] \
+        == [False, False, True, True, True]
+    # as keywords of norm_logits: ``min_p`` only when it is on
+    assert Filters(.6, .9, 0).kw() == dict(temperature=.6, top_k=-1, top_p=.9)
+    assert Filters(.6, .9, 5, .1).kw() == dict(temperature=.6, top_k=5, top_p=.9, min_p=.1)
+    with pytest.raises(Exception):
+        f.top_k = 3                                                 # frozen
+
+
+def test_dist_engine_serves_no_target_only_filter():
+    """The tensor-parallel engine normalises at whatever temperature / top-p it is handed and has no top-k or min-p: its
+    verify_probs_ids answers None for either, before the ``llm`` is touched."""
+    import types
+    from triforce_amd.utils.decoding import _DistEngine
+    from triforce_amd.utils.sampling import Filters
+
+    class Llm:
+        temperature, top_p, device, draft = 0.6, 0.9, "cpu", None
+        config = types.SimpleNamespace(model_config=None)
+        kv_cache = retrieval_cache = draft_cache = None
+
+        def verify_probs_ids(self, *a, **kw):
+            raise AssertionError("the llm was called")
+    ge = _DistEngine(Llm())
+    assert ge.verify_probs_ids([1, 2, 3], 0.6, 0.9, top_k=5) is None
+    assert ge.verify_probs_ids([1, 2, 3], 0.6, 0.9, min_p=0.1) is None
+    assert ge.verify_probs_ids([1, 2, 3], temperature=0.6, top_k=5, top_p=0.9, min_p=0.1) is None
+    with pytest.raises(AssertionError, match="the llm was called"):
+        ge.verify_probs_ids([1, 2, 3], 0.7, 0.8, top_k=0, min_p=-1.0)      # no filter of the target's own: handed on
+    assert ge.serves(Filters(0.7, 0.8)) and not ge.serves(Filters(0.6, 0.9, 5)) and not ge.serves(Filters(0.6, 0.9, min_p=0.1))
+
+
 def test_only_on_chip_takes_the_min_p_flag():
     from triforce_amd.utils import cli
     assert any(row[0] == "--min_p" for row in cli.SCRIPT_OWN["on_chip"])
@@ -160,7 +200,7 @@ def test_min_p_1_on_the_target_tier_emits_the_greedy_stream(cpu_ops):
     from triforce_amd.models.modeling_llama_68m import LlamaForCausalLM as LlamaForCausalLM_68M
     from triforce_amd.utils.decoding import TriForce, TriForceRunner
     from triforce_amd.utils.graph_infer import GraphInferenceEngine
-    from triforce_amd.utils.sampling import UniformSource
+    from triforce_amd.utils.sampling import Filters, UniformSource
     from oracle import specs
     g = Hh.load_golden("small_gamma6")
     gamma = g["gamma"]
@@ -171,9 +211,9 @@ def test_min_p_1_on_the_target_tier_emits_the_greedy_stream(cpu_ops):
     ge = GraphInferenceEngine(target, FlashSimpleCache(target, g["prefill"] + g["gen_len"] + 16),
                               RetrievalCache(target, max_budget=g["budget"], prefill=g["prefill"], gamma=gamma, chunk_size=g["chunk"]),
                               draft, StreamingLLMEvictionCache(draft, start_size=16, recent_size=256 - 16 - gamma, gamma=gamma))
-    assert ge.min_p == 0.0
+    assert ge.target_filters.min_p == 0.0
     ge.initialize_eager(gamma, probs=True, temperature=1.0, top_p=1.0, min_p=1.0)
-    assert ge.min_p == 1.0 and ge.top_k == -1 and "min_p" not in ge.sampling     # the draft tiers' capture arguments never see it
+    assert ge.target_filters == Filters(1.0, 1.0, -1, 1.0) and "min_p" not in ge.sampling     # the draft tiers' capture arguments never see it
     res = TriForce(Hh.FakeTokenizer(), ge, Hh.prompt_of(g), gamma=gamma, max_len=g["gen_len"], top_p=1.0, temperature=1.0,
                    min_p=1.0, rng=UniformSource("cpu", values=Hh.fixed_uniforms(seed=41)), return_details=True)
     gaps = Hh.teacher_forced_gaps(g, res["tokens"], tsd, dsd)
@@ -187,12 +227,12 @@ def test_min_p_1_on_the_target_tier_emits_the_greedy_stream(cpu_ops):
                                       (0.05, 0.3, False), (1.0, 1.0, True)]:
         ge.initialize_eager(gamma, probs=True, temperature=1.0, top_p=1.0, top_k=20, min_p=engine_m)
         run = TriForceRunner(Hh.FakeTokenizer(), ge, gamma, top_k=20, top_p=1.0, temperature=1.0, min_p=runner_m)
-        assert run._captured_min_p() is match and run._captured_filters() is match, (runner_m, engine_m)
-        assert run._captured_top_k() is True                       # (keeps its meaning: top-k alone)
-        assert ge._captured_with(1.0, 1.0, 20, runner_m) is match
-        assert ge._captured_with(1.0, 1.0, 20, min_p=runner_m) is match
-        assert ge._captured_with(1.0, 1.0, 20) is (engine_m <= 0)  # callers that pass no min_p mean "none"
-        assert ge._captured_with(1.0, 1.0, 21, runner_m) is False
+        assert run._served() is match and ge.serves(run.filters) is match, (runner_m, engine_m)
+        assert run.filters.top_k == ge.target_filters.top_k == 20   # (the top-k half of the rule holds throughout)
+        assert ge.serves(Filters(1.0, 1.0, 20, runner_m)) is match
+        assert ge.serves(Filters(1.0, 1.0, 20, min_p=runner_m)) is match
+        assert ge.serves(Filters(1.0, 1.0, 20)) is (engine_m <= 0)  # callers that pass no min_p mean "none"
+        assert ge.serves(Filters(1.0, 1.0, 21, runner_m)) is False
     # an engine without the attribute (tensor-parallel, Sequoia, stubs) captured without min-p
 
     class Bare:
@@ -200,6 +240,6 @@ def test_min_p_1_on_the_target_tier_emits_the_greedy_stream(cpu_ops):
         sampling = ge.sampling
     run = TriForceRunner(Hh.FakeTokenizer(), ge, gamma, top_p=1.0, temperature=1.0, min_p=0.3)
     run.ge = Bare()
-    assert run._captured_min_p() is False and run._filter_kw() == {}
-    run.min_p = 0.0
-    assert run._captured_min_p() is True
+    assert run._served() is False                                  # no ``serves``: captured without top-k and min-p
+    run.filters = Filters(1.0, 1.0, min_p=0.0)
+    assert run._served() is True

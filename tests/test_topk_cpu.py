@@ -62,7 +62,7 @@ def test_top_k_1_on_the_target_tier_emits_the_greedy_stream(cpu_ops):
     from triforce_amd.models.modeling_llama_68m import LlamaForCausalLM as LlamaForCausalLM_68M
     from triforce_amd.utils.decoding import TriForce, TriForceRunner
     from triforce_amd.utils.graph_infer import GraphInferenceEngine
-    from triforce_amd.utils.sampling import UniformSource
+    from triforce_amd.utils.sampling import Filters, UniformSource
     from oracle import specs
     g = Hh.load_golden("small_gamma6")
     gamma = g["gamma"]
@@ -73,9 +73,9 @@ def test_top_k_1_on_the_target_tier_emits_the_greedy_stream(cpu_ops):
     ge = GraphInferenceEngine(target, FlashSimpleCache(target, g["prefill"] + g["gen_len"] + 16),
                               RetrievalCache(target, max_budget=g["budget"], prefill=g["prefill"], gamma=gamma, chunk_size=g["chunk"]),
                               draft, StreamingLLMEvictionCache(draft, start_size=16, recent_size=256 - 16 - gamma, gamma=gamma))
-    assert ge.top_k == -1
+    assert ge.target_filters.top_k == -1
     ge.initialize_eager(gamma, probs=True, temperature=1.0, top_p=1.0, top_k=1)
-    assert ge.top_k == 1 and "top_k" not in ge.sampling            # the draft tiers' capture arguments never see it
+    assert ge.target_filters.top_k == 1 and "top_k" not in ge.sampling            # the draft tiers' capture arguments never see it
     res = TriForce(Hh.FakeTokenizer(), ge, Hh.prompt_of(g), gamma=gamma, max_len=g["gen_len"], top_k=1, top_p=1.0, temperature=1.0,
                    rng=UniformSource("cpu", values=Hh.fixed_uniforms(seed=41)), return_details=True)
     gaps = Hh.teacher_forced_gaps(g, res["tokens"], tsd, dsd)
@@ -88,5 +88,5 @@ def test_top_k_1_on_the_target_tier_emits_the_greedy_stream(cpu_ops):
     for runner_k, engine_k, match in [(1, 1, True), (-1, 1, False), (1, -1, False), (0, -1, True), (-1, 0, True), (20, 50, False)]:
         ge.initialize_eager(gamma, probs=True, temperature=1.0, top_p=1.0, top_k=engine_k)
         run = TriForceRunner(Hh.FakeTokenizer(), ge, gamma, top_k=runner_k, top_p=1.0, temperature=1.0)
-        assert run._captured_top_k() is match, (runner_k, engine_k)
-        assert ge._captured_with(1.0, 1.0, runner_k) is match
+        assert run._served() is match, (runner_k, engine_k)
+        assert ge.serves(Filters(1.0, 1.0, runner_k)) is match

@@ -1520,12 +1520,25 @@ TOPP_MULTI = _os.environ.get("TRIFORCE_TOPP_MULTI", "1") != "0"
 _topp_multi_state = {}
 
 
+def _device_key(device):
+    """The key of per-device state: the device's index, a device without one ("cuda") being the current device."""
+    dev = torch.device(device)
+    return torch.cuda.current_device() if dev.index is None else dev.index
+
+
+def _probs_like(logits):
+    """The output of a normaliser over (rows, V) fp32 device logits, behind the checks all of them make."""
+    _dev(logits)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()
+    return torch.empty_like(logits)
+
+
 def _topp_multi(device):
     """(control block, workspace) of tf_topp_probs_multi for this device, allocated at the first call OUTSIDE a capture (a
     graph's warm-up passes always come first); None while capturing without one.  One per device: the launches of a process are
     stream-ordered or synchronised against each other (warm-up stream -> capture -> replays); a caller that runs top-p on two
     streams at once sets TRIFORCE_TOPP_MULTI=0."""
-    key = torch.device(device).index or 0
+    key = _device_key(device)
     st = _topp_multi_state.get(key)
     if st is None:
         if torch.cuda.is_current_stream_capturing():
@@ -1542,9 +1555,7 @@ def topp_probs(logits, temperature, top_p, panel_max=None):
     workgroups with in-launch hand-offs (tf_topp_probs_multi) where the shape allows, else one workgroup per row
     (tf_topp_probs); bit-identical.  ``panel_max``: the per-panel row maxima the lm_head GEMM left (ops.linear(...,
     out_f32=True, ss_out=...)): the multi-workgroup form then skips its first hand-off."""
-    _dev(logits)
-    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()
-    probs = torch.empty_like(logits)
+    probs = _probs_like(logits)
     rows, V = logits.shape
     # (<= 16 rows: from 17 rows the launch has 8 slices of 4 000 entries per row — 36.8 -> 30.2 us on model-like rows, but
     #  52.6 -> 81.5 on near-flat ones: profiles/r06_topp_one_workgroup_vs_multi.jsonl; those calls keep one workgroup per row)
@@ -1566,9 +1577,7 @@ def topk_topp_probs(logits, temperature, top_k, top_p):
     """softmax(top_p_filter(top_k_filter(logits / temperature))) for (rows, V) fp32 logits, V <= 32768 (above: topk_topp_probs_large), top_k >= 1 — one fused
     kernel, one workgroup per row (tf_topk_topp_probs): every entry tied with the k-th value survives the top-k filter, the
     rest is tf_topp_probs over the survivors; top_k >= V is tf_topp_probs bit for bit."""
-    _dev(logits)
-    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()
-    probs = torch.empty_like(logits)
+    probs = _probs_like(logits)
     hip.check(hip.lib().tf_topk_topp_probs(_ptr(logits), _ptr(probs), logits.shape[0], logits.shape[1], float(temperature),
                                            int(top_k), float(top_p), _stream()), "tf_topk_topp_probs")
     return probs
@@ -1603,8 +1612,7 @@ def _topp_large_ws(device, rows, V):
     """Workspace of the _large normalisers for this device: allocated (or grown) at a call OUTSIDE a capture — a graph's
     warm-up passes always come first — and then kept, so a captured launch never allocates.  One per device: the launches of a
     process are stream-ordered or synchronised against each other, as for _topp_multi."""
-    dev = torch.device(device)
-    key = torch.cuda.current_device() if dev.index is None else dev.index
+    key = _device_key(device)
     need = topp_large_ws_bytes(rows, V)
     bufs = _topp_large_state.setdefault(key, [])
     if not bufs or bufs[-1].numel() < need:
@@ -1618,34 +1626,28 @@ def _topp_large_ws(device, rows, V):
     return bufs[-1]
 
 
-def _topp_large_call(logits, launch):
-    """probs for (rows, V) fp32 logits through ``launch(logits_ptr, probs_ptr, rows, V, ws_ptr, ws_bytes)``, at most
-    TOPP_LARGE_MAX_ROWS rows per launch (stream-ordered: they share the workspace)."""
-    _dev(logits)
-    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()
-    probs = torch.empty_like(logits)
+def _topp_large_call(name, logits, *args):
+    """probs for (rows, V) fp32 logits through the C entry ``name``(logits, probs, rows, V, *args, workspace, bytes, stream), at
+    most TOPP_LARGE_MAX_ROWS rows per launch (stream-ordered: they share the workspace)."""
+    probs = _probs_like(logits)
     rows, V = logits.shape
+    launch = getattr(hip.lib(), name)
     ws = _topp_large_ws(logits.device, min(rows, TOPP_LARGE_MAX_ROWS), V)
     for r0 in range(0, rows, TOPP_LARGE_MAX_ROWS):
         n = min(TOPP_LARGE_MAX_ROWS, rows - r0)
-        launch(_ptr(logits[r0:r0 + n]), _ptr(probs[r0:r0 + n]), n, V, _ptr(ws), ws.numel())
+        hip.check(launch(_ptr(logits[r0:r0 + n]), _ptr(probs[r0:r0 + n]), n, V, *args, _ptr(ws), ws.numel(), _stream()), name)
     return probs
 
 
 def topp_probs_large(logits, temperature, top_p):
     """softmax(top_p_filter(logits / temperature)) for (rows, V) fp32 logits, V <= 262144 — tf_topp_probs_large: one workgroup
     per row, the row streamed through a per-device workspace; bit-identical to topp_probs where both apply."""
-    L = hip.lib()
-    return _topp_large_call(logits, lambda lg, pr, n, V, ws, nb: hip.check(
-        L.tf_topp_probs_large(lg, pr, n, V, float(temperature), float(top_p), ws, nb, _stream()), "tf_topp_probs_large"))
+    return _topp_large_call("tf_topp_probs_large", logits, float(temperature), float(top_p))
 
 
 def topk_topp_probs_large(logits, temperature, top_k, top_p):
     """topk_topp_probs for (rows, V) fp32 logits, V <= 262144, top_k >= 1 — tf_topk_topp_probs_large."""
-    L = hip.lib()
-    return _topp_large_call(logits, lambda lg, pr, n, V, ws, nb: hip.check(
-        L.tf_topk_topp_probs_large(lg, pr, n, V, float(temperature), int(top_k), float(top_p), ws, nb, _stream()),
-        "tf_topk_topp_probs_large"))
+    return _topp_large_call("tf_topk_topp_probs_large", logits, float(temperature), int(top_k), float(top_p))
 
 
 def minp_probs(logits, temperature, top_k, top_p, min_p):
@@ -1653,9 +1655,7 @@ def minp_probs(logits, temperature, top_k, top_p, min_p):
     minp_probs_large), 0 < min_p <= 1 — tf_minp_probs, one workgroup per row: behind the select of topp_probs /
     topk_topp_probs an entry stays iff e_i = expf(x_i - max) >= min_p.  top_k <= 0 or top_k >= V: no top-k filter.  Where
     min-p removes nothing the output is topp_probs' / topk_topp_probs' (one workgroup per row) bit for bit."""
-    _dev(logits)
-    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()
-    probs = torch.empty_like(logits)
+    probs = _probs_like(logits)
     hip.check(hip.lib().tf_minp_probs(_ptr(logits), _ptr(probs), logits.shape[0], logits.shape[1], float(temperature),
                                       int(top_k), float(top_p), float(min_p), _stream()), "tf_minp_probs")
     return probs
@@ -1664,10 +1664,7 @@ def minp_probs(logits, temperature, top_k, top_p, min_p):
 def minp_probs_large(logits, temperature, top_k, top_p, min_p):
     """minp_probs for (rows, V) fp32 logits, V <= 262144 — tf_minp_probs_large, the row streamed through the per-device
     workspace of topp_probs_large; bit-identical to minp_probs where both apply."""
-    L = hip.lib()
-    return _topp_large_call(logits, lambda lg, pr, n, V, ws, nb: hip.check(
-        L.tf_minp_probs_large(lg, pr, n, V, float(temperature), int(top_k), float(top_p), float(min_p), ws, nb, _stream()),
-        "tf_minp_probs_large"))
+    return _topp_large_call("tf_minp_probs_large", logits, float(temperature), int(top_k), float(top_p), float(min_p))
 
 
 # Rows of normalised hidden state that DecoderLayers.head scores per lm_head GEMM when it is asked for the prompt's

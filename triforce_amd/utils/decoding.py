@@ -17,7 +17,7 @@ import torch
 
 from .. import ops
 from .misc import log_csv, spec_stream
-from .sampling import UniformSource, norm_logits, sample
+from .sampling import Filters, UniformSource, norm_logits, sample
 
 PAD_TOKEN = 100            # filler id of verify_tokens / pass_tokens (decoding.py:94,177)
 
@@ -46,10 +46,10 @@ def Autoregressive(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, to
             raise NotImplementedError(refusal)
         lp = torch.empty(max_len + 1, dtype=torch.float32, device=device)
     rng = rng or UniformSource(device)
-    mp = _min_p_kw(min_p)
+    kw = Filters(temperature, top_p, top_k, min_p).kw()
     eng.kv_cache.reset()
     logits = graph_engine.inference(input_ids=input_ids)
-    next_token = sample(norm_logits(logits[:, -1, :], temperature=temperature, top_k=top_k, top_p=top_p, **mp), rng=rng)
+    next_token = sample(norm_logits(logits[:, -1, :], **kw), rng=rng)
     if lp is not None:
         ops.token_logprobs(logits[:, -1, :], next_token.view(-1), out=lp[0:1])
     toks = [next_token]
@@ -60,7 +60,7 @@ def Autoregressive(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, to
         (lambda t: eng.model(input_ids=t, kv_cache=eng.kv_cache, graph_cache=None).logits)
     while n < max_len:      # no host sync inside the loop: the sampled token never leaves the device
         logits = step(next_token)
-        next_token = sample(norm_logits(logits[:, -1, :], temperature=temperature, top_k=top_k, top_p=top_p, **mp), rng=rng)
+        next_token = sample(norm_logits(logits[:, -1, :], **kw), rng=rng)
         toks.append(next_token)
         n += 1
         if lp is not None:                  # device targets, the step's own logits (a graph's static buffer until its next replay)
@@ -77,11 +77,6 @@ def Autoregressive(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, to
         if return_tokens:
             return n / (time2 - time1), ids
     return n / (time2 - time1)
-
-
-def _min_p_kw(min_p):
-    """``min_p`` for norm_logits only when the filter is on: without it the call is the one made before min-p existed."""
-    return dict(min_p=min_p) if min_p > 0 else {}
 
 
 def _logprobs_refusal(graph_engine, what):
@@ -481,9 +476,10 @@ class TriForceRunner:
     def __init__(self, tokenizer, graph_engine, gamma, top_k=-1, top_p=0.9, temperature=0.6, verbose=False, rng=None,
                  inclusive_accept=False, sync_record=None, rebuild_every=0, reanchor_at=0, logprobs=False,
                  prompt_logprobs=False, min_p=0.0):
-        # min_p: > 0 keeps a token of the TARGET's distribution (first token, target verify) only if its probability is at least
-        #              min_p times the most likely token's, behind top-k / top-p; the draft tiers stay unfiltered
-        self.min_p = float(min_p) if min_p > 0 else 0.0
+        # filters: what the TARGET's distribution (first token, target verify) is normalised with.  top_k > 0 and min_p > 0 (a
+        #              token stays only if its probability is at least min_p times the most likely token's, behind top-k / top-p:
+        #              DESIGN section 27) apply to it alone; the draft tiers stay unfiltered
+        self.filters = Filters(temperature, top_p, top_k, min_p)
         # logprobs: keep the log-probability (temperature 1, unfiltered: DESIGN section 23) of every emitted token, scored on the
         #              device from the logits of the verify that produced it — one launch per step, no host read before stats()
         # prompt_logprobs: prefill() also scores the prompt, log p(input_ids[i + 1] | input_ids[:i + 1]) for i = 0 .. n - 2
@@ -509,7 +505,7 @@ class TriForceRunner:
         #              one-shot all-reduce has timed out — its outputs are NaN-filled from then on, csrc/allreduce.hip)
         self.health = None
         self.tokenizer, self.ge, self.eng = tokenizer, graph_engine, graph_engine.engine
-        self.gamma, self.top_k, self.top_p, self.temperature, self.verbose = gamma, top_k, top_p, temperature, verbose
+        self.gamma, self.verbose = gamma, verbose
         if self.logprobs or self.want_prompt_logprobs:  # (refused before anything is captured or allocated)
             refusal = self._extend_refusal("logprobs / prompt_logprobs")
             if refusal is not None:
@@ -702,12 +698,11 @@ class TriForceRunner:
         if info is None or info.get("role") != "target" or "calibration" in info:
             return None
         from ..models import aligned
-        return aligned.calibrate_engine(self.ge, self.gamma, self.temperature, self.top_p)
+        return aligned.calibrate_engine(self.ge, self.gamma, self.filters.temperature, self.filters.top_p)
 
     @torch.inference_mode()
     def start(self, logits):
-        probs = norm_logits(logits[:, -1, :], temperature=self.temperature, top_k=self.top_k, top_p=self.top_p,
-                            **_min_p_kw(self.min_p))
+        probs = norm_logits(logits[:, -1, :], **self.filters.kw())
         self.next_token = int(sample(probs, rng=self.rng))
         if self.verbose:
             spec_stream(self.next_token, self.tokenizer, "cyan")
@@ -736,43 +731,16 @@ class TriForceRunner:
         positions / slot / key count, and the verify reads its tokens from the shared token buffer, where the inner graphs left
         [next, t_1 .. t_g2]: the chain behind the last inner record is one graph replay, no set-up launch.  An eager or rebuild
         step still sets its verify up from the host."""
-        ge = self.ge
-        if self.inner is None or self.sync_record is not None or self.inclusive_accept or not self._captured_filters() \
-                or (self.temperature, self.top_p) != (ge.sampling["temperature"], ge.sampling["top_p"]):
+        if self.inner is None or self.sync_record is not None or self.inclusive_accept or not self._served():
             return None
-        return ge.verify_sets(self.gamma)
+        return self.ge.verify_sets(self.gamma)
 
-    def _captured_top_k(self):
-        """The engine's captured target verify applies THIS runner's top-k, so its probabilities may be used.  An engine that
-        has no ``top_k`` (tensor-parallel, Sequoia) captured without one: only a runner without top-k takes its fast routes."""
-        captured = getattr(self.ge, "top_k", None)
-        if captured is None:
-            return self.top_k <= 0
-        return (captured if captured > 0 else -1) == (self.top_k if self.top_k > 0 else -1)
-
-    def _captured_min_p(self):
-        """The same for min-p: the engine's captured target verify applies THIS runner's min-p (an engine without ``min_p``
-        captured without one)."""
-        captured = getattr(self.ge, "min_p", None)
-        if captured is None:
-            return self.min_p <= 0
-        return (captured if captured > 0 else 0.0) == self.min_p
-
-    def _captured_filters(self):
-        """The captured target verify's top-k AND min-p are this runner's: what every fast route asks."""
-        return self._captured_top_k() and self._captured_min_p()
-
-    def _top_k_kw(self):
-        """``top_k`` for the verify entry points of an engine that takes one."""
-        return {} if getattr(self.ge, "top_k", None) is None else dict(top_k=self.top_k)
-
-    def _filter_kw(self):
-        """``top_k`` / ``min_p`` for the verify entry points of an engine that takes them (one without the attribute gets the
-        filter through the eager norm_logits route: _captured_filters() keeps it off the fast routes)."""
-        kw = self._top_k_kw()
-        if getattr(self.ge, "min_p", None) is not None:
-            kw["min_p"] = self.min_p
-        return kw
+    def _served(self):
+        """The engine's captured target verify was normalised with exactly THIS runner's filters (``serves``: DESIGN section 28),
+        so its probabilities may be used: what every fast verify route asks.  An engine without ``serves`` captured
+        without top-k and min-p."""
+        serves = getattr(self.ge, "serves", None)
+        return serves(self.filters) if serves is not None else not self.filters.target_only
 
     @torch.inference_mode()
     def step(self):
@@ -808,6 +776,7 @@ class TriForceRunner:
         self.rebuilds += int(rebuild)
         rebuild = rebuild or reanchor                                  # (one rebuild serves both)
         eager = self.eager_every > 0 and (len(self.counts) + 1) % self.eager_every == 0
+        served = self._served()
         sets = self._device_sets()
         on_device = sets is not None and not rebuild and not eager
         logits = None                                                  # (set by the last route below only)
@@ -816,20 +785,18 @@ class TriForceRunner:
                 ge.sync_verify_lengths(gamma)                          # stale (first step, after an eager / rebuild step): one launch each
             tg = ge.target_graphs[len(ids)]
             probs, verify_tokens = tg.replay_in_place(), tg.ids
-        elif self._captured_filters() and not rebuild and not eager and hasattr(ge, "verify_probs_ids") and len(ids) <= 32 \
-                and (fast := ge.verify_probs_ids(ids, self.temperature, self.top_p, **self._filter_kw())) is not None:
+        elif served and not rebuild and not eager and hasattr(ge, "verify_probs_ids") and len(ids) <= 32 \
+                and (fast := ge.verify_probs_ids(ids, **self.filters.kw())) is not None:
             # captured forward + temperature / top-p: ids, positions and lengths set by ONE launch (ids as kernel arguments)
             probs, verify_tokens = fast
         else:
             verify_tokens = bufs.to_device(ids)
-            if self._captured_filters() and hasattr(ge, "verify_probs"):    # one hipGraph: forward + temperature / top-k / top-p
-                probs = ge.verify_probs(verify_tokens, self.temperature, self.top_p, rebuild_retrieval=rebuild, eager=eager,
-                                        **self._filter_kw())
+            if served and hasattr(ge, "verify_probs"):                 # one hipGraph: forward + temperature / top-k / top-p
+                probs = ge.verify_probs(verify_tokens, rebuild_retrieval=rebuild, eager=eager, **self.filters.kw())
             else:
                 logits = ge.inference(input_ids=verify_tokens, rebuild_retrieval=True) if rebuild \
                     else (ge.inference(input_ids=verify_tokens, eager=True) if eager else ge.inference(input_ids=verify_tokens))
-                probs = norm_logits(logits[0], temperature=self.temperature, top_k=self.top_k, top_p=self.top_p,
-                                    **_min_p_kw(self.min_p))
+                probs = norm_logits(logits[0], **self.filters.kw())
         if getattr(bufs, "rows_generation", None) is not None:
             # spec_rows is a view of the retrieval-verify graph's static output: nothing may have replayed that graph
             # between Middle_Spec's return and this read (the target verify above is a different graph)
@@ -1196,7 +1163,13 @@ class _DistEngine:
     def replay_draft(self, gamma_offset):
         return self.llm.replay_draft(gamma_offset)
 
-    def verify_probs_ids(self, ids, temperature, top_p):
+    def serves(self, filters):
+        """The verify is normalised eagerly at whatever temperature and top-p it is handed; it has no top-k or min-p."""
+        return not filters.target_only
+
+    def verify_probs_ids(self, ids, temperature, top_p, top_k=-1, min_p=0.0):
+        if not self.serves(Filters(temperature, top_p, top_k, min_p)):
+            return None
         return self.llm.verify_probs_ids(ids, temperature, top_p)
 
     @torch.inference_mode()
@@ -1256,9 +1229,10 @@ def Baseline_Dist(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, top
                                   "Baseline_Dist (tensor-parallel loop)")
     llm = graph_engine
     rng = rng or UniformSource(llm.device, seed=1)
+    kw = Filters(temperature, top_p, top_k).kw()
     llm.reset()
     logits = llm.prefill(input_ids=input_ids)
-    next_token = sample_dist(norm_logits(logits[:, -1, :], temperature=temperature, top_k=top_k, top_p=top_p), rng)
+    next_token = sample_dist(norm_logits(logits[:, -1, :], **kw), rng)
     gen_tokens = torch.zeros((input_ids.size(0), max_len), dtype=torch.long, device=input_ids.device)
     n = 0
     check = getattr(llm, "check_exchange", None)
@@ -1266,7 +1240,7 @@ def Baseline_Dist(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, top
     time1 = time.time()
     while n < max_len:
         logits = llm.inference(input_ids=next_token)
-        next_token = sample_dist(norm_logits(logits[:, -1, :], temperature=temperature, top_k=top_k, top_p=top_p), rng)
+        next_token = sample_dist(norm_logits(logits[:, -1, :], **kw), rng)
         gen_tokens[:, n] = next_token.squeeze()
         n += 1
         if check is not None and n % 32 == 0:          # a timed-out exchange NaN-fills its outputs: stop, don't emit

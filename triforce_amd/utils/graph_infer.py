@@ -13,7 +13,7 @@ from typing import Optional
 import torch
 
 from .. import ops
-from .sampling import norm_logits
+from .sampling import Filters, norm_logits
 
 
 # Target prefill: the reference feeds 128 tokens per forward (graph_infer.py:30-37, TP_llama.py:246-250), which at
@@ -198,21 +198,6 @@ def _capture_error_mode():
     except Exception:
         pass
     return "global"
-
-
-def _norm_top_k(top_k):
-    """Every top_k <= 0 means "no top-k filter" (reference utils/sampling.py:16): one value, -1, for comparisons."""
-    return int(top_k) if top_k > 0 else -1
-
-
-def _norm_min_p(min_p):
-    """Every min_p <= 0 means "no min-p filter": one value, 0.0, for comparisons."""
-    return float(min_p) if min_p > 0 else 0.0
-
-
-def _min_p_kw(min_p):
-    """``min_p`` for norm_logits only when the filter is on: without it the call is the one made before min-p existed."""
-    return dict(min_p=min_p) if min_p > 0 else {}
 
 
 def _graphable_cache():
@@ -438,7 +423,7 @@ class _TargetGraph:
     (``top_k`` > 0: tf_topk_topp_probs — the target tier is the only one the reference filters by top-k; ``min_p`` > 0:
     tf_minp_probs, one workgroup per row)."""
 
-    def __init__(self, engine, q_len, mempool, n_warmups, probs, temperature, top_p, ids=None, top_k=-1, min_p=0.0):
+    def __init__(self, engine, q_len, mempool, n_warmups, probs, filters, ids=None):
         dev = engine.model.device
         self.engine, self.q_len, self.probs = engine, q_len, probs
         self.cache = engine.kv_cache               # the graph reads and appends THIS cache's storage
@@ -455,7 +440,7 @@ class _TargetGraph:
             logits = engine.model(input_ids=self.ids, kv_cache=engine.kv_cache, graph_cache=None,
                                   position_ids=self.pos.unsqueeze(0), dev_len=(self.slot, self.sk)).logits
             if probs:
-                return logits, norm_logits(logits[0], temperature=temperature, top_k=top_k, top_p=top_p, **_min_p_kw(min_p))
+                return logits, norm_logits(logits[0], **filters.kw())
             return logits, None
 
         self.graph, (self.logits, self.out_probs) = _capture(run, (), mempool, n_warmups)
@@ -516,12 +501,10 @@ class GraphInferenceEngine:
         self.dev_len = None
         self.mempool = None
         self.sampling = dict(probs=False, temperature=0.6, top_p=0.9)
-        # top-k of the TARGET's verify distribution (reference decoding.py:62,90: the two draft tiers always run with -1).
-        # Not a key of ``sampling``: that dict is splatted into the draft / retrieval-verify capture functions.
-        self.top_k = -1
-        # min-p of the TARGET's verify distribution: like top_k it stays out of ``sampling``, so both draft
-        # tiers run unfiltered
-        self.min_p = 0.0
+        # what the TARGET's verify distribution is normalised with: temperature and top-p as in ``sampling``, plus the top-k
+        # (reference decoding.py:62,90: the two draft tiers always run with -1) and min-p that are never keys
+        # of ``sampling`` — that dict is splatted into the draft / retrieval-verify capture functions
+        self.target_filters = Filters(0.6, 0.9)
         # (1, rows, V) fp32 logits of the last target verify that went through verify_probs / verify_probs_ids — a captured
         # graph's static buffer or the eager forward's result; valid until the next target forward (what a runner with
         # ``logprobs`` scores; the replay_in_place route leaves them in its _TargetGraph.logits)
@@ -535,8 +518,7 @@ class GraphInferenceEngine:
         gc.collect()
         self.mempool = torch.cuda.graphs.graph_pool_handle()
         self.sampling = dict(probs=probs, temperature=temperature, top_p=top_p)
-        self.top_k = _norm_top_k(top_k)
-        self.min_p = _norm_min_p(min_p)
+        self.target_filters = Filters(temperature, top_p, top_k, min_p)
         common = dict(engine=self.engine, mempool=self.mempool, n_warmups=3, verbose=verbose, **self.sampling)
         # ONE token buffer is the static input of every draft graph (its first gamma_offset + 1 entries) and of the
         # retrieval-verify graph (its first gamma + 1): the decode loop writes drafted tokens straight into it (the
@@ -556,16 +538,14 @@ class GraphInferenceEngine:
             for q_len in sorted({1, gamma + 1, gamma + 2}):
                 # the two verify lengths read their tokens from the head of the shared token buffer (see _TargetGraph)
                 self.target_graphs[q_len] = _TargetGraph(self.engine, q_len, self.mempool, 3, probs and q_len > 1,
-                                                         temperature, top_p, ids=self.tok_buf[:, :q_len] if q_len > 1 else None,
-                                                         top_k=self.top_k, min_p=self.min_p)
+                                                         self.target_filters, ids=self.tok_buf[:, :q_len] if q_len > 1 else None)
         self.dev_len = None                        # cache length the verify graphs' device scalars encode (None: unknown)
         self.engine.clear_kv()
 
     def initialize_eager(self, gamma=6, probs=True, temperature=0.6, top_p=0.9, top_k=-1, min_p=0.0):
         """Same surface without graph capture (debugging / parity bisecting)."""
         self.sampling = dict(probs=probs, temperature=temperature, top_p=top_p)
-        self.top_k = _norm_top_k(top_k)
-        self.min_p = _norm_min_p(min_p)
+        self.target_filters = Filters(temperature, top_p, top_k, min_p)
         eng, kw = self.engine, self.sampling
         self.callables = {off: (lambda ids, off=off: eng.draft_run(input_ids=ids, gamma_offset=off, **kw))
                           for off in range(gamma + 3)}
@@ -595,23 +575,21 @@ class GraphInferenceEngine:
         tg = self.target_graphs.get(input_ids.shape[-1])
         return tg if (tg is not None and tg.cache is self.engine.kv_cache) else None   # cache swapped after capture: eager
 
-    @torch.inference_mode()
-    def _captured_with(self, temperature, top_p, top_k, min_p=0.0):
-        """The captured target verifies were normalised with exactly these settings (any top_k <= 0 is -1, any min_p <= 0
-        is 0.0)."""
-        return (temperature, top_p, _norm_top_k(top_k), _norm_min_p(min_p)) \
-            == (self.sampling["temperature"], self.sampling["top_p"], self.top_k, self.min_p)
+    def serves(self, filters):
+        """The captured target verifies were normalised with exactly these Filters: their probabilities may be used."""
+        return filters == self.target_filters
 
     @torch.inference_mode()
     def verify_probs(self, input_ids, temperature, top_p, rebuild_retrieval=False, eager=False, top_k=-1, min_p=0.0):
         """Target verify -> (rows, V) probabilities after temperature / top-k / top-p / min-p: one graph replay when captured with
         these settings, else the eager forward + norm_logits.  The result is valid until the next target forward."""
+        filters = Filters(temperature, top_p, top_k, min_p)
         tg = None if (eager or rebuild_retrieval) else self._target_graph(input_ids)
-        if tg is not None and tg.probs and self._captured_with(temperature, top_p, top_k, min_p):
+        if tg is not None and tg.probs and self.serves(filters):
             self.last_logits, probs = tg(input_ids)
             return probs
         logits = self.last_logits = self.inference(input_ids, rebuild_retrieval=rebuild_retrieval, eager=eager)
-        return norm_logits(logits[0], temperature=temperature, top_k=top_k, top_p=top_p, **_min_p_kw(min_p))
+        return norm_logits(logits[0], **filters.kw())
 
     @torch.inference_mode()
     def verify_probs_ids(self, ids, temperature, top_p, top_k=-1, min_p=0.0):
@@ -620,7 +598,7 @@ class GraphInferenceEngine:
         One launch sets ids, positions and lengths (tf_set_tokens) in front of the replay."""
         tg = self.target_graphs.get(len(ids))
         if tg is None or tg.cache is not self.engine.kv_cache or not tg.probs or not tg.ids.is_cuda \
-                or not self._captured_with(temperature, top_p, top_k, min_p):
+                or not self.serves(Filters(temperature, top_p, top_k, min_p)):
             return None
         self.last_logits, probs = tg(list(ids))
         return probs, tg.ids

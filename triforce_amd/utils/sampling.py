@@ -7,6 +7,8 @@ Tie rule: the reference sorts with torch.sort(descending=True), whose order amon
 implementation-defined; here the sort is *stable* (lowest token id first among equals) so greedy
 emulation (temperature=1, top_p->0) is deterministic on every device.
 """
+import dataclasses
+
 import torch
 from torch.nn import functional as F
 
@@ -28,39 +30,61 @@ def top_k_top_p_filter(logits: torch.Tensor, top_k: int = 0, top_p: float = 0.0)
     return logits
 
 
-def _norm_logits_min_p(logits, temperature, top_k, top_p, min_p):
-    """norm_logits with min_p > 0 (HF order: temperature -> top-k -> top-p -> min-p): a token stays only if
-    its probability is at least min_p times the most likely token's.  fp32 device logits with top_p > 0 take the fused kernels
-    (ops.minp_probs / ops.minp_probs_large), everything else the torch restatement below."""
-    route = ops.topp_route(logits.shape[-1], top_p, logits.is_cuda, logits.dtype)
-    if route == "fused":
-        return ops.minp_probs(logits.contiguous(), temperature, top_k, top_p, min_p)
-    if route == "large":
-        return ops.minp_probs_large(logits.contiguous(), temperature, top_k, top_p, min_p)
-    probs = F.softmax(top_k_top_p_filter(logits / temperature, top_k=top_k, top_p=top_p), dim=-1)
-    probs = probs.masked_fill(probs < min_p * probs.amax(dim=-1, keepdim=True), 0.0)
-    return probs / probs.sum(dim=-1, keepdim=True)
+@dataclasses.dataclass(frozen=True)
+class Filters:
+    """The sampling settings of one distribution, as one comparable value.  Every top_k <= 0 means "no top-k" and is kept as
+    -1, every min_p <= 0 means "no min-p" and is kept as 0.0 (reference utils/sampling.py:16), so two values are equal exactly
+    when they normalise alike: the rule by which an engine's captured target verify may stand in for a runner's own
+    (``serves``: DESIGN section 28)."""
+    temperature: float
+    top_p: float
+    top_k: int = -1
+    min_p: float = 0.0
+
+    def __post_init__(self):
+        if self.top_k <= 0:
+            object.__setattr__(self, "top_k", -1)
+        if self.min_p <= 0:
+            object.__setattr__(self, "min_p", 0.0)
+
+    @property
+    def target_only(self):
+        """Top-k or min-p is on: the filters of the TARGET's distribution that the two draft tiers never see."""
+        return self.top_k > 0 or self.min_p > 0
+
+    def kw(self):
+        """The keywords of norm_logits (and of the engines' verify entry points); ``min_p`` only when it is on: without it the
+        call is the one made before min-p existed."""
+        kw = dict(temperature=self.temperature, top_k=self.top_k, top_p=self.top_p)
+        if self.min_p > 0:
+            kw["min_p"] = self.min_p
+        return kw
+
+
+# route of ops.topp_route -> the ops wrappers without top-k and min-p, with top-k, with min-p (DESIGN section 28)
+_KERNELS = {"fused": ("topp_probs", "topk_topp_probs", "minp_probs"),
+            "large": ("topp_probs_large", "topk_topp_probs_large", "minp_probs_large")}
 
 
 def norm_logits(logits: torch.Tensor, temperature=0.6, top_k=-1, top_p=0.9, min_p=0.0) -> torch.Tensor:
-    """(rows, vocab) fp32 logits -> probabilities after temperature / top-k / top-p (/ min-p when ``min_p`` > 0)."""
+    """(rows, vocab) fp32 logits -> probabilities after temperature / top-k / top-p / min-p (HF order; a token passes min-p only
+    if its probability is at least min_p times the most likely token's: DESIGN section 27).  ops.topp_route names the form —
+    one fused kernel with the row in LDS, the same select with the row streamed through a workspace, or the torch restatement
+    — and the filters that are on name the kernel."""
     assert logits.dim() == 2
+    route = ops.topp_route(logits.shape[-1], top_p, logits.is_cuda, logits.dtype)
+    if route == "torch":
+        probs = F.softmax(top_k_top_p_filter(logits / temperature, top_k=top_k, top_p=top_p), dim=-1)
+        if min_p > 0.0:
+            probs = probs.masked_fill(probs < min_p * probs.amax(dim=-1, keepdim=True), 0.0)
+            probs = probs / probs.sum(dim=-1, keepdim=True)
+        return probs
+    plain, with_top_k, with_min_p = _KERNELS[route]         # (looked up on ops per call: tests and tools replace them by name)
     if min_p > 0.0:
-        return _norm_logits_min_p(logits, temperature, top_k, top_p, min_p)
-    if logits.is_cuda and top_k <= 0 and 0.0 < top_p and logits.shape[-1] <= ops.TOPP_MAX_VOCAB \
-            and logits.dtype == torch.float32:
-        return ops.topp_probs(logits.contiguous(), temperature, top_p)      # fused HIP kernel, no vocabulary sort
-    if logits.is_cuda and top_k > 0 and 0.0 < top_p and logits.shape[-1] <= ops.TOPP_MAX_VOCAB \
-            and logits.dtype == torch.float32:
-        return ops.topk_topp_probs(logits.contiguous(), temperature, top_k, top_p)   # the same kernel behind a top-k select
-    if ops.topp_route(logits.shape[-1], top_p, logits.is_cuda, logits.dtype) == "large":
-        # ops.TOPP_MAX_VOCAB < V <= ops.TOPP_LARGE_MAX_VOCAB: the same select with the row streamed through a workspace
-        if top_k > 0:
-            return ops.topk_topp_probs_large(logits.contiguous(), temperature, top_k, top_p)
-        return ops.topp_probs_large(logits.contiguous(), temperature, top_p)
-    logits = logits / temperature
-    logits = top_k_top_p_filter(logits, top_k=top_k, top_p=top_p)
-    return F.softmax(logits, dim=-1)
+        return getattr(ops, with_min_p)(logits.contiguous(), temperature, top_k, top_p, min_p)
+    if top_k > 0:
+        return getattr(ops, with_top_k)(logits.contiguous(), temperature, top_k, top_p)
+    return getattr(ops, plain)(logits.contiguous(), temperature, top_p)
 
 
 def max_fn(x):
