@@ -822,6 +822,37 @@ int tf_token_logprobs(const float* logits, int64_t row_stride, const int64_t* ta
 int tf_token_logprobs_ids(const float* logits, int64_t row_stride, const int64_t* host_ids, int rows, int V,
                           float* logprob, float* lse, void* stream);
 
+/* -------------------------------------------------------------------------------------------
+ * ATTENTION BIAS: the q / k / v / o projections of a model with `attention_bias` (the reference builds
+ * them with bias=config.attention_bias, models/modeling_llama.py:174-177).  Each entry is its bias-free neighbour — same
+ * operands, layouts, launch forms and gates — plus `bias`: fp16 [N], 8-byte aligned, in the ROW ORDER OF THE PACKED WEIGHT
+ * (q|k|v: triforce_amd.ops.rope_row_order(H, Hkv, D); plain: natural).  The contract:
+ *   - for an output element with fp32 accumulator acc (the COMPLETE K sum) and bias b:  y = fp16(acc + float(b)) — one
+ *     rounding, to nearest even;
+ *   - the other steps keep their rounding points: q and k rows — the fp16 RoPE arithmetic acts on y (the bias goes in BEFORE
+ *     the rotation); v rows — y is stored; plain with resid — out = fp16(resid + y) in fp16 as in tf_skinny_gemm_act, and
+ *     ss_out is taken from that sum;
+ *   - in a K-split form the bias is added once, where the partial sums have been folded, never per share;
+ *   - rows >= M are not written.
+ * tf_skinny_gemm_bias_act: tf_skinny_gemm_act with fp16 output (o_proj; the un-fused q|k|v projection of a <= 32-row block).
+ * tf_skinny_qkv_rope_bias_act / tf_skinny_qkv_rope_gqa_bias_act: tf_skinny_qkv_rope_act / tf_skinny_qkv_rope_gqa_act.
+ * TF_EINVAL before any launch: NULL or misaligned bias, out_f32 != 0, and every gate of the neighbour.  The 8-row-panel and
+ * the exchange forms (tensor-parallel shards) have no bias form.
+ * ------------------------------------------------------------------------------------------- */
+int tf_skinny_gemm_bias_act(const void* w_packed, const void* x, int64_t xs_m, int64_t xs_k, const void* ln_w, float eps,
+                            const float* ss_in, const void* resid, int64_t rs_m, int64_t rs_k, float* ss_out, void* y,
+                            int64_t ys_m, int64_t ys_k, int M, int N, int K, int out_f32, const void* bias, void* stream);
+int tf_skinny_qkv_rope_bias_act(const void* wqkv_packed, const void* x, int64_t xs_m, int64_t xs_k, const void* ln_w,
+                                float eps, const float* ss_in, const void* cos, const void* sin, const int64_t* positions,
+                                void* q_out, void* k_cache, void* v_cache, int64_t stride_t, int64_t stride_h, int slot0,
+                                const int32_t* slot0_dev, int M, int H, int D, int K, int rotate_k, const void* bias,
+                                void* stream);
+int tf_skinny_qkv_rope_gqa_bias_act(const void* wqkv_packed, const void* x, int64_t xs_m, int64_t xs_k, const void* ln_w,
+                                    float eps, const float* ss_in, const void* cos, const void* sin,
+                                    const int64_t* positions, void* q_out, void* k_cache, void* v_cache, int64_t stride_t,
+                                    int64_t stride_h, int slot0, const int32_t* slot0_dev, int M, int H, int Hkv, int D,
+                                    int K, int rotate_k, const void* bias, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

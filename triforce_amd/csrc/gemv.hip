@@ -152,6 +152,9 @@ __device__ __forceinline__ half4 xc_ld8(const h16* p) {
                                                        __HIP_MEMORY_SCOPE_SYSTEM));
 }
 
+typedef unsigned int sg_u32x4 __attribute__((ext_vector_type(4)));   // (native vectors: the bias travels as two of these)
+typedef unsigned int sg_u32x2 __attribute__((ext_vector_type(2)));
+
 struct SgRope {                       // arguments of the RoPE + KV-append epilogue (SG_QKV)
     const h16* cosb;                  // [max_pos][D] fp16
     const h16* sinb;
@@ -186,7 +189,7 @@ __device__ __forceinline__ half8 sg_normalise(half8 xv, half8 wv, float inv) {
     return o;
 }
 
-template <int MT, int MODE, bool NORM, int WAVES, int P, bool KSPLIT, bool XCHG = false>
+template <int MT, int KMODE, bool NORM, int WAVES, int P, bool KSPLIT, bool XCHG = false>
 // Argument order: what the PROLOGUE needs comes first, as plain pointers / scalars — weights, x and its two strides, the
 // norm partials and weights, K, M: 14 dwords, the most the hardware preloads into SGPRs with the dispatch (built with
 // -mllvm -amdgpu-kernarg-preload-count=14, triforce_amd/build.py): the first loads are issued without waiting for the
@@ -202,6 +205,14 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const half8* __
                                                                  SgRope rp, float* __restrict__ ss_out, SgKsplit kx,
                                                                  SgXchg xc) {
     const SgAct xa = {(int64_t)xa_sm, (int64_t)xa_sk};          // (32-bit in the argument list: two more preloaded dwords)
+    // Attention bias (SG_PLAIN_B / SG_QKV_B / SG_QKVG_B): the base mode's kernel with y = fp16(acc + float(b)) — ONE rounding
+    // of the complete K sum (after the waves' and the K-splits' partial sums have been folded), in front of the RoPE
+    // rotation / the residual add, which keep their own fp16 rounding points.  b: fp16 [N] in the weight's packed row order
+    // (q|k|v: ops.rope_row_order), 8-byte aligned.  The argument list is the bias-free one: the pointer travels in a field
+    // the mode does not use — resid in the q|k|v modes, rp.cosb in the plain mode.
+    constexpr int MODE = sg_base_mode(KMODE);
+    constexpr bool BIAS = sg_has_bias(KMODE);
+    static_assert(!BIAS || !XCHG, "the exchange form stays bias-free");
     static_assert(!XCHG || (MODE == SG_PLAIN && P == 1 && !KSPLIT), "the exchange form is the plain one-panel GEMM");
     constexpr bool GATEUP = MODE == SG_GATEUP;
     constexpr int NA = GATEUP ? 2 : 1;                       // weight streams (accumulator sets) per panel
@@ -413,8 +424,22 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const half8* __
     // wait for the argument segment stood in front of the first weight load of every o_proj / down_proj.
     unsigned xepoch = 0, xerr = 0;
     half4 rope_cs[MT], rope_sn[MT], res_pre[MT];
+    // BIAS: the panel's 16 bias values.  The address is wave-uniform (a wave finishes ONE panel), so they arrive through the
+    // scalar cache into SGPRs and cost the K loop no vector register — the bias-free forms' occupancy holds (DESIGN section
+    // 29); every lane picks the 4 values of its output rows 4 g + r at the epilogue.
+    sg_u32x4 bias_lo = {0, 0, 0, 0}, bias_hi = {0, 0, 0, 0};
     int64_t r_off = 0, y_off = 0;
     bool res_early = false;
+    // (read as CONSTANT memory — nothing writes the bias while a GEMM runs — which is what selects the scalar load.  It must
+    //  sit in wave-uniform control flow to stay in SGPRs: the forms without a norm prologue run prefetch_epi under
+    //  `c == c0`, which the compiler takes for divergent, so they fetch the bias behind the main K loop instead — in flight
+    //  across the tail batch and the merge of the waves.)
+    auto load_bias = [&]() {
+        typedef const sg_u32x4 __attribute__((address_space(4))) sg_cu4;
+        sg_cu4* bp = (sg_cu4*)((MODE == SG_PLAIN ? rp.cosb : resid) + __builtin_amdgcn_readfirstlane(panel) * 16);
+        bias_lo = bp[0];
+        bias_hi = bp[1];
+    };
     auto prefetch_epi = [&]() {
         if constexpr (XCHG) {
             if (epi) {
@@ -444,6 +469,7 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const half8* __
                 }
             }
         }
+        if constexpr (BIAS && NORM) load_bias();
         // (resid may alias y: every element is read and written by the same lane only.)
         r_off = (int64_t)(2 * panel + (g >> 1)) * ra.sk + 4 * (g & 1);   // this lane's 4 columns, piece form
         y_off = (int64_t)(2 * panel + (g >> 1)) * ya.sk + 4 * (g & 1);
@@ -506,6 +532,7 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const half8* __
 #endif
     }
     SG_STAMP(4);
+    if constexpr (BIAS && !NORM) load_bias();
     if constexpr (NORM) {
         // (norm-prologue forms: K = hidden, whose k-chunks divide evenly among the waves in every configuration that
         //  matters; the batch below would only cost them registers — a wave per SIMD on the gate|up form)
@@ -697,6 +724,15 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const half8* __
             }
         }
     }
+    half4 bias_pre = {0, 0, 0, 0};                               // this lane's rows: values 4 g .. 4 g + 3 of the 16
+    if constexpr (BIAS) {
+        // (g again, from the lane counter: keeping `g` itself alive across the K loop for this select cost the two-row-tile
+        //  8-wave plain form its 96th register and with it a wave per SIMD)
+        const int gb = (int)(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) >> 4);
+        const sg_u32x2 bsel = gb == 0 ? sg_u32x2{bias_lo.x, bias_lo.y} : gb == 1 ? sg_u32x2{bias_lo.z, bias_lo.w}
+                            : gb == 2 ? sg_u32x2{bias_hi.x, bias_hi.y} : sg_u32x2{bias_hi.z, bias_hi.w};
+        bias_pre = __builtin_bit_cast(half4, bsel);
+    }
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
         const int m = t * 16 + li;
@@ -720,7 +756,7 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const half8* __
             h16 val[4], oth[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                val[r] = (h16)s[r];
+                val[r] = BIAS ? (h16)(s[r] + (float)bias_pre[r]) : (h16)s[r];   // bias BEFORE the rotation, one rounding
                 oth[r] = (h16)__shfl_xor((float)val[r], 32, 64);         // rotary partner: lane g <-> g ^ 2 (exact)
             }
             if (m >= M) continue;
@@ -775,7 +811,7 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_kernel(const half8* __
                 } else {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        o[r] = (h16)s[r];
+                        o[r] = BIAS ? (h16)(s[r] + (float)bias_pre[r]) : (h16)s[r];
                         if (resid)               // residual + hidden, fp16 add
                             o[r] = hadd_rn(res_early ? res_pre[t][r] : resid[(int64_t)m * ra.sm + r_off + r], o[r]);
                         s2[r] = (float)o[r];
@@ -1199,10 +1235,11 @@ static int launch_sg_form(const SgArgs& a, const SgRope& rp, const SgKsplit& kx,
 
 template <int MODE, bool NORM>
 static int launch_sg(const SgArgs& a, const SgRope& rp, hipStream_t st) {
-    const SgForm f = sg_pick_form(MODE, NORM, a.M, a.N, a.K, g_sg_knobs);
+    constexpr int BASE = sg_base_mode(MODE);                      // a bias mode takes the form of its bias-free neighbour
+    const SgForm f = sg_pick_form(BASE, NORM, a.M, a.N, a.K, g_sg_knobs);
     // (the instrumented build stamps the forms that may split, and the exchange GEMM: no others, as before)
-    SgKsplit kx = {nullptr, nullptr, (f.P == 1 && MODE != SG_F32) ? sg_stamps_ptr() : nullptr};
-    const int ks = sg_ksplit(a, f, MODE, kx, st);
+    SgKsplit kx = {nullptr, nullptr, (f.P == 1 && BASE != SG_F32) ? sg_stamps_ptr() : nullptr};
+    const int ks = sg_ksplit(a, f, BASE, kx, st);
 #define SG_FORM(MT_, W_, P_) \
     if (f.MT == MT_ && f.WAVES == W_ && f.P == P_) return launch_sg_form<MT_, MODE, NORM, W_, P_>(a, rp, kx, ks, st)
     SG_FORM(1, SG_WAVES, 1);
@@ -1255,10 +1292,15 @@ extern "C" int tf_sg_workspace(void* ws, int64_t bytes) {
     return TF_OK;
 }
 
-extern "C" int tf_skinny_gemm_act(const void* w_packed, const void* x, int64_t xs_m, int64_t xs_k, const void* ln_w,
-                                  float eps, const float* ss_in, const void* resid, int64_t rs_m, int64_t rs_k,
-                                  float* ss_out, void* y, int64_t ys_m, int64_t ys_k, int M, int N, int K, int out_f32,
-                                  void* stream) {
+// A bias operand (the *_bias_act entry points): fp16 [N], read as 8-byte pieces.
+static bool sg_bias_ok(const void* bias) { return bias && (reinterpret_cast<uintptr_t>(bias) % 8) == 0; }
+
+// tf_skinny_gemm_act (biased = false, the call it always was) and tf_skinny_gemm_bias_act
+static int sg_plain_entry(const void* w_packed, const void* x, int64_t xs_m, int64_t xs_k, const void* ln_w, float eps,
+                          const float* ss_in, const void* resid, int64_t rs_m, int64_t rs_k, float* ss_out, void* y,
+                          int64_t ys_m, int64_t ys_k, int M, int N, int K, int out_f32, const void* bias, bool biased,
+                          void* stream) {
+    if (biased && (!sg_bias_ok(bias) || out_f32)) return TF_EINVAL;
     SgArgs a = {};
     a.wp = w_packed, a.x = x, a.ln_w = ln_w, a.resid = resid, a.y = y;
     a.xa = SgAct{xs_m, xs_k}, a.ra = SgAct{rs_m, rs_k}, a.ya = SgAct{ys_m, ys_k};
@@ -1267,9 +1309,31 @@ extern "C" int tf_skinny_gemm_act(const void* w_packed, const void* x, int64_t x
     if ((out_f32 && (resid || ss_out)) || (ss_in && !ln_w)) return TF_EINVAL;
     if (ys_m <= 0 || (!out_f32 && ys_k <= 0) || (resid && (rs_m <= 0 || rs_k <= 0))) return TF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const SgRope rp = {};
+    SgRope rp = {};
+    if (biased) {
+        rp.cosb = (const h16*)bias;                               // (the plain mode has no use for rp: see the kernel)
+        return ln_w ? launch_sg<SG_PLAIN_B, true>(a, rp, st) : launch_sg<SG_PLAIN_B, false>(a, rp, st);
+    }
     if (out_f32) return ln_w ? launch_sg<SG_F32, true>(a, rp, st) : launch_sg<SG_F32, false>(a, rp, st);
     return ln_w ? launch_sg<SG_PLAIN, true>(a, rp, st) : launch_sg<SG_PLAIN, false>(a, rp, st);
+}
+
+extern "C" int tf_skinny_gemm_act(const void* w_packed, const void* x, int64_t xs_m, int64_t xs_k, const void* ln_w,
+                                  float eps, const float* ss_in, const void* resid, int64_t rs_m, int64_t rs_k,
+                                  float* ss_out, void* y, int64_t ys_m, int64_t ys_k, int M, int N, int K, int out_f32,
+                                  void* stream) {
+    return sg_plain_entry(w_packed, x, xs_m, xs_k, ln_w, eps, ss_in, resid, rs_m, rs_k, ss_out, y, ys_m, ys_k, M, N, K,
+                          out_f32, nullptr, false, stream);
+}
+
+// tf_skinny_gemm_act with y = fp16(acc + float(bias[n])) in front of the residual add (o_proj of a model with attention
+// bias; its un-fused q|k|v projection).  fp16 output only.
+extern "C" int tf_skinny_gemm_bias_act(const void* w_packed, const void* x, int64_t xs_m, int64_t xs_k, const void* ln_w,
+                                       float eps, const float* ss_in, const void* resid, int64_t rs_m, int64_t rs_k,
+                                       float* ss_out, void* y, int64_t ys_m, int64_t ys_k, int M, int N, int K,
+                                       int out_f32, const void* bias, void* stream) {
+    return sg_plain_entry(w_packed, x, xs_m, xs_k, ln_w, eps, ss_in, resid, rs_m, rs_k, ss_out, y, ys_m, ys_k, M, N, K,
+                          out_f32, bias, true, stream);
 }
 
 extern "C" int tf_skinny_gemm_ex(const void* w_packed, const void* x, int64_t ldx, const void* ln_w, float eps,
@@ -1309,11 +1373,13 @@ extern "C" int tf_skinny_gemm_swiglu(const void* gate_packed, const void* up_pac
     return tf_skinny_gemm_swiglu_ex(gate_packed, up_packed, x, ldx, nullptr, 0.f, nullptr, act, ldy, M, I, K, stream);
 }
 
-extern "C" int tf_skinny_qkv_rope_act(const void* wqkv_packed, const void* x, int64_t xs_m, int64_t xs_k,
-                                      const void* ln_w, float eps, const float* ss_in, const void* cosb,
-                                      const void* sinb, const int64_t* positions, void* q_out, void* k_cache,
-                                      void* v_cache, int64_t stride_t, int64_t stride_h, int slot0,
-                                      const int32_t* slot0_dev, int M, int H, int D, int K, int rotate_k, void* stream) {
+// tf_skinny_qkv_rope_act (biased = false) and tf_skinny_qkv_rope_bias_act
+static int sg_qkv_entry(const void* wqkv_packed, const void* x, int64_t xs_m, int64_t xs_k, const void* ln_w, float eps,
+                        const float* ss_in, const void* cosb, const void* sinb, const int64_t* positions, void* q_out,
+                        void* k_cache, void* v_cache, int64_t stride_t, int64_t stride_h, int slot0,
+                        const int32_t* slot0_dev, int M, int H, int D, int K, int rotate_k, const void* bias, bool biased,
+                        void* stream) {
+    if (biased && !sg_bias_ok(bias)) return TF_EINVAL;
     if (!wqkv_packed || !x || !cosb || !sinb || !positions || !q_out || !k_cache || !v_cache) return TF_EINVAL;
     SgArgs a = {};
     a.wp = wqkv_packed, a.x = x, a.ln_w = ln_w;
@@ -1336,18 +1402,43 @@ extern "C" int tf_skinny_qkv_rope_act(const void* wqkv_packed, const void* x, in
     rp.H = H;
     rp.D = D;
     rp.rotate_k = rotate_k;
+    if (biased) {
+        a.resid = bias;                                           // (the q|k|v modes have no residual: see the kernel)
+        return ln_w ? launch_sg<SG_QKV_B, true>(a, rp, st) : launch_sg<SG_QKV_B, false>(a, rp, st);
+    }
     return ln_w ? launch_sg<SG_QKV, true>(a, rp, st) : launch_sg<SG_QKV, false>(a, rp, st);
+}
+
+extern "C" int tf_skinny_qkv_rope_act(const void* wqkv_packed, const void* x, int64_t xs_m, int64_t xs_k,
+                                      const void* ln_w, float eps, const float* ss_in, const void* cosb,
+                                      const void* sinb, const int64_t* positions, void* q_out, void* k_cache,
+                                      void* v_cache, int64_t stride_t, int64_t stride_h, int slot0,
+                                      const int32_t* slot0_dev, int M, int H, int D, int K, int rotate_k, void* stream) {
+    return sg_qkv_entry(wqkv_packed, x, xs_m, xs_k, ln_w, eps, ss_in, cosb, sinb, positions, q_out, k_cache, v_cache,
+                        stride_t, stride_h, slot0, slot0_dev, M, H, D, K, rotate_k, nullptr, false, stream);
+}
+
+// tf_skinny_qkv_rope_act with the q / k / v biases (fp16 [3 H D] in ops.rope_row_order(H, H, D), the weight's row order)
+// added to the K sum BEFORE the rotation: y = fp16(acc + float(b)), then the fp16 RoPE arithmetic on y.
+extern "C" int tf_skinny_qkv_rope_bias_act(const void* wqkv_packed, const void* x, int64_t xs_m, int64_t xs_k,
+                                           const void* ln_w, float eps, const float* ss_in, const void* cosb,
+                                           const void* sinb, const int64_t* positions, void* q_out, void* k_cache,
+                                           void* v_cache, int64_t stride_t, int64_t stride_h, int slot0,
+                                           const int32_t* slot0_dev, int M, int H, int D, int K, int rotate_k,
+                                           const void* bias, void* stream) {
+    return sg_qkv_entry(wqkv_packed, x, xs_m, xs_k, ln_w, eps, ss_in, cosb, sinb, positions, q_out, k_cache, v_cache,
+                        stride_t, stride_h, slot0, slot0_dev, M, H, D, K, rotate_k, bias, true, stream);
 }
 
 // tf_skinny_qkv_rope_act for grouped-query attention: rows [q: H D | k: Hkv D | v: Hkv D] (N = (H + 2 Hkv) D) in
 // ops.rope_row_order(H, Hkv, D); q_out stays [M][H][D], the k / v rows go to KV head hd of the cache (Hkv heads).
 // Row-major callers pass xs_m = ld, xs_k = 8.
-extern "C" int tf_skinny_qkv_rope_gqa_act(const void* wqkv_packed, const void* x, int64_t xs_m, int64_t xs_k,
-                                          const void* ln_w, float eps, const float* ss_in, const void* cosb,
-                                          const void* sinb, const int64_t* positions, void* q_out, void* k_cache,
-                                          void* v_cache, int64_t stride_t, int64_t stride_h, int slot0,
-                                          const int32_t* slot0_dev, int M, int H, int Hkv, int D, int K, int rotate_k,
-                                          void* stream) {
+static int sg_qkvg_entry(const void* wqkv_packed, const void* x, int64_t xs_m, int64_t xs_k, const void* ln_w, float eps,
+                         const float* ss_in, const void* cosb, const void* sinb, const int64_t* positions, void* q_out,
+                         void* k_cache, void* v_cache, int64_t stride_t, int64_t stride_h, int slot0,
+                         const int32_t* slot0_dev, int M, int H, int Hkv, int D, int K, int rotate_k, const void* bias,
+                         bool biased, void* stream) {
+    if (biased && !sg_bias_ok(bias)) return TF_EINVAL;
     if (!wqkv_packed || !x || !cosb || !sinb || !positions || !q_out || !k_cache || !v_cache) return TF_EINVAL;
     if (H < 1 || Hkv < 1 || (H % Hkv) || H > 0x7fff || (D != 64 && D != 128)) return TF_EINVAL;
     SgArgs a = {};
@@ -1371,7 +1462,32 @@ extern "C" int tf_skinny_qkv_rope_gqa_act(const void* wqkv_packed, const void* x
     rp.H = H | (Hkv << 16);                                                           // (see SgRope)
     rp.D = D;
     rp.rotate_k = rotate_k;
+    if (biased) {
+        a.resid = bias;
+        return ln_w ? launch_sg<SG_QKVG_B, true>(a, rp, st) : launch_sg<SG_QKVG_B, false>(a, rp, st);
+    }
     return ln_w ? launch_sg<SG_QKVG, true>(a, rp, st) : launch_sg<SG_QKVG, false>(a, rp, st);
+}
+
+extern "C" int tf_skinny_qkv_rope_gqa_act(const void* wqkv_packed, const void* x, int64_t xs_m, int64_t xs_k,
+                                          const void* ln_w, float eps, const float* ss_in, const void* cosb,
+                                          const void* sinb, const int64_t* positions, void* q_out, void* k_cache,
+                                          void* v_cache, int64_t stride_t, int64_t stride_h, int slot0,
+                                          const int32_t* slot0_dev, int M, int H, int Hkv, int D, int K, int rotate_k,
+                                          void* stream) {
+    return sg_qkvg_entry(wqkv_packed, x, xs_m, xs_k, ln_w, eps, ss_in, cosb, sinb, positions, q_out, k_cache, v_cache,
+                         stride_t, stride_h, slot0, slot0_dev, M, H, Hkv, D, K, rotate_k, nullptr, false, stream);
+}
+
+// tf_skinny_qkv_rope_gqa_act with the q / k / v biases: fp16 [(H + 2 Hkv) D] in ops.rope_row_order(H, Hkv, D).
+extern "C" int tf_skinny_qkv_rope_gqa_bias_act(const void* wqkv_packed, const void* x, int64_t xs_m, int64_t xs_k,
+                                               const void* ln_w, float eps, const float* ss_in, const void* cosb,
+                                               const void* sinb, const int64_t* positions, void* q_out, void* k_cache,
+                                               void* v_cache, int64_t stride_t, int64_t stride_h, int slot0,
+                                               const int32_t* slot0_dev, int M, int H, int Hkv, int D, int K,
+                                               int rotate_k, const void* bias, void* stream) {
+    return sg_qkvg_entry(wqkv_packed, x, xs_m, xs_k, ln_w, eps, ss_in, cosb, sinb, positions, q_out, k_cache, v_cache,
+                         stride_t, stride_h, slot0, slot0_dev, M, H, Hkv, D, K, rotate_k, bias, true, stream);
 }
 
 extern "C" int tf_skinny_qkv_rope(const void* wqkv_packed, const void* x, int64_t ldx, const void* ln_w, float eps,

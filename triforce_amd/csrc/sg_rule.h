@@ -4,6 +4,11 @@
 #pragma once
 
 enum { SG_PLAIN = 0, SG_GATEUP = 1, SG_F32 = 2, SG_QKV = 3, SG_QKVG = 4 };   // SG_QKVG: SG_QKV with two head counts (GQA); same launch rule
+// Attention bias: SG_PLAIN / SG_QKV / SG_QKVG with an fp16 bias added to the complete K sum.  Kernel
+// modes of their own, so that the bias-free instantiations keep their names and their code; the launch rule sees the base mode.
+enum { SG_PLAIN_B = 5, SG_QKV_B = 6, SG_QKVG_B = 7 };
+constexpr bool sg_has_bias(int mode) { return mode >= SG_PLAIN_B; }
+constexpr int sg_base_mode(int mode) { return mode == SG_PLAIN_B ? SG_PLAIN : mode == SG_QKV_B ? SG_QKV : mode == SG_QKVG_B ? SG_QKVG : mode; }
 
 // Waves per workgroup = K-splits of one 16-row panel.  A wave keeps 4 KiB of weights in flight, so a grid of few panels
 // (o_proj / down_proj: N = 4096 -> 256 workgroups, one per CU) needs more waves per panel to cover the HBM

@@ -181,6 +181,12 @@ SIGNATURES["tf_topk_topp_probs_large"] = (_i32, [_vp, _vp, _i32, _i32, _f32, _i3
 SIGNATURES["tf_minp_probs"] = (_i32, [_vp, _vp, _i32, _i32, _f32, _i32, _f32, _f32, _vp])
 SIGNATURES["tf_minp_probs_large"] = (_i32, [_vp, _vp, _i32, _i32, _f32, _i32, _f32, _f32, _vp, _i64, _vp])
 
+# attention bias: each entry is its bias-free neighbour's signature + the bias pointer (include/triforce_hip.h "ATTENTION BIAS",
+# DESIGN section 29)
+for _name in ("tf_skinny_gemm", "tf_skinny_qkv_rope", "tf_skinny_qkv_rope_gqa"):
+    _res, _args = SIGNATURES[_name + "_act"]
+    SIGNATURES[_name + "_bias_act"] = (_res, _args[:-1] + [_vp, _vp])
+
 ABI_VERSION = 1
 _lib = None
 

@@ -11,8 +11,18 @@ _DEFAULTS = dict(
     num_attention_heads=32, num_key_value_heads=None, hidden_act="silu", max_position_embeddings=2048,
     rms_norm_eps=1e-6, rope_theta=10000.0, rope_scaling=None, attention_bias=False, pad_token_id=None,
     bos_token_id=1, eos_token_id=2, _name_or_path="",
+    # attention bias: kept to tell a Qwen2-family config (model_type "qwen2": q/k/v bias implied) from a
+    # Llama one, and to refuse what the path does not compute
+    model_type="llama", mlp_bias=False, use_sliding_window=False,
 )
 GQA_HEAD_DIMS = (64, 128)        # head widths of the grouped-query kernels (tf_attn_decode_gqa_act, tf_attn_prefill_gqa)
+
+
+def refuse_attention_bias(cfg, what):
+    """ValueError for a config with attention bias in a component whose projections are bias-free."""
+    if getattr(cfg, "attention_bias", False):
+        raise ValueError(f"attention bias (attention_bias=True) is not supported by {what}: q/k/v/o biases run on the "
+                         "single-GPU resident engine with fp16 weights only")
 
 
 def refuse_gqa(cfg, what):
@@ -36,8 +46,13 @@ class LlamaConfig:
         # role of config_yarn.py:170-193 (_rope_scaling_validation), reduced to what the path supports
         if self.hidden_act != "silu":
             raise ValueError(f"hidden_act {self.hidden_act!r} is not supported (silu only)")
-        if self.attention_bias:
-            raise ValueError("attention_bias is not supported")
+        # attention_bias: q/k/v/o projections with a bias (reference models/modeling_llama.py:174-177) — accepted; the MLP
+        # stays bias-free and attention stays global
+        self.attention_bias = bool(self.attention_bias)
+        if self.mlp_bias:
+            raise ValueError("mlp_bias=True is not supported (the MLP projections are bias-free)")
+        if self.use_sliding_window:
+            raise ValueError("use_sliding_window=True is not supported (attention is global)")
         H, Hkv = self.num_attention_heads, self.num_key_value_heads
         if not isinstance(Hkv, int) or Hkv < 1 or H % Hkv:
             raise ValueError(f"GQA: num_attention_heads ({H}) must be a multiple of num_key_value_heads ({Hkv})")
@@ -75,6 +90,8 @@ class LlamaConfig:
         with open(os.path.join(path, "config.json")) as f:
             d = json.load(f)
         d = {k: v for k, v in d.items() if k in _DEFAULTS or k.startswith("rope")}
+        if d.get("model_type") == "qwen2" and "attention_bias" not in d:
+            d["attention_bias"] = True                   # Qwen2 / Qwen2.5: bias on q/k/v (none on o_proj), no config key
         d["_name_or_path"] = path
         return cls(**d)
 

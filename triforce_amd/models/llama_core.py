@@ -61,6 +61,10 @@ def softmax_scale_for(head_dim):
 
 # ---- retrieval-verify weight tier ----------------------------------------------------------------------
 RETRIEVAL_WEIGHTS_ENV = "TRIFORCE_RETRIEVAL_WEIGHTS"
+# Standard deviation of the randomly drawn attention biases (init_random of a bias config).  Large against the matrices'
+# 0.02 on purpose: trained q/k biases are O(1) and larger, and a bias that moved no logit would make every test of the biased
+# path vacuous (tests/test_attn_bias_cpu.py pins that zeroing the biases changes the greedy stream).
+BIAS_STD = 0.5
 
 
 def retrieval_weights():
@@ -93,6 +97,13 @@ class LlamaWeights:
         if self.Hkv != self.H and world_size > 1:
             raise ValueError(f"GQA ({self.H} query / {self.Hkv} KV heads) is not supported by tensor-parallel weight shards "
                              f"(world_size={world_size})")
+        # attention bias: q|k|v biases fused like the weights, an o_proj bias where the checkpoint has one
+        # (Llama-architecture checkpoints with attention_bias carry all four; the Qwen2 family has none on o_proj)
+        self.attn_bias = bool(getattr(cfg, "attention_bias", False))
+        if self.attn_bias and world_size > 1:
+            raise ValueError(f"attention bias is not supported by tensor-parallel weight shards (world_size={world_size}): "
+                             "the shard's 8-row-panel and exchange GEMMs are bias-free")
+        self.bqkv, self.bo = [], []                     # per layer: fp16 (N,) tensors; bo[i] is None without an o_proj bias
         assert self.H % world_size == 0 and cfg.intermediate_size % world_size == 0
         self.H_local = self.H // world_size
         self.Hkv_local = self.Hkv // world_size if self.Hkv == self.H else self.Hkv
@@ -128,6 +139,7 @@ class LlamaWeights:
             v = self._shard_rows(get(p + "self_attn.v_proj.weight"), kvd)
             self.wqkv.append(torch.cat([q, k, v], dim=0).contiguous().to(dev))
             self.wo.append(self._shard_cols(get(p + "self_attn.o_proj.weight"), hd).contiguous().to(dev))
+            self._load_attn_bias(sd, i, dev)
             g = self._shard_rows(get(p + "mlp.gate_proj.weight"), self.I_local)
             u = self._shard_rows(get(p + "mlp.up_proj.weight"), self.I_local)
             self.wgu.append(torch.cat([g, u], dim=0).contiguous().to(dev))
@@ -136,18 +148,45 @@ class LlamaWeights:
             self.ln2.append(get(p + "post_attention_layernorm.weight").to(dev))
         return self.finalize()
 
-    def init_random(self, seed, std=0.02):
+    def _load_attn_bias(self, sd, i, dev):
+        """self_attn.{q,k,v}_proj.bias -> the fused [q | k | v] bias of layer i, self_attn.o_proj.bias if the checkpoint has
+        one.  q/k/v biases come all together or not at all, and their presence must agree with config.attention_bias."""
+        p = f"model.layers.{i}.self_attn."
+        have = [n for n in ("q", "k", "v") if p + n + "_proj.bias" in sd]
+        if 0 < len(have) < 3:
+            raise ValueError(f"layer {i}: attention bias present for {have} only; q_proj, k_proj and v_proj biases come "
+                             "together")
+        has_o = p + "o_proj.bias" in sd
+        if bool(have) != self.attn_bias or (has_o and not self.attn_bias):
+            found = [n + "_proj" for n in have] + (["o_proj"] if has_o else [])
+            raise ValueError(f"layer {i}: the checkpoint has attention bias for {found or 'no projection'} but the config says "
+                             f"attention_bias={self.attn_bias}")
+        if not self.attn_bias:
+            return
+        b = torch.cat([sd[p + n + "_proj.bias"].to(torch.float16).reshape(-1) for n in ("q", "k", "v")]).contiguous()
+        if b.numel() != (self.H_local + 2 * self.Hkv_local) * self.D:
+            raise ValueError(f"layer {i}: attention bias has {b.numel()} q|k|v entries, expected "
+                             f"{(self.H_local + 2 * self.Hkv_local) * self.D}")
+        self.bqkv.append(b.to(dev))
+        self.bo.append(sd[p + "o_proj.bias"].to(torch.float16).reshape(-1).contiguous().to(dev) if has_o else None)
+
+    def _o_bias_drawn(self):
+        """Does a random draw give o_proj a bias?  Every bias config but the Qwen2 family's (q/k/v only)."""
+        return self.attn_bias and getattr(self.cfg, "model_type", "llama") != "qwen2"
+
+    def init_random(self, seed, std=0.02, bias_std=BIAS_STD):
         """Random-init directly on the device (no checkpoints offline): N(0,std) like
         modeling_llama.py:306-315; every rank draws the full matrix stream and keeps its shard
         only for the small configs — for big models each tensor is drawn shard-sized with a
-        (seed, layer, name, rank)-derived generator."""
+        (seed, layer, name, rank)-derived generator.  A bias config draws its biases N(0, bias_std) from tags of their own
+        (("bqkv", layer, rank), ("bo", layer, rank)): the matrices are the bias-free draw, bit for bit."""
         dev, cfg = self.device, self.cfg
         hid, hd = cfg.hidden_size, self.H_local * self.D
 
-        def draw(tag, *shape):
+        def draw(tag, *shape, s=std):
             g = torch.Generator(device=dev)
             g.manual_seed((seed * 1000003 + zlib.crc32(repr(tag).encode())) % (2 ** 31))
-            return (torch.randn(*shape, generator=g, device=dev, dtype=torch.float32) * std).to(torch.float16)
+            return (torch.randn(*shape, generator=g, device=dev, dtype=torch.float32) * s).to(torch.float16)
 
         self.embed = draw("embed", cfg.vocab_size, hid)
         self.lm_head = draw("lm_head", cfg.vocab_size, hid)
@@ -155,22 +194,25 @@ class LlamaWeights:
         for i in range(self.L):
             self.wqkv.append(draw(("qkv", i, self.rank), hd + 2 * self.Hkv_local * self.D, hid))
             self.wo.append(draw(("o", i, self.rank), hid, hd))
+            if self.attn_bias:
+                self.bqkv.append(draw(("bqkv", i, self.rank), hd + 2 * self.Hkv_local * self.D, s=bias_std))
+                self.bo.append(draw(("bo", i, self.rank), hid, s=bias_std) if self._o_bias_drawn() else None)
             self.wgu.append(draw(("gu", i, self.rank), 2 * self.I_local, hid))
             self.wd.append(draw(("d", i, self.rank), hid, self.I_local))
             self.ln1.append(torch.ones(hid, dtype=torch.float16, device=dev))
             self.ln2.append(torch.ones(hid, dtype=torch.float16, device=dev))
         return self.finalize()
 
-    def overwrite_random_(self, seed, std=0.02):
+    def overwrite_random_(self, seed, std=0.02, bias_std=BIAS_STD):
         """Re-draw every matrix IN PLACE with the values ``init_random(seed)`` would give (same storage, so captured
         hipGraphs and packed-weight pointers stay valid): lets one process measure two weight sets back to back."""
         dev, cfg = self.device, self.cfg
         assert isinstance(self.lm_head, ops.PackedLinear), "finalize() first"
 
-        def draw_into(dst, tag):
+        def draw_into(dst, tag, s=std):
             g = torch.Generator(device=dev)
             g.manual_seed((seed * 1000003 + zlib.crc32(repr(tag).encode())) % (2 ** 31))
-            dst.copy_((torch.randn(*dst.shape, generator=g, device=dev, dtype=torch.float32) * std).to(torch.float16))
+            dst.copy_((torch.randn(*dst.shape, generator=g, device=dev, dtype=torch.float32) * s).to(torch.float16))
 
         tied = self.embed is self.lm_head.w
         draw_into(self.lm_head.w, "lm_head")
@@ -181,6 +223,8 @@ class LlamaWeights:
         for i in range(self.L):
             for lst, tag in ((self.wqkv, "qkv"), (self.wo, "o"), (self.wgu, "gu"), (self.wd, "d")):
                 draw_into(lst[i].w, (tag, i, self.rank))
+                if lst[i].bias is not None:             # (wqkv / wo of a bias config; refresh_ re-derives the rotary copy)
+                    draw_into(lst[i].bias, ("b" + tag, i, self.rank), s=bias_std)
                 lst[i].refresh_()
             self.ln1[i].fill_(1.0)
             self.ln2[i].fill_(1.0)
@@ -191,8 +235,9 @@ class LlamaWeights:
         """Aligned synthetic weights (models/aligned.py): real shapes, dense values, planted successor table so that
         draft / retrieval / full-cache forwards agree to a tunable degree."""
         from . import aligned
-        from .config_yarn import refuse_gqa
+        from .config_yarn import refuse_attention_bias, refuse_gqa
         refuse_gqa(self.cfg, "aligned synthetic weights (models/aligned.py init_aligned)")
+        refuse_attention_bias(self.cfg, "aligned synthetic weights (models/aligned.py init_aligned)")
         return aligned.init_weights(self, spec, role, attn_keys=attn_keys)
 
     def finalize(self):
@@ -205,8 +250,18 @@ class LlamaWeights:
         if tied:
             self.embed = self.lm_head.w
         rope = (self.H_local, self.D) if self.Hkv == self.H else (self.H_local, self.Hkv_local, self.D)
-        self.wqkv = [PL(w, rope=rope) for w in self.wqkv]
-        self.wo = [PL(w) for w in self.wo]
+        if self.attn_bias:
+            if self.retrieval_fp8:
+                raise ValueError(f"attention bias is not supported with {RETRIEVAL_WEIGHTS_ENV}=fp8: the FP8 weight kernels "
+                                 "have no bias epilogue")
+            assert len(self.bqkv) == len(self.bo) == len(self.wqkv), "a bias config needs its biases before finalize()"
+            self.wqkv = [PL(w, rope=rope, bias=b) for w, b in zip(self.wqkv, self.bqkv)]
+            self.wo = [PL(w, bias=b) for w, b in zip(self.wo, self.bo)]
+            self.bqkv = [pl.bias for pl in self.wqkv]        # the tensors the packed weights hold (refresh_ reads them)
+            self.bo = [pl.bias for pl in self.wo]
+        else:
+            self.wqkv = [PL(w, rope=rope) for w in self.wqkv]
+            self.wo = [PL(w) for w in self.wo]
         self.wgu = [PL(w, split=2) for w in self.wgu]
         self.wd = [PL(w) for w in self.wd]
         if self.retrieval_fp8:
@@ -219,6 +274,9 @@ class LlamaWeights:
         if self.Hkv != self.H:
             raise ValueError(f"GQA ({self.H} query / {self.Hkv} KV heads) is not supported by {RETRIEVAL_WEIGHTS_ENV}=fp8: "
                              "no grouped-query FP8 q|k|v epilogue exists")
+        if self.attn_bias:
+            raise ValueError(f"attention bias is not supported with {RETRIEVAL_WEIGHTS_ENV}=fp8: the FP8 weight kernels have "
+                             "no bias epilogue")
         for pl in [self.lm_head] + self.wqkv + self.wo + self.wgu + self.wd:
             if pl.fp8 is None:
                 pl.fp8 = ops.Fp8Linear(pl)
@@ -230,7 +288,7 @@ class LlamaWeights:
 
     def nbytes(self):
         ts = [self.embed, self.lm_head, self.norm] + self.wqkv + self.wo + self.wgu + self.wd + self.ln1 + self.ln2
-        ts = [ops._w(t) for t in ts]
+        ts = [ops._w(t) for t in ts] + [b for b in self.bqkv + self.bo if b is not None]
         return sum(t.numel() * t.element_size() for t in ts)
 
 
@@ -255,6 +313,14 @@ class DecoderLayers:
         W = self.W
         return {} if W.Hkv_local == W.H_local else {"Hkv": W.Hkv_local}
 
+    @staticmethod
+    def _bias(w, rope=False):
+        """The bias of a projection for ops.linear / ops.qkv_rope (the rotary-order copy for the fused q|k|v kernel), passed
+        only by a model with attention bias: the bias-free call is unchanged."""
+        if w.bias is None:
+            return {}
+        return {"bias": w.bias_rope if rope else w.bias}
+
     def _capture(self, x):
         """W.capture (a list, while aligned weights are calibrated) receives the final residual stream, before the norm."""
         if self.W.capture is not None:
@@ -266,13 +332,15 @@ class DecoderLayers:
         W = self.W
         w = W.wqkv[i]
         return ops.qkv_rope(x, w.fp8 if f8 else w, W.ln1[i], W.eps, self.cos, self.sin, pos, kl, vl, slot, W.H_local, W.D,
-                            rotate_k=self.rotate_k, slot0_dev=slot_dev, ss_in=ss if i > 0 else None, **self._kv_heads())
+                            rotate_k=self.rotate_k, slot0_dev=slot_dev, ss_in=ss if i > 0 else None, **self._kv_heads(),
+                            **self._bias(w, rope=True))
 
     def o_fused(self, i, a, x, ss, f8=False, out=None):
         w = self.W.wo[i].fp8 if f8 else self.W.wo[i]
+        b = self._bias(self.W.wo[i])
         if out is None:
-            return ops.linear(a, w, resid=x, out=x, ss_out=ss)                  # x += attn_out
-        return ops.linear(a, w, out=out)
+            return ops.linear(a, w, resid=x, out=x, ss_out=ss, **b)             # x += attn_out
+        return ops.linear(a, w, out=out, **b)
 
     def gate_up_fused(self, i, x, ss, f8=False):
         W = self.W
@@ -300,11 +368,11 @@ class DecoderLayers:
             h = ops.rmsnorm(x, W.ln1[i], W.eps)
         else:                                       # x += mlp_out of the previous layer, fused into the norm
             h = ops.rmsnorm(d, W.ln1[i], W.eps, residual=x, sum_out=x)
-        return ops.rope_append(ops.linear(h, W.wqkv[i]), self.cos, self.sin, pos, kl, vl, slot, W.H_local, W.D,
+        return ops.rope_append(ops.linear(h, W.wqkv[i], **self._bias(W.wqkv[i])), self.cos, self.sin, pos, kl, vl, slot, W.H_local, W.D,
                                rotate_k=self.rotate_k, slot0_dev=slot_dev, **self._kv_heads())
 
     def o_proj(self, i, a, out=None):
-        return ops.linear(a, self.W.wo[i], out=out)
+        return ops.linear(a, self.W.wo[i], out=out, **self._bias(self.W.wo[i]))
 
     def mlp(self, i, x, o, out=None):
         """x += o (the attention output), then the MLP: returns its output, which the next norm adds to x."""

@@ -39,6 +39,11 @@ class LlamaForCausalLM:
         self.gqa = config.num_key_value_heads != config.num_attention_heads     # grouped-query target
         if self.gqa:
             _check_gqa_env()
+        if getattr(config, "attention_bias", False) and retrieval_weights() == "fp8":
+            # attention bias runs the fp16 weights; the FP8 KV tiers only consume what the GEMMs produce
+            from .llama_core import RETRIEVAL_WEIGHTS_ENV
+            raise ValueError(f"attention bias is not supported with {RETRIEVAL_WEIGHTS_ENV}=fp8: the FP8 weight kernels "
+                             "(Fp8Linear) have no bias epilogue")
         self.weights = LlamaWeights(config, self.device)
         # TRIFORCE_RETRIEVAL_WEIGHTS=fp8: the retrieval-cache (spec) forward streams FP8 copies of its five GEMM weights
         # (DESIGN section 16); every other forward keeps the fp16 weights

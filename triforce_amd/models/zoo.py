@@ -34,6 +34,25 @@ CONFIGS = {
                      num_key_value_heads=2, max_position_embeddings=131072, rms_norm_eps=1e-6,
                      rope_scaling=dict(type="yarn", factor=16.0, original_max_position_embeddings=256),
                      _name_or_path="tiny-yarn-gqa-target"),
+    # the tiny targets with attention bias: "tiny" with q/k/v/o biases (the Llama-architecture form),
+    # "tiny-gqa" with q/k/v biases only (the Qwen2 form: model_type qwen2, no o_proj bias)
+    "tiny-bias": dict(hidden_size=256, intermediate_size=768, num_hidden_layers=2, num_attention_heads=2,
+                      max_position_embeddings=131072, rms_norm_eps=1e-6, attention_bias=True,
+                      rope_scaling=dict(type="yarn", factor=16.0, original_max_position_embeddings=256),
+                      _name_or_path="tiny-yarn-bias-target"),
+    "tiny-gqa-bias": dict(hidden_size=512, intermediate_size=768, num_hidden_layers=2, num_attention_heads=4,
+                          num_key_value_heads=2, max_position_embeddings=131072, rms_norm_eps=1e-6, attention_bias=True,
+                          model_type="qwen2",
+                          rope_scaling=dict(type="yarn", factor=16.0, original_max_position_embeddings=256),
+                          _name_or_path="tiny-yarn-gqa-bias-target"),
+    # Qwen/Qwen2.5-7B-Instruct-1M shape (grouped-query 28 / 4 heads, q/k/v bias, plain RoPE with theta 1e7).  Written from
+    # memory of the model card: there is no hub access offline, so these values are NOT checked against the published
+    # config.json.  With g = 7 the decode attention stacks gs = 1 query head at 7 rows (ops.gqa_stack): K / V is read per
+    # query head (known limit)
+    "qwen2.5-7B-1M": dict(vocab_size=152064, hidden_size=3584, intermediate_size=18944, num_hidden_layers=28,
+                          num_attention_heads=28, num_key_value_heads=4, max_position_embeddings=1010000, rms_norm_eps=1e-6,
+                          rope_theta=1e7, attention_bias=True, model_type="qwen2", bos_token_id=151643, eos_token_id=151645,
+                          _name_or_path="Qwen/Qwen2.5-7B-Instruct-1M"),
     # the tiny target and the 68M-shaped draft with the Llama-3 vocabulary (128 256 entries).  No trained
     # draft of that vocabulary exists offline: both are random-init shapes
     "tiny-v128k": dict(vocab_size=128256, hidden_size=256, intermediate_size=768, num_hidden_layers=2, num_attention_heads=2,

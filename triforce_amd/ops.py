@@ -191,9 +191,11 @@ class PackedLinear:
     marks a fused q|k|v weight: a second packed copy in rotary-pair row order feeds tf_skinny_qkv_rope.
     ``rope=(H, Hkv, D)`` with Hkv < H marks a grouped-query weight ([q: H D | k: Hkv D | v: Hkv D] rows): its rotary copy
     feeds tf_skinny_qkv_rope_gqa_act, and it gets neither the 8-row-panel copy nor an FP8 copy (no GQA epilogue exists
-    for either)."""
+    for either).  ``bias`` = fp16 (N,) bias of the projection (attention bias), rows in ``w``'s order; a
+    rope weight keeps a second copy ``bias_rope`` in the rotary row order of ``wp_rope``, which is what the fused q|k|v
+    kernel reads.  A biased weight gets neither the 8-row-panel copy nor an FP8 copy (bias-free forms)."""
 
-    def __init__(self, w, split=1, pack=None, rope=None):
+    def __init__(self, w, split=1, pack=None, rope=None, bias=None):
         self.w = w
         self.N, self.K = w.shape
         self.split = split
@@ -214,7 +216,13 @@ class PackedLinear:
         self.parts_n8 = self.wp_rope_n8 = None
         if ok and w.is_cuda and split == 2 and n8_applies(self.N // split, self.K):
             self.parts_n8 = [pack_weight_n8(b) for b in w.chunk(split, dim=0)]
-        if self.wp_rope is not None and not self.gqa and w.is_cuda and n8_applies(self.N, self.K):
+        self.bias = self.bias_rope = None
+        if bias is not None:
+            assert split == 1 and bias.dtype == _HALF and tuple(bias.shape) == (self.N,) and bias.device == w.device
+            self.bias = bias.contiguous()
+            if rope is not None and rope[-1] % 32 == 0 and self.N == _rope_rows(rope):
+                self.bias_rope = self.bias[rope_row_order(*_rope3(rope), w.device)].contiguous()
+        if self.wp_rope is not None and not self.gqa and bias is None and w.is_cuda and n8_applies(self.N, self.K):
             self.wp_rope_n8 = pack_weight_n8(w[rope_row_order_n8(rope[0], rope[1], w.device)])
         self.fp8 = None           # Fp8Linear of the retrieval-verify tier (models/llama_core.LlamaWeights.build_fp8_)
 
@@ -225,6 +233,8 @@ class PackedLinear:
                 dst.copy_(pack_weight(blk))
         if self.wp_rope is not None:
             self.wp_rope.copy_(pack_weight(self.w[rope_row_order(*_rope3(self.rope), self.w.device)]))
+        if self.bias_rope is not None:                                        # (``bias`` itself is what was modified in place)
+            self.bias_rope.copy_(self.bias[rope_row_order(*_rope3(self.rope), self.w.device)])
         if self.parts_n8 is not None:
             for dst, blk in zip(self.parts_n8, self.w.chunk(self.split, dim=0)):
                 dst.copy_(pack_weight_n8(blk))
@@ -280,6 +290,9 @@ class Fp8Linear:
     def __init__(self, pl):
         assert isinstance(pl, PackedLinear)
         self.src, self.N, self.K, self.split, self.rope = pl, pl.N, pl.K, pl.split, pl.rope
+        if getattr(pl, "bias", None) is not None:
+            raise ValueError(f"attention bias: a biased {pl.N} x {pl.K} weight is not supported by the FP8 weight tier "
+                             "(Fp8Linear): the FP8 kernels have no bias epilogue")
         if getattr(pl, "gqa", False):
             raise ValueError(f"GQA q|k|v weight (H, Hkv, D = {pl.rope}) is not supported by the FP8 weight tier (Fp8Linear): "
                              "no grouped-query FP8 epilogue exists")
@@ -487,7 +500,7 @@ def can_fuse_rows(rows, embed, *ws):
             and all(isinstance(w, PackedLinear) and w.parts is not None for w in ws))
 
 
-def linear(x, w, out_f32=False, ln=None, eps=0.0, resid=None, out=None, ss_in=None, ss_out=None):
+def linear(x, w, out_f32=False, ln=None, eps=0.0, resid=None, out=None, ss_in=None, ss_out=None, bias=None):
     """y = x . W^T, fp16 with fp32 accumulation — the reference's nn.Linear / F.linear.  <=32 rows against a
     PackedLinear run the hand-written weight-streaming kernel; larger blocks (prefill) go to hipBLASLt.
     Fused forms of the skinny kernel (only valid when ``can_fuse``): ``ln`` = RMSNorm weight applied to x first
@@ -495,9 +508,13 @@ def linear(x, w, out_f32=False, ln=None, eps=0.0, resid=None, out=None, ss_in=No
     to write (may be ``resid`` itself); ``ss_out`` (N/16, 32) fp32 receives the per-panel sums of squares of the
     output rows and ``ss_in`` feeds such partials of x to the norm prologue (see ``ss_buffer``).
     x / resid / out may be ``Act`` blocks (k-octet-major); an Act input gives an Act output unless ``out`` says
-    otherwise (fp32 logits are always a row-major tensor)."""
+    otherwise (fp32 logits are always a row-major tensor).
+    ``bias`` (N,) fp16, rows in W's order: y = fp16(acc + float(bias)) before the residual add (tf_skinny_gemm_bias_act);
+    prefill blocks take F.linear(x, W, bias).  No bias with fp32 output or FP8 weights."""
     M = x.shape[0]
     f8 = isinstance(w, Fp8Linear)
+    if bias is not None:
+        assert not f8 and not out_f32 and bias.dtype == _HALF and bias.is_contiguous() and tuple(bias.shape) == (_w(w).shape[0],)
     if f8:
         _fp8_rows_ok(x, w)
         assert w.split == 1 and w.rope is None, "an FP8 gate|up / q|k|v weight runs through mlp_act / qkv_rope"
@@ -527,6 +544,12 @@ def linear(x, w, out_f32=False, ln=None, eps=0.0, resid=None, out=None, ss_in=No
                                                        _ptr(ss_in), rp, rsm, rsk, _ptr(ss_out), yp, ysm, ysk, M, w.N, w.K,
                                                        1 if out_f32 else 0, _stream()), "tf_skinny_gemm_fp8_act")
             return out
+        if bias is not None:
+            _dev(bias)
+            hip.check(hip.lib().tf_skinny_gemm_bias_act(_ptr(w.wp), xp, xsm, xsk, _ptr(ln), float(eps), _ptr(ss_in), rp, rsm,
+                                                        rsk, _ptr(ss_out), yp, ysm, ysk, M, w.N, w.K, 0, _ptr(bias), _stream()),
+                      "tf_skinny_gemm_bias_act")
+            return out
         hip.check(hip.lib().tf_skinny_gemm_act(_ptr(w.wp), xp, xsm, xsk, _ptr(ln), float(eps), _ptr(ss_in), rp, rsm, rsk,
                                                _ptr(ss_out), yp, ysm, ysk, M, w.N, w.K, 1 if out_f32 else 0, _stream()),
                   "tf_skinny_gemm_act")
@@ -534,7 +557,7 @@ def linear(x, w, out_f32=False, ln=None, eps=0.0, resid=None, out=None, ss_in=No
     assert ln is None and resid is None and out is None and ss_in is None and ss_out is None, \
         "fused linear needs the skinny kernel (ops.can_fuse)"
     assert not isinstance(x, Act), "k-octet-major activations exist only on the skinny decode path"
-    y = F.linear(x, _w(w))
+    y = F.linear(x, _w(w)) if bias is None else F.linear(x, _w(w), bias)
     return y.float() if out_f32 else y
 
 
@@ -578,14 +601,18 @@ def ss_buffer(hidden, device):
 
 
 def qkv_rope(x, wqkv, ln, eps, cos, sin, positions, k_layer, v_layer, slot0, H, D, rotate_k=True, slot0_dev=None,
-             ss_in=None, Hkv=None):
+             ss_in=None, Hkv=None, bias=None):
     """One kernel for [RMSNorm ->] fused q|k|v GEMM -> RoPE -> KV append: x (rows, hidden) is the residual stream
     (ln = input_layernorm weight, or None when x is already normalised; a row-major tensor or an Act); q (rows,H,D)
     is returned rotated, the k (rotated unless rotate_k is False) and v rows land in the cache at slot0+i.
-    ``Hkv`` < H: a grouped-query weight (PackedLinear rope=(H, Hkv, D)), k / v rows go to the Hkv heads of the cache."""
-    _dev(ln, cos, sin, positions, k_layer, v_layer, slot0_dev)
+    ``Hkv`` < H: a grouped-query weight (PackedLinear rope=(H, Hkv, D)), k / v rows go to the Hkv heads of the cache.
+    ``bias``: the weight's q|k|v bias IN ROTARY ROW ORDER (PackedLinear.bias_rope), added to the GEMM result before the
+    rotation (tf_skinny_qkv_rope[_gqa]_bias_act); never the 8-row-panel or FP8 forms."""
+    _dev(ln, cos, sin, positions, k_layer, v_layer, slot0_dev, bias)
     gqa = Hkv is not None and Hkv != H
     f8 = isinstance(wqkv, Fp8Linear)
+    if bias is not None:
+        assert not f8 and bias is wqkv.bias_rope, "qkv_rope takes the PackedLinear's own rotary-order bias"
     if f8:
         _fp8_rows_ok(x, wqkv)
     assert f8 or (isinstance(wqkv, PackedLinear) and wqkv.wp_rope is not None)
@@ -600,6 +627,14 @@ def qkv_rope(x, wqkv, ln, eps, cos, sin, positions, k_layer, v_layer, slot0, H, 
     xp, xsm, xsk = _lay(x)
     if gqa:
         assert not f8 and k_layer.shape[0] == Hkv and v_layer.shape[0] == Hkv and H % Hkv == 0
+        if bias is not None:
+            hip.check(hip.lib().tf_skinny_qkv_rope_gqa_bias_act(_ptr(wqkv.wp_rope), xp, xsm, xsk, _ptr(ln), float(eps),
+                                                                _ptr(ss_in), _ptr(cos), _ptr(sin), _ptr(positions), _ptr(q),
+                                                                _ptr(k_layer), _ptr(v_layer), st, sh, int(slot0),
+                                                                _ptr(slot0_dev), rows, H, Hkv, D, wqkv.K,
+                                                                1 if rotate_k else 0, _ptr(bias), _stream()),
+                      "tf_skinny_qkv_rope_gqa_bias_act")
+            return q
         hip.check(hip.lib().tf_skinny_qkv_rope_gqa_act(_ptr(wqkv.wp_rope), xp, xsm, xsk, _ptr(ln), float(eps), _ptr(ss_in),
                                                        _ptr(cos), _ptr(sin), _ptr(positions), _ptr(q), _ptr(k_layer),
                                                        _ptr(v_layer), st, sh, int(slot0), _ptr(slot0_dev), rows, H, Hkv, D,
@@ -611,6 +646,13 @@ def qkv_rope(x, wqkv, ln, eps, cos, sin, positions, k_layer, v_layer, slot0, H, 
                                                        _ptr(k_layer), _ptr(v_layer), st, sh, int(slot0), _ptr(slot0_dev), rows,
                                                        H, D, wqkv.K, 1 if rotate_k else 0, _stream()),
                   "tf_skinny_qkv_rope_fp8_act")
+        return q
+    if bias is not None:
+        hip.check(hip.lib().tf_skinny_qkv_rope_bias_act(_ptr(wqkv.wp_rope), xp, xsm, xsk, _ptr(ln), float(eps), _ptr(ss_in),
+                                                        _ptr(cos), _ptr(sin), _ptr(positions), _ptr(q), _ptr(k_layer),
+                                                        _ptr(v_layer), st, sh, int(slot0), _ptr(slot0_dev), rows, H, D,
+                                                        wqkv.K, 1 if rotate_k else 0, _ptr(bias), _stream()),
+                  "tf_skinny_qkv_rope_bias_act")
         return q
     if wqkv.wp_rope_n8 is not None and ln is not None and rows <= N8_MAX_ROWS:      # few-panel shard: 8-row panels
         hip.check(hip.lib().tf_skinny_qkv_rope_n8(_ptr(wqkv.wp_rope_n8), xp, xsm, xsk, _ptr(ln), float(eps), _ptr(ss_in),
