@@ -485,6 +485,12 @@ int tf_sg_workspace(void* ws, int64_t bytes);
  * Sampling / accept-rollback (utils/sampling.py:63-75, utils/decoding.py:97-134,190-220).
  * tf_sample_inverse_cdf: token = first index whose inclusive cumulative sum of probs exceeds
  *                        u * sum(probs)  (stand-in for torch.multinomial with an explicit uniform).
+ *                        Only an index with non-zero mass is ever returned.  When no cumulative sum
+ *                        exceeds u * sum(probs) (u = 1.0 reaches the total exactly, or the product
+ *                        rounds past it) the token is the LAST index with non-zero mass, not V - 1.
+ *                        A row with no mass at all (every entry <= 0) gives token 0.  The same two
+ *                        rules hold for every draw below: the residual, the bonus and the follow-up
+ *                        sample, and the final draw of tf_tree_accept.
  * tf_accept_chain      : sequential speculative accept test of g2 drafted tokens against the
  *                        target distribution rows p[0..g2] and the drafting rows q[0..g2-1]:
  *                        flag_i = u_i < min(1, p_i[x_i]/q_i[x_i])  (<= when inclusive), count =

@@ -233,11 +233,15 @@ def max_fn(x):
 
 def sample_inverse_cdf(probs, u):
     """Injected-RNG stand-in for torch.multinomial(probs, 1) (sampling.py:63-66): first index
-    whose inclusive fp32 cumulative sum exceeds u * total.  Same distribution, explicit u."""
+    whose inclusive fp32 cumulative sum exceeds u * total.  Same distribution, explicit u.  When no sum exceeds
+    the target (u = 1.0, or the product rounded past the end) the token is the last index with non-zero mass; a row with no
+    mass at all gives token 0 (include/triforce_hip.h, the sampling section: the kernels' rule)."""
     c = torch.cumsum(probs.float(), dim=-1)
     tgt = float(u) * float(c[-1])
     idx = int(torch.searchsorted(c, torch.tensor(tgt, dtype=c.dtype), right=True))
     nz = torch.nonzero(probs > 0).flatten()
+    if nz.numel() == 0:
+        return 0
     if idx >= probs.numel() or probs[idx] <= 0:      # guard rounding at the tail / zero bins
         cand = nz[nz >= idx]
         idx = int(cand[0]) if cand.numel() else int(nz[-1])
