@@ -808,6 +808,29 @@ int tf_rope_append_gqa(const void* qkv, int64_t qkv_row_stride, const void* cos,
                        int rows, int H, int Hkv, int D, int rotate_k, void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * QK NORM.  Qwen3-style targets normalise every q and k head over the head width before the rotation:
+ * one [D] fp16 weight for all query heads (q_norm_w), one for all KV heads (k_norm_w), eps = the model's rms_norm_eps.
+ * For one token row and one head, with x[0..D) the fp16 values of the q or k projection as the GEMM rounded them:
+ *   ms   = (sum_d float(x[d])^2) / D          fp32; the sum in any order
+ *   inv  = 1.0f / sqrtf(ms + eps)             fp32 (the expression of tf_rmsnorm)
+ *   n[d] = fp16(float(x[d]) * inv)            cast BEFORE the weight multiply
+ *   y[d] = hmul_rn(w[d], n[d])                fp16
+ * — the rounding points of tf_rmsnorm (fp32 normalise -> fp16 -> times weight).  The fp16 rotation of tf_rope_append then
+ * acts on y: hadd_rn(hmul_rn(y, cos), hmul_rn(rotate_half(y), sin)).
+ * tf_qk_norm_rope_append: tf_rope_append_gqa with that norm in front of the rotation.  qkv rows [q: H D | k: Hkv D | v: Hkv D]
+ *   fp16 at qkv + row * qkv_row_stride; q -> q_out[row][head][D]; k -> cache row slot0 + row (or *slot0_dev + row) of its KV
+ *   head, normalised and, unless rotate_k == 0, rotated; v copied untouched.  Hkv == H is the multi-head case.  D = 64 or 128.
+ *   TF_EINVAL: a NULL buffer, rows < 0, H or Hkv < 1, H % Hkv != 0, H > 65535, D outside {64, 128}, a norm weight that is not
+ *   16-byte aligned, eps < 0 or NaN.  rows == 0 is a no-op after these gates.  One launch: one wave per (row, head), four
+ *   waves per workgroup, no LDS, no workspace.
+ * ------------------------------------------------------------------------------------------- */
+int tf_qk_norm_rope_append(const void* qkv, int64_t qkv_row_stride, const void* cos, const void* sin,
+                           const int64_t* positions, void* q_out, void* k_cache, void* v_cache,
+                           int64_t stride_t, int64_t stride_h, int slot0, const int32_t* slot0_dev,
+                           int rows, int H, int Hkv, int D, int rotate_k, const void* q_norm_w, const void* k_norm_w,
+                           float eps, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * PER-TOKEN LOG-PROBABILITIES.  For fp32 logits rows x[r] (row r at logits + r * row_stride,
  * row_stride >= V elements) and a target id per row:
  *   logprob[r] = x[r][t] - max_i x[r][i] - log sum_i exp(x[r][i] - max_i x[r][i]),   lse[r] = max + log sum

@@ -131,6 +131,65 @@ __global__ void rope_append_gqa_kernel(const h16* __restrict__ qkv, int64_t row_
     vc[d + half] = vp[d + half];
 }
 
+// ---- QK norm: per-head RMSNorm of q and k -> RoPE -> KV append ------------------------------------------
+// One wave per (row, unit): units 0..H-1 are the query heads, H..H+Hkv-1 the KV heads (k normalised and stored, v copied).
+// Lane l holds the rotary pair (l, l + D/2) of its head, so the sum of squares is one wave reduction and the rotation needs
+// no exchange; D = 64 fills half a wave.  Four waves per workgroup, no LDS.  Rounding points: include/triforce_hip.h
+// "QK NORM" (those of rmsnorm_kernel, then those of rope_append_kernel).
+// fp16(a * b) with the contract's TWO roundings: the product to fp32, that to fp16.  Written as (h16)(a * b) the compiler
+// folds the pair into v_fma_mixlo_f16, which rounds the exact product once — one fp16 ulp apart wherever the fp32 product
+// lands on an fp16 midpoint (found by the exact probes of tests/test_gpu_qk_norm.py).  The empty asm keeps the fp32 value.
+__device__ __forceinline__ h16 mul_f32_then_h16(float a, float b) {
+    float p = a * b;
+    asm volatile("" : "+v"(p));
+    return (h16)p;
+}
+
+__global__ __launch_bounds__(256) void qk_norm_rope_append_kernel(
+        const h16* __restrict__ qkv, int64_t row_stride, const h16* __restrict__ cosb, const h16* __restrict__ sinb,
+        const int64_t* __restrict__ positions, h16* __restrict__ q_out, h16* __restrict__ k_cache, h16* __restrict__ v_cache,
+        int64_t stride_t, int64_t stride_h, int slot0, const int32_t* __restrict__ slot0_dev, const h16* __restrict__ qn,
+        const h16* __restrict__ kn, float eps, int64_t units, int H, int Hkv, int D, int rotate_k) {
+    const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (u >= units) return;                         // (whole waves leave: no barrier below)
+    const int lane = threadIdx.x & 63, half = D >> 1, per_row = H + Hkv;
+    const int64_t row = u / per_row;
+    const int hu = (int)(u - row * per_row);        // q heads and k heads are contiguous in the row: head hu at hu * D
+    const bool is_k = hu >= H, act = lane < half;
+    const int h = is_k ? hu - H : hu;
+    const h16* src = qkv + row * row_stride + (int64_t)hu * D;
+    const h16 x1 = act ? src[lane] : (h16)0.f, x2 = act ? src[lane + half] : (h16)0.f;
+    const float f1 = (float)x1, f2 = (float)x2;
+    const float ss = wave_sum(fmaf(f1, f1, f2 * f2));
+    const float inv = 1.0f / sqrtf(ss / (float)D + eps);
+    if (!act) return;
+    const h16* w = is_k ? kn : qn;
+    const h16 y1 = hmul_rn(w[lane], mul_f32_then_h16(f1, inv));             // cast BEFORE the weight multiply
+    const h16 y2 = hmul_rn(w[lane + half], mul_f32_then_h16(f2, inv));
+    h16 o1 = y1, o2 = y2;
+    if (!is_k || rotate_k) {
+        const int64_t pos = positions[row];
+        const h16 c1 = cosb[pos * D + lane], c2 = cosb[pos * D + lane + half];
+        const h16 s1 = sinb[pos * D + lane], s2 = sinb[pos * D + lane + half];
+        o1 = hadd_rn(hmul_rn(y1, c1), hmul_rn((h16)(-(float)y2), s1));
+        o2 = hadd_rn(hmul_rn(y2, c2), hmul_rn(y1, s2));
+    }
+    if (!is_k) {
+        h16* qo = q_out + (row * H + h) * D;
+        qo[lane] = o1;
+        qo[lane + half] = o2;
+        return;
+    }
+    const int64_t slot = (int64_t)(slot0_dev ? *slot0_dev : slot0) + row;
+    h16* kc = k_cache + slot * stride_t + (int64_t)h * stride_h;
+    h16* vc = v_cache + slot * stride_t + (int64_t)h * stride_h;
+    const h16* vp = src + (int64_t)Hkv * D;
+    kc[lane] = o1;
+    kc[lane + half] = o2;
+    vc[lane] = vp[lane];
+    vc[lane + half] = vp[lane + half];
+}
+
 __global__ __launch_bounds__(256) void silu_mul_kernel(const h16* __restrict__ gu, h16* __restrict__ out, int I,
                                                        int64_t total_vec) {
     const int vpr = I / 8;
@@ -184,6 +243,28 @@ extern "C" int tf_rope_append_gqa(const void* qkv, int64_t qkv_row_stride, const
     hipLaunchKernelGGL(rope_append_gqa_kernel, dim3(rows, H), dim3(D / 2), 0, (hipStream_t)stream, (const h16*)qkv,
                        qkv_row_stride, (const h16*)cosb, (const h16*)sinb, positions, (h16*)q_out, (h16*)k_cache,
                        (h16*)v_cache, stride_t, stride_h, slot0, slot0_dev, H, Hkv, D, rotate_k);
+    TF_LAUNCH_CHECK();
+    return TF_OK;
+}
+
+// tf_rope_append_gqa behind a per-head RMSNorm of q and k (QK norm): q_norm_w / k_norm_w are the [D] fp16
+// weights shared by all query / KV heads, eps the model's rms_norm_eps.  Hkv == H is the multi-head case.
+extern "C" int tf_qk_norm_rope_append(const void* qkv, int64_t qkv_row_stride, const void* cosb, const void* sinb,
+                                      const int64_t* positions, void* q_out, void* k_cache, void* v_cache, int64_t stride_t,
+                                      int64_t stride_h, int slot0, const int32_t* slot0_dev, int rows, int H, int Hkv, int D,
+                                      int rotate_k, const void* q_norm_w, const void* k_norm_w, float eps, void* stream) {
+    if (!qkv || !cosb || !sinb || !positions || !q_out || !k_cache || !v_cache || !q_norm_w || !k_norm_w) return TF_EINVAL;
+    if (rows < 0 || H < 1 || Hkv < 1 || (H % Hkv) || (D != 64 && D != 128)) return TF_EINVAL;
+    if (H > 65535) return TF_EINVAL;
+    if (((uintptr_t)q_norm_w | (uintptr_t)k_norm_w) & 15) return TF_EINVAL;
+    if (!(eps >= 0.f)) return TF_EINVAL;
+    if (rows == 0) return TF_OK;
+    const int64_t units = (int64_t)rows * (H + Hkv), gx = (units + 3) / 4;
+    if (gx > 0x7fffffffLL) return TF_EINVAL;
+    hipLaunchKernelGGL(qk_norm_rope_append_kernel, dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream, (const h16*)qkv,
+                       qkv_row_stride, (const h16*)cosb, (const h16*)sinb, positions, (h16*)q_out, (h16*)k_cache,
+                       (h16*)v_cache, stride_t, stride_h, slot0, slot0_dev, (const h16*)q_norm_w, (const h16*)k_norm_w, eps,
+                       units, H, Hkv, D, rotate_k);
     TF_LAUNCH_CHECK();
     return TF_OK;
 }

@@ -169,6 +169,10 @@ SIGNATURES["tf_skinny_qkv_rope_gqa_act"] = (_i32, [_vp, _vp, _i64, _i64, _vp, _f
 SIGNATURES["tf_rope_append_gqa"] = (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i32, _i32, _i32,
                                            _i32, _i32, _vp])
 
+# QK norm (include/triforce_hip.h "QK NORM")
+SIGNATURES["tf_qk_norm_rope_append"] = (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i32, _i32, _i32,
+                                               _i32, _i32, _vp, _vp, _f32, _vp])
+
 # per-token log-probabilities (include/triforce_hip.h "PER-TOKEN LOG-PROBABILITIES")
 SIGNATURES["tf_token_logprobs"] = (_i32, [_vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp])
 SIGNATURES["tf_token_logprobs_ids"] = (_i32, [_vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp])

@@ -25,7 +25,7 @@ from .. import ops
 from ..utils.sampling import norm_logits
 from .cache import (DistributedKVCacheBuffer, DistributedRetrievalCache, DistributedRetrievalCache_Seqouia,
                     DistributedSimpleCache, _refuse_fp8, _refuse_retrieval_fp8)
-from .config_yarn import LlamaConfig, refuse_attention_bias, refuse_gqa
+from .config_yarn import LlamaConfig, refuse_attention_bias, refuse_gqa, refuse_qk_norm
 from .llama_core import (RETRIEVAL_WEIGHTS_ENV, DecoderLayers, LlamaWeights, parse_random_spec, retrieval_weights, rope_tables_for,
                          softmax_scale_for)
 from .TP_layers import DistributedOffloadingConfig
@@ -67,6 +67,7 @@ class DistributedLlama:
         model_config = config if config is not None else LlamaConfig.from_pretrained(model_name_or_path)
         refuse_gqa(model_config, "the tensor-parallel / Sequoia engine (TP_llama.DistributedLlama, TP_llama_tree)")
         refuse_attention_bias(model_config, "the tensor-parallel / Sequoia engine (TP_llama.DistributedLlama, TP_llama_tree)")
+        refuse_qk_norm(model_config, "the tensor-parallel / Sequoia engine (TP_llama.DistributedLlama, TP_llama_tree)")
         self.model_name_or_path = model_name_or_path
         self.config = DistributedOffloadingConfig(model_config, local_rank, world_size)
         self.on_chip_layers = min(on_chip_layers, model_config.num_hidden_layers)

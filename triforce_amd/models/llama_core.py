@@ -25,8 +25,8 @@ def rope_tables_plain(dim, max_pos, base):
     return emb.cos().to(torch.float16), emb.sin().to(torch.float16)
 
 
-def rope_tables_yarn(dim, max_pos, factor, orig_max_pos, base=10000.0, beta_fast=32, beta_slow=1):
-    """reference models/modeling_llama.py:50-124 (YaRN; base hard-wired to 10000 at :193)."""
+def yarn_inv_freq(dim, factor, orig_max_pos, base=10000.0, beta_fast=32, beta_slow=1):
+    """(inverse frequencies (dim/2,) fp32, attention factor) of YaRN: reference models/modeling_llama.py:50-107."""
     def corr_dim(n_rot):
         return (dim * math.log(orig_max_pos / (n_rot * 2 * math.pi))) / (2 * math.log(base))
 
@@ -41,6 +41,12 @@ def rope_tables_yarn(dim, max_pos, factor, orig_max_pos, base=10000.0, beta_fast
     mask = 1 - ramp
     inv_freq = inv_interpolation * (1 - mask) + inv_extrapolation * mask
     mscale = 1.0 if factor <= 1 else 0.1 * math.log(factor) + 1.0
+    return inv_freq, mscale
+
+
+def rope_tables_yarn(dim, max_pos, factor, orig_max_pos, base=10000.0, beta_fast=32, beta_slow=1):
+    """reference models/modeling_llama.py:50-124 (YaRN; base hard-wired to 10000 at :193)."""
+    inv_freq, mscale = yarn_inv_freq(dim, factor, orig_max_pos, base, beta_fast, beta_slow)
     freqs = torch.outer(torch.arange(max_pos, dtype=torch.float32), inv_freq)
     emb = torch.cat((freqs, freqs), dim=-1)
     return (emb.cos() * mscale).to(torch.float16), (emb.sin() * mscale).to(torch.float16)
@@ -51,6 +57,11 @@ def rope_tables_for(cfg, force_plain=False):
     rs = cfg.rope_scaling
     if rs is None or force_plain:
         return rope_tables_plain(D, cfg.max_position_embeddings, cfg.rope_theta)
+    if getattr(cfg, "qk_norm", False):
+        # a QK-norm (Qwen3-family) config: YaRN over the model's own theta.  Llama / Qwen2 configs keep the reference's
+        # hard-wired base 10000
+        return rope_tables_yarn(D, cfg.max_position_embeddings, rs["factor"], rs["original_max_position_embeddings"],
+                                base=float(cfg.rope_theta))
     return rope_tables_yarn(D, cfg.max_position_embeddings, rs["factor"], rs["original_max_position_embeddings"])
 
 
@@ -65,6 +76,10 @@ RETRIEVAL_WEIGHTS_ENV = "TRIFORCE_RETRIEVAL_WEIGHTS"
 # 0.02 on purpose: trained q/k biases are O(1) and larger, and a bias that moved no logit would make every test of the biased
 # path vacuous (tests/test_attn_bias_cpu.py pins that zeroing the biases changes the greedy stream).
 BIAS_STD = 0.5
+# Standard deviation of the randomly drawn q_norm / k_norm weights around 1 (init_random of a QK-norm config, DESIGN section
+# 30): trained ones spread far wider; 0.25 moves the greedy stream of the tiny models well clear of the norm-free one
+# (tests/test_qk_norm_cpu.py pins that).
+QK_NORM_STD = 0.25
 
 
 def retrieval_weights():
@@ -103,6 +118,12 @@ class LlamaWeights:
         if self.attn_bias and world_size > 1:
             raise ValueError(f"attention bias is not supported by tensor-parallel weight shards (world_size={world_size}): "
                              "the shard's 8-row-panel and exchange GEMMs are bias-free")
+        # QK norm: per-head RMSNorm of q and k before the rotation, one [D] weight each per layer
+        self.qk_norm = bool(getattr(cfg, "qk_norm", False))
+        if self.qk_norm and world_size > 1:
+            raise ValueError(f"QK norm is not supported by tensor-parallel weight shards (world_size={world_size}): the "
+                             "shard's fused q|k|v GEMMs rotate un-normalised heads")
+        self.qn, self.kn = [], []                       # per layer: fp16 (D,) tensors
         self.bqkv, self.bo = [], []                     # per layer: fp16 (N,) tensors; bo[i] is None without an o_proj bias
         assert self.H % world_size == 0 and cfg.intermediate_size % world_size == 0
         self.H_local = self.H // world_size
@@ -140,6 +161,7 @@ class LlamaWeights:
             self.wqkv.append(torch.cat([q, k, v], dim=0).contiguous().to(dev))
             self.wo.append(self._shard_cols(get(p + "self_attn.o_proj.weight"), hd).contiguous().to(dev))
             self._load_attn_bias(sd, i, dev)
+            self._load_qk_norm(sd, i, dev)
             g = self._shard_rows(get(p + "mlp.gate_proj.weight"), self.I_local)
             u = self._shard_rows(get(p + "mlp.up_proj.weight"), self.I_local)
             self.wgu.append(torch.cat([g, u], dim=0).contiguous().to(dev))
@@ -170,6 +192,24 @@ class LlamaWeights:
         self.bqkv.append(b.to(dev))
         self.bo.append(sd[p + "o_proj.bias"].to(torch.float16).reshape(-1).contiguous().to(dev) if has_o else None)
 
+    def _load_qk_norm(self, sd, i, dev):
+        """self_attn.{q,k}_norm.weight of layer i: both or neither, and their presence must agree with config.qk_norm — a
+        checkpoint with norms the path would skip, or without norms it would apply, is another model."""
+        p = f"model.layers.{i}.self_attn."
+        have = [n for n in ("q", "k") if p + n + "_norm.weight" in sd]
+        if len(have) == 1:
+            raise ValueError(f"layer {i}: QK norm weight present for {have[0]}_norm only; q_norm and k_norm come together")
+        if bool(have) != self.qk_norm:
+            raise ValueError(f"layer {i}: the checkpoint has {'q_norm / k_norm weights' if have else 'no q_norm / k_norm weights'}"
+                             f" but the config says qk_norm={self.qk_norm}")
+        if not self.qk_norm:
+            return
+        for lst, n in ((self.qn, "q"), (self.kn, "k")):
+            w = sd[p + n + "_norm.weight"].to(torch.float16).reshape(-1).contiguous()
+            if w.numel() != self.D:
+                raise ValueError(f"layer {i}: {n}_norm weight has {w.numel()} entries, expected head_dim = {self.D}")
+            lst.append(w.to(dev))
+
     def _o_bias_drawn(self):
         """Does a random draw give o_proj a bias?  Every bias config but the Qwen2 family's (q/k/v only)."""
         return self.attn_bias and getattr(self.cfg, "model_type", "llama") != "qwen2"
@@ -179,7 +219,8 @@ class LlamaWeights:
         modeling_llama.py:306-315; every rank draws the full matrix stream and keeps its shard
         only for the small configs — for big models each tensor is drawn shard-sized with a
         (seed, layer, name, rank)-derived generator.  A bias config draws its biases N(0, bias_std) from tags of their own
-        (("bqkv", layer, rank), ("bo", layer, rank)): the matrices are the bias-free draw, bit for bit."""
+        (("bqkv", layer, rank), ("bo", layer, rank)): the matrices are the bias-free draw, bit for bit.  A QK-norm config
+        draws its norm weights 1 + QK_NORM_STD * N(0, 1) from ("qn", layer) / ("kn", layer) in the same way."""
         dev, cfg = self.device, self.cfg
         hid, hd = cfg.hidden_size, self.H_local * self.D
 
@@ -197,6 +238,9 @@ class LlamaWeights:
             if self.attn_bias:
                 self.bqkv.append(draw(("bqkv", i, self.rank), hd + 2 * self.Hkv_local * self.D, s=bias_std))
                 self.bo.append(draw(("bo", i, self.rank), hid, s=bias_std) if self._o_bias_drawn() else None)
+            if self.qk_norm:
+                self.qn.append((1.0 + draw(("qn", i), self.D, s=QK_NORM_STD).float()).to(torch.float16))
+                self.kn.append((1.0 + draw(("kn", i), self.D, s=QK_NORM_STD).float()).to(torch.float16))
             self.wgu.append(draw(("gu", i, self.rank), 2 * self.I_local, hid))
             self.wd.append(draw(("d", i, self.rank), hid, self.I_local))
             self.ln1.append(torch.ones(hid, dtype=torch.float16, device=dev))
@@ -226,6 +270,10 @@ class LlamaWeights:
                 if lst[i].bias is not None:             # (wqkv / wo of a bias config; refresh_ re-derives the rotary copy)
                     draw_into(lst[i].bias, ("b" + tag, i, self.rank), s=bias_std)
                 lst[i].refresh_()
+            if self.qk_norm:
+                for lst, tag in ((self.qn, "qn"), (self.kn, "kn")):
+                    draw_into(lst[i], (tag, i), s=QK_NORM_STD)
+                    lst[i].copy_((1.0 + lst[i].float()).to(torch.float16))
             self.ln1[i].fill_(1.0)
             self.ln2[i].fill_(1.0)
         self.aligned = None
@@ -235,7 +283,8 @@ class LlamaWeights:
         """Aligned synthetic weights (models/aligned.py): real shapes, dense values, planted successor table so that
         draft / retrieval / full-cache forwards agree to a tunable degree."""
         from . import aligned
-        from .config_yarn import refuse_attention_bias, refuse_gqa
+        from .config_yarn import refuse_attention_bias, refuse_gqa, refuse_qk_norm
+        refuse_qk_norm(self.cfg, "aligned synthetic weights (models/aligned.py init_aligned)")
         refuse_gqa(self.cfg, "aligned synthetic weights (models/aligned.py init_aligned)")
         refuse_attention_bias(self.cfg, "aligned synthetic weights (models/aligned.py init_aligned)")
         return aligned.init_weights(self, spec, role, attn_keys=attn_keys)
@@ -250,7 +299,16 @@ class LlamaWeights:
         if tied:
             self.embed = self.lm_head.w
         rope = (self.H_local, self.D) if self.Hkv == self.H else (self.H_local, self.Hkv_local, self.D)
-        if self.attn_bias:
+        if self.qk_norm:
+            # the norm GEMM writes the raw q|k|v rows in natural order and tf_qk_norm_rope_append does the rest: a plain
+            # packed weight, no rotary-order copy
+            if self.retrieval_fp8:
+                raise ValueError(f"QK norm is not supported with {RETRIEVAL_WEIGHTS_ENV}=fp8: no FP8 q|k|v weight (Fp8Linear) "
+                                 "feeds the per-head norm")
+            assert len(self.qn) == len(self.kn) == len(self.wqkv), "a QK-norm config needs its norm weights before finalize()"
+            self.wqkv = [PL(w) for w in self.wqkv]
+            self.wo = [PL(w) for w in self.wo]
+        elif self.attn_bias:
             if self.retrieval_fp8:
                 raise ValueError(f"attention bias is not supported with {RETRIEVAL_WEIGHTS_ENV}=fp8: the FP8 weight kernels "
                                  "have no bias epilogue")
@@ -277,6 +335,9 @@ class LlamaWeights:
         if self.attn_bias:
             raise ValueError(f"attention bias is not supported with {RETRIEVAL_WEIGHTS_ENV}=fp8: the FP8 weight kernels have "
                              "no bias epilogue")
+        if self.qk_norm:
+            raise ValueError(f"QK norm is not supported with {RETRIEVAL_WEIGHTS_ENV}=fp8: no FP8 q|k|v weight (Fp8Linear) feeds "
+                             "the per-head norm")
         for pl in [self.lm_head] + self.wqkv + self.wo + self.wgu + self.wd:
             if pl.fp8 is None:
                 pl.fp8 = ops.Fp8Linear(pl)
@@ -288,7 +349,7 @@ class LlamaWeights:
 
     def nbytes(self):
         ts = [self.embed, self.lm_head, self.norm] + self.wqkv + self.wo + self.wgu + self.wd + self.ln1 + self.ln2
-        ts = [ops._w(t) for t in ts] + [b for b in self.bqkv + self.bo if b is not None]
+        ts = [ops._w(t) for t in ts] + [b for b in self.bqkv + self.bo if b is not None] + self.qn + self.kn
         return sum(t.numel() * t.element_size() for t in ts)
 
 
@@ -331,6 +392,12 @@ class DecoderLayers:
         """[norm ->] q|k|v GEMM -> RoPE -> K/V rows into kl / vl at ``slot`` (or the device scalar slot_dev); returns q."""
         W = self.W
         w = W.wqkv[i]
+        if W.qk_norm:                               # norm GEMM -> raw row-major q|k|v rows, then per-head norm -> RoPE -> append
+            assert not f8, "a QK-norm model has no FP8 q|k|v weight"
+            rows = torch.empty(x.shape[0], w.N, dtype=torch.float16, device=W.device)
+            ops.linear(x, w, ln=W.ln1[i], eps=W.eps, ss_in=ss if i > 0 else None, out=rows)
+            return ops.qk_norm_rope_append(rows, W.qn[i], W.kn[i], W.eps, self.cos, self.sin, pos, kl, vl, slot, W.H_local, W.D,
+                                           rotate_k=self.rotate_k, slot0_dev=slot_dev, **self._kv_heads())
         return ops.qkv_rope(x, w.fp8 if f8 else w, W.ln1[i], W.eps, self.cos, self.sin, pos, kl, vl, slot, W.H_local, W.D,
                             rotate_k=self.rotate_k, slot0_dev=slot_dev, ss_in=ss if i > 0 else None, **self._kv_heads(),
                             **self._bias(w, rope=True))
@@ -368,6 +435,9 @@ class DecoderLayers:
             h = ops.rmsnorm(x, W.ln1[i], W.eps)
         else:                                       # x += mlp_out of the previous layer, fused into the norm
             h = ops.rmsnorm(d, W.ln1[i], W.eps, residual=x, sum_out=x)
+        if W.qk_norm:
+            return ops.qk_norm_rope_append(ops.linear(h, W.wqkv[i]), W.qn[i], W.kn[i], W.eps, self.cos, self.sin, pos, kl, vl,
+                                           slot, W.H_local, W.D, rotate_k=self.rotate_k, slot0_dev=slot_dev, **self._kv_heads())
         return ops.rope_append(ops.linear(h, W.wqkv[i], **self._bias(W.wqkv[i])), self.cos, self.sin, pos, kl, vl, slot, W.H_local, W.D,
                                rotate_k=self.rotate_k, slot0_dev=slot_dev, **self._kv_heads())
 

@@ -44,6 +44,11 @@ class LlamaForCausalLM:
             from .llama_core import RETRIEVAL_WEIGHTS_ENV
             raise ValueError(f"attention bias is not supported with {RETRIEVAL_WEIGHTS_ENV}=fp8: the FP8 weight kernels "
                              "(Fp8Linear) have no bias epilogue")
+        if getattr(config, "qk_norm", False) and retrieval_weights() == "fp8":
+            # QK norm: the per-head norm sits between the q|k|v GEMM and the rotation the FP8 kernel fuses
+            from .llama_core import RETRIEVAL_WEIGHTS_ENV
+            raise ValueError(f"QK norm is not supported with {RETRIEVAL_WEIGHTS_ENV}=fp8: no FP8 q|k|v weight (Fp8Linear) "
+                             "feeds the per-head norm")
         self.weights = LlamaWeights(config, self.device)
         # TRIFORCE_RETRIEVAL_WEIGHTS=fp8: the retrieval-cache (spec) forward streams FP8 copies of its five GEMM weights
         # (DESIGN section 16); every other forward keeps the fp16 weights
@@ -126,7 +131,7 @@ class LlamaForCausalLM:
         # decode-sized blocks run the fused kernels: [norm ->] qkv GEMM -> RoPE -> KV append in one launch, the
         # residual adds in the o / down GEMM epilogues, the post-attention norm in the gate|up GEMM prologue
         fused = (ops.FUSE_MODE == "all" and ops.can_fuse_rows(q_len, W.embed, W.wqkv[0], W.wo[0], W.wgu[0], W.wd[0], W.lm_head)
-                 and W.wqkv[0].wp_rope is not None)
+                 and (W.qk_norm or W.wqkv[0].wp_rope is not None))
         # the retrieval-verify tier: a spec forward with FP8 weights (ops.Fp8Linear) in its five GEMMs
         f8 = spec and W.fp8_active()
         if f8 and not fused:

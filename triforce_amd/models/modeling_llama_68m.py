@@ -6,7 +6,7 @@ re-applied to every cached key on read with cache-relative positions (:151-178);
 import torch
 
 from .. import ops
-from .config_yarn import LlamaConfig, refuse_attention_bias, refuse_gqa
+from .config_yarn import LlamaConfig, refuse_attention_bias, refuse_gqa, refuse_qk_norm
 from .llama_core import (CausalLMOutput, DecoderLayers, LlamaWeights, load_checkpoint_state_dict, parse_random_spec,
                          rope_tables_plain, softmax_scale_for)
 
@@ -18,6 +18,7 @@ class LlamaForCausalLM:
         self.dtype = torch.float16
         refuse_gqa(config, "the 68M draft model (modeling_llama_68m; TfDraftModel has one head count)")
         refuse_attention_bias(config, "the 68M draft model (modeling_llama_68m; tf_draft_forward_68m has no bias operands)")
+        refuse_qk_norm(config, "the 68M draft model (modeling_llama_68m; tf_draft_forward_68m has no q/k norm)")
         self.weights = LlamaWeights(config, self.device)
         D = config.hidden_size // config.num_attention_heads
         cos, sin = rope_tables_plain(D, config.max_position_embeddings, config.rope_theta)   # 68m.py:123-128

@@ -53,6 +53,22 @@ CONFIGS = {
                           num_attention_heads=28, num_key_value_heads=4, max_position_embeddings=1010000, rms_norm_eps=1e-6,
                           rope_theta=1e7, attention_bias=True, model_type="qwen2", bos_token_id=151643, eos_token_id=151645,
                           _name_or_path="Qwen/Qwen2.5-7B-Instruct-1M"),
+    # the tiny targets with QK norm: per-head RMSNorm of q and k before the rotation.  "tiny" with plain RoPE
+    # at theta 1e6, "tiny-gqa" as a Qwen3-form config (model_type qwen3 implies the norms when a config.json is read; here
+    # the key is spelled out)
+    "tiny-qknorm": dict(hidden_size=256, intermediate_size=768, num_hidden_layers=2, num_attention_heads=2,
+                        max_position_embeddings=131072, rms_norm_eps=1e-6, rope_theta=1e6, qk_norm=True,
+                        _name_or_path="tiny-qknorm-target"),
+    "tiny-gqa-qknorm": dict(hidden_size=512, intermediate_size=768, num_hidden_layers=2, num_attention_heads=4,
+                            num_key_value_heads=2, max_position_embeddings=131072, rms_norm_eps=1e-6, rope_theta=1e6,
+                            qk_norm=True, model_type="qwen3", _name_or_path="tiny-gqa-qknorm-target"),
+    # Qwen/Qwen3-8B shape (grouped-query 32 / 8 heads, head_dim 128 = hidden / heads, q_norm / k_norm, plain RoPE with theta
+    # 1e6).  Written from memory of the model card: there is no hub access offline, so these values are NOT checked against
+    # the published config.json
+    "qwen3-8B": dict(vocab_size=151936, hidden_size=4096, intermediate_size=12288, num_hidden_layers=36,
+                     num_attention_heads=32, num_key_value_heads=8, max_position_embeddings=40960, rms_norm_eps=1e-6,
+                     rope_theta=1e6, qk_norm=True, model_type="qwen3", bos_token_id=151643, eos_token_id=151645,
+                     _name_or_path="Qwen/Qwen3-8B"),
     # the tiny target and the 68M-shaped draft with the Llama-3 vocabulary (128 256 entries).  No trained
     # draft of that vocabulary exists offline: both are random-init shapes
     "tiny-v128k": dict(vocab_size=128256, hidden_size=256, intermediate_size=768, num_hidden_layers=2, num_attention_heads=2,

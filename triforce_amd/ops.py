@@ -705,6 +705,61 @@ def rope_append(qkv, cos, sin, positions, k_layer, v_layer, slot0, H, D, rotate_
     return q
 
 
+def qk_norm_rope_append(qkv, qn, kn, eps, cos, sin, positions, k_layer, v_layer, slot0, H, D, rotate_k=True, slot0_dev=None,
+                        Hkv=None):
+    """rope_append for a QK-norm model: every q and k head of the fused rows [q: H D | k: Hkv D | v: Hkv D]
+    goes through an RMSNorm over the head width (``qn`` / ``kn``: the [D] fp16 weights, ``eps``) before the rotation; k rows
+    (rotated unless rotate_k is False) and the untouched v rows land in the cache at slot0+i.  Returns q (rows,H,D).
+    One kernel, tf_qk_norm_rope_append, for decode blocks and prefill chunks, multi-head (Hkv None or H) and grouped-query."""
+    _dev(qkv, qn, kn, cos, sin, positions, k_layer, v_layer, slot0_dev)
+    Hkv = H if Hkv is None else Hkv
+    rows = qkv.shape[0]
+    assert qkv.dtype == _HALF and qkv.dim() == 2 and qkv.stride(1) == 1 and qkv.shape[1] == (H + 2 * Hkv) * D and H % Hkv == 0
+    assert positions.dtype == torch.int64 and positions.numel() == rows and positions.is_contiguous()
+    assert cos.dtype == _HALF and cos.is_contiguous() and cos.shape[1] == D and sin.shape == cos.shape and sin.is_contiguous()
+    for w in (qn, kn):
+        assert w.dtype == _HALF and tuple(w.shape) == (D,) and w.is_contiguous()
+    st, sh = _kv(k_layer)
+    assert _kv(v_layer) == (st, sh) and k_layer.shape[0] == Hkv and v_layer.shape[0] == Hkv
+    q = torch.empty(rows, H, D, dtype=_HALF, device=qkv.device)
+    hip.check(hip.lib().tf_qk_norm_rope_append(_ptr(qkv), qkv.stride(0), _ptr(cos), _ptr(sin), _ptr(positions), _ptr(q),
+                                               _ptr(k_layer), _ptr(v_layer), st, sh, int(slot0), _ptr(slot0_dev), rows, H, Hkv,
+                                               D, 1 if rotate_k else 0, _ptr(qn), _ptr(kn), float(eps), _stream()),
+              "tf_qk_norm_rope_append")
+    return q
+
+
+def qk_norm_rope_ref(qkv, qn, kn, eps, cos, sin, positions, H, D, rotate_k=True, Hkv=None):
+    """Host restatement of the QK NORM contract (include/triforce_hip.h) with its rounding points, on any device:
+    -> (q (rows, H, D), k (rows, Hkv, D), v (rows, Hkv, D)) fp16 — what tf_qk_norm_rope_append writes to q_out and to the
+    cache rows.  fp32 sum of squares (torch's order), inv = 1 / sqrt(ms + eps) in IEEE fp32, fp16 cast, fp16 weight multiply, then
+    the fp16 rotation; each fp16 operation is an fp32 operation on fp16 values rounded once, as hmul_rn / hadd_rn are."""
+    Hkv = H if Hkv is None else Hkv
+    rows = qkv.shape[0]
+    q = qkv[:, :H * D].reshape(rows, H, D)
+    k = qkv[:, H * D:(H + Hkv) * D].reshape(rows, Hkv, D)
+    v = qkv[:, (H + Hkv) * D:(H + 2 * Hkv) * D].reshape(rows, Hkv, D).clone()
+    eps32 = torch.tensor(float(eps), dtype=torch.float32, device=qkv.device)
+
+    def norm(x, w):
+        f = x.float()
+        ms = f.pow(2).sum(-1, keepdim=True) / float(D)
+        # fp32 sqrt and divide, each correctly rounded: through float64 (exact for both by 53 >= 2 * 24 + 2), because torch's
+        # vectorised fp32 sqrt on the CPU is not correctly rounded (0.65 % of random inputs are one ulp off)
+        root = torch.sqrt((ms + eps32).double()).float()
+        inv = (1.0 / root.double()).float()
+        return (w.float() * (f * inv).to(_HALF).float()).to(_HALF)
+
+    def rope(y):
+        c, s = cos[positions].float()[:, None, :], sin[positions].float()[:, None, :]
+        f = y.float()
+        rot = torch.cat([-f[..., D // 2:], f[..., :D // 2]], dim=-1)
+        return ((f * c).to(_HALF).float() + (rot * s).to(_HALF).float()).to(_HALF)
+
+    qy, ky = norm(q, qn), norm(k, kn)
+    return rope(qy), (rope(ky) if rotate_k else ky), v
+
+
 def silu_mul(gate_up):
     _dev(gate_up)
     rows, two_i = gate_up.shape
