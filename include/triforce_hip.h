@@ -18,6 +18,14 @@
  *     never synchronises and is hipGraph-capturable; workspaces are caller-provided;
  *   - return value: 0 on success, a negative errno-style code on bad arguments (TF_E*), or the
  *     positive hipError_t of a failed launch.
+ *
+ * ROUNDING OF fp16(a * b).  Wherever a contract below writes fp16(a * b) with an fp32 operand — the
+ * normalisation fp16(x * inv) of every RMSNorm, the FP8 row scale fp16(s[n] * acc), the chunk mean
+ * fp16(sum * (1 / chunk)) — the product is rounded to fp32 and THAT value to fp16: two roundings, as
+ * torch and the reference compute it.  One rounding of the exact product (what a fused multiply-convert
+ * instruction gives) differs by one fp16 spacing wherever the fp32 product lands on an fp16 midpoint;
+ * tests/test_gpu_rounding_probes.py holds every such site to the two roundings on inputs where the
+ * two differ.  (A product of two fp16 values is exact in fp32: there the question does not arise.)
  */
 #ifndef TRIFORCE_HIP_H
 #define TRIFORCE_HIP_H
@@ -196,6 +204,8 @@ int tf_draft_persist_reset(void* ctl, void* host_mirror, int set_mirror);
  * top-k, chunk gather.
  * tf_retrieval_score : scores[h][c] = fp16( q[h] . fp16(mean_{t in chunk c} K[t][h]) ), un-scaled
  *                      (cache.py:154-157).  k rows [0, C*chunk) are read once.
+ *                      mean = fp16(fp32(sum * fp32(1 / chunk))), the sum in fp32 in row order
+ *                      (ROUNDING OF fp16(a * b), above).
  * tf_retrieval_topk  : idx[h][0] = 0, idx[h][1..sets-1] = the sets-1 best chunks of [1,C),
  *                      descending score, ascending chunk index among equal scores
  *                      (cache.py:159-162; torch.topk leaves the tie order undefined).  C <= 32768.
@@ -215,7 +225,8 @@ int tf_retrieval_gather(const void* k_src, const void* v_src, int64_t src_stride
  * of 8, >= the chunks addressed * D).
  * tf_chunk_mean              : for every head and chunk c in [c0, c1):
  *                              index[h][c][d] = fp16( (sum_r float(K[c*chunk + r][h][d])) * (1.0f / chunk) ),
- *                              the sum in fp32 in row order - the mean tf_retrieval_score forms.
+ *                              the sum in fp32 in row order, the product an fp32 value first (ROUNDING OF
+ *                              fp16(a * b), above) - the mean tf_retrieval_score forms.
  *                              Chunks outside [c0, c1) are not written; c1 == c0 launches nothing.
  * tf_retrieval_score_indexed : scores[h][c] = fp16( q[h] . index[h][c] ), c < C, with the dot product
  *                              formed as tf_retrieval_score forms it behind its mean: BIT-IDENTICAL to
@@ -260,7 +271,8 @@ int tf_kv_gather_rows(void* k_cache, void* v_cache, int64_t stride_l, int64_t st
  * Dense-block glue (models/modeling_llama.py:132-159,221-238; models/tensor_op.py:25-64).
  * tf_rmsnorm    : optional fused residual add: s = fp16(x + res) (written to sum_out when
  *                 non-NULL), y = w * fp16(s * rsqrt(mean(s^2)+eps))  — the cast precedes the
- *                 weight multiply exactly as modeling_llama.py:138-143.
+ *                 weight multiply exactly as modeling_llama.py:138-143; the product inside
+ *                 fp16(.) is an fp32 value first (ROUNDING OF fp16(a * b), above).
  * tf_rope_append: split a fused qkv row [q | k | v] (each H*D), rotate q (and k unless
  *                 rotate_k==0) at positions[i] with fp16 tables, write q to q_out [rows][H][D]
  *                 and the k/v rows into the cache at token slot0+i (slot0 read from slot0_dev
@@ -304,7 +316,9 @@ int tf_skinny_gemm_swiglu(const void* gate_packed, const void* up_packed, const 
 /* Fused forms of the same kernel — what sits between the GEMMs of a decoder layer folded into the GEMM that consumes
  * or produces it, with the reference's rounding points (each was a 4-5 us launch of its own at <= 18 rows):
  *   ln_w != NULL : RMSNorm prologue on the input rows, h = ln_w * fp16(x * rsqrt(mean(x^2) + eps))
- *                  (models/modeling_llama.py:138-143, tensor_op.py:52-64); x is then the residual stream.
+ *                  (models/modeling_llama.py:138-143, tensor_op.py:52-64; tf_rmsnorm's rounding points, the product
+ *                  inside fp16(.) an fp32 value first: ROUNDING OF fp16(a * b), top of this file); x is then the
+ *                  residual stream.
  *   resid != NULL: y = fp16(resid + fp16(x . W^T))  (hidden_states = residual + ..., modeling_llama.py:278,284);
  *                  y may alias resid (every element is read and written by the same lane).
  *   ss_out != NULL (with a fp16 output): every panel also writes sum(y[m][n]^2) over its 16 columns to
@@ -380,7 +394,8 @@ int tf_skinny_qkv_rope_n8(const void* wqkv_n8, const void* x, int64_t xs_m, int6
  *   weight-only: activations stay fp16; the codes are decoded to fp16 exactly (scale 1.0) and multiplied on the 16-bit
  *     kernel's f16 MFMA with fp32 accumulation (no fp8 x fp8 / MX-scaled MFMA: those would quantize the activations);
  *   the row scale is applied ONCE, in fp32, on the accumulator, where the 16-bit kernel rounds: fp16(s[n] * acc) instead
- *     of fp16(acc); gate|up: s_gate and s_up before their separate fp16 roundings.  Every other rounding point — norm
+ *     of fp16(acc), the scaled accumulator an fp32 value first (ROUNDING OF fp16(a * b), top of this file); gate|up: s_gate
+ *     and s_up before their separate fp16 roundings.  Every other rounding point — norm
  *     prologue, residual add, SwiGLU, RoPE + append, the fp32 cast of the logits, ss_in / ss_out — is the 16-bit form's.
  * Codes packed by triforce_amd.ops.pack_weight_fp8: [N/16][K/64][4 (g)][16 (i)][16 B], the 16 bytes of piece (g, i) =
  * W[n0+i][k0+8g .. +7] then W[n0+i][k0+32+8g .. +7]: one 16x64 tile is one contiguous KiB.  `scale` / `gate_scale` /

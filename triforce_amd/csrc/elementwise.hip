@@ -136,15 +136,6 @@ __global__ void rope_append_gqa_kernel(const h16* __restrict__ qkv, int64_t row_
 // Lane l holds the rotary pair (l, l + D/2) of its head, so the sum of squares is one wave reduction and the rotation needs
 // no exchange; D = 64 fills half a wave.  Four waves per workgroup, no LDS.  Rounding points: include/triforce_hip.h
 // "QK NORM" (those of rmsnorm_kernel, then those of rope_append_kernel).
-// fp16(a * b) with the contract's TWO roundings: the product to fp32, that to fp16.  Written as (h16)(a * b) the compiler
-// folds the pair into v_fma_mixlo_f16, which rounds the exact product once — one fp16 ulp apart wherever the fp32 product
-// lands on an fp16 midpoint (found by the exact probes of tests/test_gpu_qk_norm.py).  The empty asm keeps the fp32 value.
-__device__ __forceinline__ h16 mul_f32_then_h16(float a, float b) {
-    float p = a * b;
-    asm volatile("" : "+v"(p));
-    return (h16)p;
-}
-
 __global__ __launch_bounds__(256) void qk_norm_rope_append_kernel(
         const h16* __restrict__ qkv, int64_t row_stride, const h16* __restrict__ cosb, const h16* __restrict__ sinb,
         const int64_t* __restrict__ positions, h16* __restrict__ q_out, h16* __restrict__ k_cache, h16* __restrict__ v_cache,

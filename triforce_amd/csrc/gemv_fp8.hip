@@ -289,7 +289,7 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_fp8_kernel(const u32x4
             h16 val[4], oth[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                val[r] = (h16)s[r];
+                val[r] = (h16)s[r];                                      // (two roundings by the compiler's choice; guard: tests/test_gpu_rounding_probes.py)
                 oth[r] = (h16)__shfl_xor((float)val[r], 32, 64);         // rotary partner: lane g <-> g ^ 2 (exact)
             }
             if (m >= M) continue;
@@ -327,13 +327,13 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_fp8_kernel(const u32x4
             if (MODE == F8_F32) {                                        // logits.float(): fp16 result, then cast
                 float* dst = (float*)yv + (int64_t)m * ya.sm + panel * 16 + 4 * g;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) dst[r] = (float)(h16)s[r];
+                for (int r = 0; r < 4; ++r) dst[r] = (float)(h16)s[r];   // (two roundings by the compiler's choice; guard: tests/test_gpu_rounding_probes.py)
             } else {
                 half4 o;
                 if (GATEUP) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const h16 gt = (h16)s[r], up = (h16)s2[r];
+                        const h16 gt = (h16)s[r], up = (h16)s2[r];       // (two roundings by the compiler's choice; guard: tests/test_gpu_rounding_probes.py)
                         const float gf = (float)gt;
                         const h16 act = (h16)(gf / (1.0f + expf(-gf)));
                         o[r] = hmul_rn(act, up);
@@ -341,7 +341,7 @@ __global__ __launch_bounds__(WAVES * 64) void skinny_gemm_fp8_kernel(const u32x4
                 } else {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        o[r] = (h16)s[r];
+                        o[r] = f32_then_h16(s[r]);                           // two roundings: written (h16)s[r] it folds (common.h)
                         if (resid) o[r] = hadd_rn(resid[(int64_t)m * ra.sm + r_off + r], o[r]);   // residual + hidden
                         q[r] = (float)o[r];
                     }

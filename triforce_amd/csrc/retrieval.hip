@@ -14,7 +14,8 @@
 
 // ---- scoring ------------------------------------------------------------------------------
 // One 16-lane group per chunk (a wave scores 4 chunks per step); lane (c4, li) owns 8 d's.
-// Rounding points follow the reference: mean -> fp16, dot -> fp16.
+// Rounding points follow the reference: mean -> fp16, dot -> fp16.  The mean is fp16(fp32(sum * (1 / chunk))), two roundings
+// (mul_f32_then_h16, common.h), here and in chunk_mean_kernel alike: their bit-identity depends on it at chunks 12 and 24.
 template <int D>
 __global__ __launch_bounds__(256) void retrieval_score_kernel(const h16* __restrict__ k, int64_t stride_t,
                                                               int64_t stride_h, const h16* __restrict__ q,
@@ -43,7 +44,7 @@ __global__ __launch_bounds__(256) void retrieval_score_kernel(const h16* __restr
         float dot = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const h16 mean = (h16)(acc[e] * inv);    // chunk mean rounded to fp16 (cache.py:154)
+            const h16 mean = mul_f32_then_h16(acc[e], inv);   // chunk mean: fp32 product, then fp16 (cache.py:154)
             dot = fmaf(qf[e], (float)mean, dot);
         }
 #pragma unroll
@@ -80,7 +81,7 @@ __global__ __launch_bounds__(256) void chunk_mean_kernel(const h16* __restrict__
         }
         half8 mean;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) mean[e] = (h16)(acc[e] * inv);
+        for (int e = 0; e < 8; ++e) mean[e] = mul_f32_then_h16(acc[e], inv);
         store_half8(ib + (int64_t)c * D, mean);
     }
 }
