@@ -897,6 +897,35 @@ int tf_skinny_qkv_rope_gqa_bias_act(const void* wqkv_packed, const void* x, int6
                                     int64_t stride_h, int slot0, const int32_t* slot0_dev, int M, int H, int Hkv, int D,
                                     int K, int rotate_k, const void* bias, void* stream);
 
+/* -------------------------------------------------------------------------------------------
+ * SAMPLING PENALTIES: repetition, frequency and presence penalties on the target tier's fp32 logits.
+ * State (device, V entries each): gen_count int32 — occurrences among the generated tokens of the current answer, the pending
+ * token excluded; prompt_seen uint8 — 1 where the token occurs in the context the answer is conditioned on.
+ * tf_penalize_logits: for row i of a block whose input tokens are ids[0 .. rows) (ids may be NULL: no tokens), entry t with
+ * raw logit x = logits[i * ls_m + t]:
+ *     c    = gen_count[t] + #{ j <= i : ids[j] == t }                       (int32)
+ *     seen = prompt_seen[t] != 0 || c > 0
+ *     y = x
+ *     if seen && repetition != 1:  y = (x > 0) ? x / repetition : x * repetition
+ *     if c > 0:                    y = y - frequency * (float)c ;  y = y - presence
+ *     out[i * os_m + t] = y
+ *   Every / * - is ONE IEEE fp32 operation with its own rounding (no contraction); an entry with !seen is copied bit for bit;
+ *   -inf stays -inf; NaN and +inf are outside the contract.  An id outside [0, V) matches no entry.  One launch over V, a
+ *   thread owns four entries for all rows; 16-byte loads / stores when V, ls_m and os_m are multiples of 4 and logits, out,
+ *   gen_count are 16-byte (prompt_seen 4-byte) aligned, else a scalar path with the same results.  Only READS the state: no
+ *   atomics, no workspace, nothing shared between workgroups — capturable, replayable back to back.  out == logits (exactly)
+ *   is allowed; any other overlap is not.
+ *   TF_EINVAL before any launch: NULL logits / out / gen_count / prompt_seen, rows outside [1, 64], V < 1, ls_m < V or
+ *   os_m < V, repetition not finite or <= 0, frequency or presence not finite (negative values are legal).
+ * tf_penalty_commit: gen_count[ids[j]] += 1 for j < n (device ids; duplicates accumulate; an id outside [0, V) is skipped,
+ *   never written).  One small workgroup.  TF_EINVAL: NULL gen_count or ids (checked BEFORE n == 0), n outside [0, 64], V < 1;
+ *   n == 0 is a no-op returning 0.
+ * ------------------------------------------------------------------------------------------- */
+int tf_penalize_logits(const float* logits, int64_t ls_m, float* out, int64_t os_m, const int64_t* ids,
+                       const int32_t* gen_count, const uint8_t* prompt_seen, int rows, int V, float repetition,
+                       float frequency, float presence, void* stream);
+int tf_penalty_commit(int32_t* gen_count, const int64_t* ids, int n, int V, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

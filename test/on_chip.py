@@ -19,6 +19,12 @@ from triforce_amd.utils.misc import colored, print_config  # noqa: E402
 DEVICE = "cuda:0"
 
 
+def penalties(args):
+    """--repetition_penalty / --frequency_penalty / --presence_penalty as the keywords of the engine and of both loops."""
+    return dict(repetition_penalty=args.repetition_penalty, frequency_penalty=args.frequency_penalty,
+                presence_penalty=args.presence_penalty)
+
+
 def build_engine(args, target, draft):
     """Caches sized as on_chip.py:76-80 (16 sink tokens, recent = draft budget - 16 - gamma) and the captured graphs."""
     # (--followups: a question's rows sit between the document and its answer; 0 by default.  --reanchor_at: the answer may
@@ -34,7 +40,7 @@ def build_engine(args, target, draft):
                                           gamma=args.gamma)
     engine = GraphInferenceEngine(target, full, retrieval, draft, streaming)
     engine.initialize_cuda_graph(args.gamma, probs=True, temperature=args.temp, top_p=args.top_p, top_k=args.top_k,
-                                 min_p=args.min_p)
+                                 min_p=args.min_p, **penalties(args))
     for c in (full, retrieval, streaming):
         c.print_status()
     return engine
@@ -89,6 +95,7 @@ def main():
                  spec_args={"budget": args.budget, "chunk_size": args.chunk_size}, dataset=args.dataset, **sampling)
     engine = build_engine(args, target, draft)
     sampling["min_p"] = args.min_p                   # (target tier only, like top_k; print_config has the reference's columns)
+    sampling.update(penalties(args))                 # (target tier only as well: DESIGN section 31)
     print(colored(f"tokenized_prompts length: {len(prompts)}", "green"))
 
     def clip(p):

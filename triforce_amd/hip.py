@@ -191,6 +191,10 @@ for _name in ("tf_skinny_gemm", "tf_skinny_qkv_rope", "tf_skinny_qkv_rope_gqa"):
     _res, _args = SIGNATURES[_name + "_act"]
     SIGNATURES[_name + "_bias_act"] = (_res, _args[:-1] + [_vp, _vp])
 
+# repetition / frequency / presence penalties on the target tier (include/triforce_hip.h "SAMPLING PENALTIES")
+SIGNATURES["tf_penalize_logits"] = (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _f32, _f32, _f32, _vp])
+SIGNATURES["tf_penalty_commit"] = (_i32, [_vp, _vp, _i32, _i32, _vp])
+
 ABI_VERSION = 1
 _lib = None
 

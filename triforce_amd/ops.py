@@ -1764,6 +1764,63 @@ def minp_probs_large(logits, temperature, top_k, top_p, min_p):
     return _topp_large_call("tf_minp_probs_large", logits, float(temperature), int(top_k), float(top_p), float(min_p))
 
 
+PENALTY_MAX_ROWS = 64
+
+
+class PenaltyState:
+    """What the target tier's penalties remember, per engine: ``gen_count`` (V,) int32 — occurrences among
+    the generated tokens of the current answer, the pending token excluded — and ``prompt_seen`` (V,) uint8 — 1 where the token
+    occurs in the context the answer is conditioned on.  Allocated once; the kernels hold its addresses (captured graphs)."""
+
+    def __init__(self, V, device):
+        self.V = int(V)
+        self.gen_count = torch.zeros(self.V, dtype=torch.int32, device=device)
+        self.prompt_seen = torch.zeros(self.V, dtype=torch.uint8, device=device)
+
+    def reset(self, context_ids):
+        """A new answer: ``prompt_seen`` becomes the set of ``context_ids`` (any shape, ids outside [0, V) ignored), no token
+        generated yet.  Torch fill / scatter in place, once per prompt."""
+        ids = torch.as_tensor(context_ids, dtype=torch.long, device=self.gen_count.device).reshape(-1)
+        ids = ids[(ids >= 0) & (ids < self.V)]
+        self.prompt_seen.zero_()
+        self.prompt_seen.index_fill_(0, ids, 1)
+        self.gen_count.zero_()
+
+
+def penalize_logits(logits, ids, state, penalties, out=None):
+    """(rows, V) fp32 device logits -> the penalised rows of include/triforce_hip.h "SAMPLING PENALTIES" (tf_penalize_logits, one
+    launch, 1 <= rows <= 64): row i counts ``state.gen_count`` plus ids[0 .. i].  ``ids``: None, or an int64 device tensor whose
+    first ``rows`` entries are the block's input tokens.  ``penalties``: .repetition / .frequency / .presence.  ``out``: fp32
+    (rows, V) device tensor, unit stride on V (``logits`` itself is allowed); allocated when None.  The state is only read."""
+    _dev(logits, ids, state.gen_count, state.prompt_seen, out)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.numel() > 0
+    rows, V = logits.shape
+    assert V == state.V and rows <= PENALTY_MAX_ROWS
+    if out is None:
+        out = torch.empty((rows, V), dtype=torch.float32, device=logits.device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (rows, V) and out.stride(1) == 1
+    if ids is not None:
+        ids = ids.reshape(-1)
+        assert ids.dtype == torch.int64 and ids.numel() >= rows and ids.is_contiguous()
+    ls = logits.stride(0) if rows > 1 else max(logits.stride(0), V)
+    os_ = out.stride(0) if rows > 1 else max(out.stride(0), V)
+    hip.check(hip.lib().tf_penalize_logits(_ptr(logits), ls, _ptr(out), os_, _ptr(ids), _ptr(state.gen_count),
+                                           _ptr(state.prompt_seen), rows, V, float(penalties.repetition),
+                                           float(penalties.frequency), float(penalties.presence), _stream()),
+              "tf_penalize_logits")
+    return out
+
+
+def penalty_commit(state, ids_row, n):
+    """state.gen_count[ids_row[j]] += 1 for j < n (tf_penalty_commit: one small launch, 0 <= n <= 64; duplicates accumulate, ids
+    outside [0, V) are skipped).  ``ids_row``: int64 device tensor with at least n entries."""
+    _dev(state.gen_count, ids_row)
+    ids_row = ids_row.reshape(-1)
+    assert ids_row.dtype == torch.int64 and ids_row.is_contiguous() and 0 <= n <= min(ids_row.numel(), PENALTY_MAX_ROWS)
+    hip.check(hip.lib().tf_penalty_commit(_ptr(state.gen_count), _ptr(ids_row), int(n), state.V, _stream()),
+              "tf_penalty_commit")
+
+
 # Rows of normalised hidden state that DecoderLayers.head scores per lm_head GEMM when it is asked for the prompt's
 # log-probabilities: the fp32 logits block is SCORE_BLOCK_ROWS x V (131 MB at 32 000) instead of chunk x V (DESIGN section 23).
 SCORE_BLOCK_ROWS = 1024

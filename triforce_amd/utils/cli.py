@@ -69,6 +69,13 @@ SCRIPT_OWN = {
         ("--min_p", float, 0.0, "min-p of the TARGET's sampling, applied behind top-k / top-p: a token stays only if its "
                                 "probability is at least min_p times the most likely token's (0 < min_p <= 1); the two draft "
                                 "tiers never filter by it; 0 = off"),
+        ("--repetition_penalty", float, 1.0, "repetition penalty of the TARGET's sampling (HF's rule): the logit of a token "
+                                             "of the prompt or of the answer so far is divided by it when positive and "
+                                             "multiplied when not; > 0, 1 = off; the two draft tiers are never penalised"),
+        ("--frequency_penalty", float, 0.0, "frequency penalty of the TARGET's sampling (OpenAI's rule): subtracted from a "
+                                            "token's logit once per occurrence in the answer so far; 0 = off"),
+        ("--presence_penalty", float, 0.0, "presence penalty of the TARGET's sampling (OpenAI's rule): subtracted once from "
+                                           "the logit of every token of the answer so far; 0 = off"),
         ("--reanchor_at", int, 0, "re-anchor the retrieval cache (fold the generated rows into the covered region and "
                                   "re-select) before its generated tail exceeds N rows, gamma + 2 <= N <= --budget: "
                                   "generation and follow-ups may then pass the budget; 0 = never"),

@@ -16,8 +16,9 @@ import numpy as np
 import torch
 
 from .. import ops
+from . import sampling as _sampling
 from .misc import log_csv, spec_stream
-from .sampling import Filters, UniformSource, norm_logits, sample
+from .sampling import Filters, Penalties, UniformSource, norm_logits, sample
 
 PAD_TOKEN = 100            # filler id of verify_tokens / pass_tokens (decoding.py:94,177)
 
@@ -34,11 +35,16 @@ def _eos(tokenizer):
 
 @torch.inference_mode()
 def Autoregressive(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, top_p=0.9, temperature=0.6, verbose=False,
-                   rng=None, return_tokens=False, logprobs=False, min_p=0.0):
+                   rng=None, return_tokens=False, logprobs=False, min_p=0.0, repetition_penalty=1.0, frequency_penalty=0.0,
+                   presence_penalty=0.0):
     """``min_p`` > 0: min-p behind top-k / top-p.  ``logprobs``: also the log-probability (temperature 1, unfiltered: DESIGN section 23) of every emitted token, scored
-    on the device from the step's own logits -> (tokens / s, ids, logprobs)."""
+    on the device from the step's own logits -> (tokens / s, ids, logprobs).  The three penalties: every
+    step's row is penalised with the engine's state and its own input token, which is then committed — on the device, no
+    host sync in the loop; the log-probabilities stay those of the raw logits."""
     eng = graph_engine.engine
     device = eng.model.device
+    pen = Penalties(repetition_penalty, frequency_penalty, presence_penalty)
+    state = _penalty_state(graph_engine, pen)
     lp = None
     if logprobs:
         refusal = _logprobs_refusal(graph_engine, "logprobs")
@@ -49,7 +55,11 @@ def Autoregressive(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, to
     kw = Filters(temperature, top_p, top_k, min_p).kw()
     eng.kv_cache.reset()
     logits = graph_engine.inference(input_ids=input_ids)
-    next_token = sample(norm_logits(logits[:, -1, :], **kw), rng=rng)
+    row = logits[:, -1, :]
+    if pen.on:
+        state.reset(input_ids)
+        row = _sampling.penalize(row, None, state, pen)
+    next_token = sample(norm_logits(row, **kw), rng=rng)
     if lp is not None:
         ops.token_logprobs(logits[:, -1, :], next_token.view(-1), out=lp[0:1])
     toks = [next_token]
@@ -60,7 +70,12 @@ def Autoregressive(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, to
         (lambda t: eng.model(input_ids=t, kv_cache=eng.kv_cache, graph_cache=None).logits)
     while n < max_len:      # no host sync inside the loop: the sampled token never leaves the device
         logits = step(next_token)
-        next_token = sample(norm_logits(logits[:, -1, :], **kw), rng=rng)
+        if pen.on:                          # the row counts its own input token, which then joins the counts
+            row = _sampling.penalize(logits[:, -1, :], next_token.view(-1), state, pen)
+            _sampling.commit_penalties(state, next_token.view(-1), 1)
+            next_token = sample(norm_logits(row, **kw), rng=rng)
+        else:
+            next_token = sample(norm_logits(logits[:, -1, :], **kw), rng=rng)
         toks.append(next_token)
         n += 1
         if lp is not None:                  # device targets, the step's own logits (a graph's static buffer until its next replay)
@@ -77,6 +92,21 @@ def Autoregressive(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, to
         if return_tokens:
             return n / (time2 - time1), ids
     return n / (time2 - time1)
+
+
+def _penalty_state(graph_engine, penalties):
+    """The engine's ops.PenaltyState for ``penalties`` (None when they are off: nothing is touched).  Refused before anything
+    is captured or allocated over an engine that has none — the tensor-parallel and Sequoia engines, or a
+    GraphInferenceEngine initialised without penalties."""
+    if not penalties.on:
+        return None
+    state = getattr(graph_engine, "penalty_state", None)
+    if state is None:
+        raise NotImplementedError(
+            f"repetition / frequency / presence penalties need the single-GPU GraphInferenceEngine initialised with them "
+            f"(initialize_cuda_graph / initialize_eager(repetition_penalty=..., frequency_penalty=..., presence_penalty=...)); "
+            f"{type(graph_engine).__name__} holds no penalty state")
+    return state
 
 
 def _logprobs_refusal(graph_engine, what):
@@ -475,11 +505,16 @@ class TriForceRunner:
 
     def __init__(self, tokenizer, graph_engine, gamma, top_k=-1, top_p=0.9, temperature=0.6, verbose=False, rng=None,
                  inclusive_accept=False, sync_record=None, rebuild_every=0, reanchor_at=0, logprobs=False,
-                 prompt_logprobs=False, min_p=0.0):
+                 prompt_logprobs=False, min_p=0.0, repetition_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0):
         # filters: what the TARGET's distribution (first token, target verify) is normalised with.  top_k > 0 and min_p > 0 (a
         #              token stays only if its probability is at least min_p times the most likely token's, behind top-k / top-p:
         #              DESIGN section 27) apply to it alone; the draft tiers stay unfiltered
         self.filters = Filters(temperature, top_p, top_k, min_p)
+        # penalties: repetition / frequency / presence on the TARGET's logits, in front of the normaliser;
+        #              the draft tiers stay unpenalised, so decoding is lossless for the penalised target distribution.  The
+        #              state lives with the engine (refused here, before anything is captured, over an engine without one)
+        self.penalties = Penalties(repetition_penalty, frequency_penalty, presence_penalty)
+        self.penalty_state = _penalty_state(graph_engine, self.penalties)
         # logprobs: keep the log-probability (temperature 1, unfiltered: DESIGN section 23) of every emitted token, scored on the
         #              device from the logits of the verify that produced it — one launch per step, no host read before stats()
         # prompt_logprobs: prefill() also scores the prompt, log p(input_ids[i + 1] | input_ids[:i + 1]) for i = 0 .. n - 2
@@ -567,6 +602,8 @@ class TriForceRunner:
             eng.graph_cache.print_status()
             eng.draft_cache.print_status()
         self.calibrate_aligned()
+        if self.penalties.on:
+            self.penalty_state.reset(input_ids)            # the context is the prompt; nothing generated yet
         self.start(logits)
         self.history, self._fed = input_ids, []
 
@@ -680,6 +717,8 @@ class TriForceRunner:
         self.n = self.inner_iters = self.rebuilds = 0
         self.reanchors = moved
         self.counts, self.acc_rate_middle_list, self.last_reason = [], [], None
+        if self.penalties.on:
+            self.penalty_state.reset(hist)                 # a fresh request whose prompt is the conversation so far
         self.start(logits)                                 # (take + advance: the uniform stream's device cursor is re-written
         if self.time_extend:                               #  before its next reader)
             self.extend_seconds = dict(target_feed=t[1] - t[0], retrieval_rebuild=t[2] - t[1], draft_refill=t[3] - t[2],
@@ -702,7 +741,10 @@ class TriForceRunner:
 
     @torch.inference_mode()
     def start(self, logits):
-        probs = norm_logits(logits[:, -1, :], **self.filters.kw())
+        row = logits[:, -1, :]
+        if self.penalties.on:                          # the first token: no block ids, the state as prefill() / extend() left it
+            row = _sampling.penalize(row, None, self.penalty_state, self.penalties)
+        probs = norm_logits(row, **self.filters.kw())
         self.next_token = int(sample(probs, rng=self.rng))
         if self.verbose:
             spec_stream(self.next_token, self.tokenizer, "cyan")
@@ -736,11 +778,18 @@ class TriForceRunner:
         return self.ge.verify_sets(self.gamma)
 
     def _served(self):
-        """The engine's captured target verify was normalised with exactly THIS runner's filters (``serves``: DESIGN section 28),
-        so its probabilities may be used: what every fast verify route asks.  An engine without ``serves`` captured
-        without top-k and min-p."""
+        """The engine's captured target verify was normalised with exactly THIS runner's filters (``serves``: DESIGN section 28)
+        behind exactly its penalties, so its probabilities may be used: what every fast verify route asks.
+        An engine without ``serves`` captured without top-k, min-p and penalties."""
         serves = getattr(self.ge, "serves", None)
-        return serves(self.filters) if serves is not None else not self.filters.target_only
+        if serves is None:
+            return not self.filters.target_only and not self.penalties.on
+        return serves(self.filters, self.penalties) if self.penalties.on else serves(self.filters)
+
+    def _pen_kw(self):
+        """``penalties`` for the engines' verify entry points, only when they are on: without it the call is the one made
+        before penalties existed."""
+        return dict(penalties=self.penalties) if self.penalties.on else {}
 
     @torch.inference_mode()
     def step(self):
@@ -786,17 +835,21 @@ class TriForceRunner:
             tg = ge.target_graphs[len(ids)]
             probs, verify_tokens = tg.replay_in_place(), tg.ids
         elif served and not rebuild and not eager and hasattr(ge, "verify_probs_ids") and len(ids) <= 32 \
-                and (fast := ge.verify_probs_ids(ids, **self.filters.kw())) is not None:
+                and (fast := ge.verify_probs_ids(ids, **self.filters.kw(), **self._pen_kw())) is not None:
             # captured forward + temperature / top-p: ids, positions and lengths set by ONE launch (ids as kernel arguments)
             probs, verify_tokens = fast
         else:
             verify_tokens = bufs.to_device(ids)
             if served and hasattr(ge, "verify_probs"):                 # one hipGraph: forward + temperature / top-k / top-p
-                probs = ge.verify_probs(verify_tokens, rebuild_retrieval=rebuild, eager=eager, **self.filters.kw())
+                probs = ge.verify_probs(verify_tokens, rebuild_retrieval=rebuild, eager=eager, **self.filters.kw(),
+                                        **self._pen_kw())
             else:
                 logits = ge.inference(input_ids=verify_tokens, rebuild_retrieval=True) if rebuild \
                     else (ge.inference(input_ids=verify_tokens, eager=True) if eager else ge.inference(input_ids=verify_tokens))
-                probs = norm_logits(logits[0], **self.filters.kw())
+                rows = logits[0]
+                if self.penalties.on:                                  # out of place: ``logits`` stays raw (logprobs below)
+                    rows = _sampling.penalize(rows, verify_tokens.view(-1), self.penalty_state, self.penalties)
+                probs = norm_logits(rows, **self.filters.kw())
         if getattr(bufs, "rows_generation", None) is not None:
             # spec_rows is a view of the retrieval-verify graph's static output: nothing may have replayed that graph
             # between Middle_Spec's return and this read (the target verify above is a different graph)
@@ -820,6 +873,11 @@ class TriForceRunner:
         if self.sync_record is not None:
             self.sync_record(rec.tensor)
         count, pred, reason, consumed = rec.read(4)                      # the one host read of the outer step
+        if self.penalties.on:
+            # the pass tokens [next_token] + generated[:count] join the counts: they are the head of the verify block's own
+            # device row in every route (the accept kernel writes behind them).  One launch, outside every graph; the
+            # resampled / bonus token stays pending and is counted by the next block's row 0
+            _sampling.commit_penalties(self.penalty_state, verify_tokens.view(-1), count + 1)
         if self.health is not None:
             self.health()
         dp = getattr(getattr(eng, "draft", None), "_persist", None)                        # one-launch draft forward: pinned mirror of its error word
@@ -937,13 +995,16 @@ class TriForceRunner:
 @torch.inference_mode()
 def TriForce(tokenizer, graph_engine, input_ids, gamma=4, max_len=256, top_k=-1, top_p=0.9, temperature=0.6, verbose=False,
              file_path=None, dataset=None, spec_args=None, rng=None, return_details=False, rebuild_every=0, reanchor_at=0,
-             logprobs=False, prompt_logprobs=False, min_p=0.0):
+             logprobs=False, prompt_logprobs=False, min_p=0.0, repetition_penalty=1.0, frequency_penalty=0.0,
+             presence_penalty=0.0):
     """``min_p`` > 0: min-p on the target tier.
+    ``repetition_penalty`` / ``frequency_penalty`` / ``presence_penalty``: penalties on the target tier.
     ``logprobs`` / ``prompt_logprobs``: ``return_details`` then carries ``logprobs`` — a list aligned
     with ``tokens`` — and ``prompt_logprobs`` — an fp32 host tensor of n - 1 values."""
     run = TriForceRunner(tokenizer, graph_engine, gamma, top_k, top_p, temperature, verbose, rng,
                          rebuild_every=rebuild_every, reanchor_at=reanchor_at, logprobs=logprobs,
-                         prompt_logprobs=prompt_logprobs, min_p=min_p)
+                         prompt_logprobs=prompt_logprobs, min_p=min_p, repetition_penalty=repetition_penalty,
+                         frequency_penalty=frequency_penalty, presence_penalty=presence_penalty)
     run.prefill(input_ids)
     eng, device = run.eng, run.device
     _sync(device)
@@ -978,10 +1039,12 @@ class TriForceSession:
     Every answer returns the runner's stats plus ``ttft`` — the seconds from the call to the first token of the answer."""
 
     def __init__(self, tokenizer, graph_engine, gamma=4, top_k=-1, top_p=0.9, temperature=0.6, verbose=False, rng=None,
-                 rebuild_every=0, reanchor_at=0, logprobs=False, prompt_logprobs=False, min_p=0.0):
+                 rebuild_every=0, reanchor_at=0, logprobs=False, prompt_logprobs=False, min_p=0.0, repetition_penalty=1.0,
+                 frequency_penalty=0.0, presence_penalty=0.0):
         self.run = TriForceRunner(tokenizer, graph_engine, gamma, top_k, top_p, temperature, verbose, rng,
                                   rebuild_every=rebuild_every, reanchor_at=reanchor_at, logprobs=logprobs,
-                                  prompt_logprobs=prompt_logprobs, min_p=min_p)
+                                  prompt_logprobs=prompt_logprobs, min_p=min_p, repetition_penalty=repetition_penalty,
+                                  frequency_penalty=frequency_penalty, presence_penalty=presence_penalty)
         self.ttft = None
 
     @property

@@ -13,7 +13,8 @@ from typing import Optional
 import torch
 
 from .. import ops
-from .sampling import Filters, norm_logits
+from . import sampling as _sampling
+from .sampling import Filters, Penalties, norm_logits
 
 
 # Target prefill: the reference feeds 128 tokens per forward (graph_infer.py:30-37, TP_llama.py:246-250), which at
@@ -421,9 +422,11 @@ class _TargetGraph:
     (tf_skinny_qkv_rope slot0_dev, tf_attn_decode sk_dev) and the launch is sized by the cache capacity, so one
     capture serves every cache length.  With ``probs`` the temperature / top-k / top-p normalisation is part of the graph
     (``top_k`` > 0: tf_topk_topp_probs — the target tier is the only one the reference filters by top-k; ``min_p`` > 0:
-    tf_minp_probs, one workgroup per row)."""
+    tf_minp_probs, one workgroup per row).  ``penalties`` on: the rows are penalised
+    with the block's own ids and the engine's ``state`` in front of the normaliser, out of place — ``logits`` stays raw; the
+    kernel only reads the state, whose values are live at every replay."""
 
-    def __init__(self, engine, q_len, mempool, n_warmups, probs, filters, ids=None):
+    def __init__(self, engine, q_len, mempool, n_warmups, probs, filters, ids=None, penalties=None, state=None):
         dev = engine.model.device
         self.engine, self.q_len, self.probs = engine, q_len, probs
         self.cache = engine.kv_cache               # the graph reads and appends THIS cache's storage
@@ -435,10 +438,16 @@ class _TargetGraph:
         self.pos = torch.arange(q_len, dtype=torch.long, device=dev)
         self.slot = torch.zeros(1, dtype=torch.int32, device=dev)
         self.sk = torch.full((1,), q_len, dtype=torch.int32, device=dev)
+        penalised = probs and penalties is not None and penalties.on
+        # the penalised rows have a buffer of their own: what the normaliser reads when penalties are on
+        self.pen_rows = torch.empty((q_len, engine.model.config.vocab_size), dtype=torch.float32, device=dev) if penalised else None
 
         def run():
             logits = engine.model(input_ids=self.ids, kv_cache=engine.kv_cache, graph_cache=None,
                                   position_ids=self.pos.unsqueeze(0), dev_len=(self.slot, self.sk)).logits
+            if penalised:
+                return logits, norm_logits(_sampling.penalize(logits[0], self.ids[0], state, penalties, out=self.pen_rows),
+                                           **filters.kw())
             if probs:
                 return logits, norm_logits(logits[0], **filters.kw())
             return logits, None
@@ -505,6 +514,10 @@ class GraphInferenceEngine:
         # (reference decoding.py:62,90: the two draft tiers always run with -1) and min-p that are never keys
         # of ``sampling`` — that dict is splatted into the draft / retrieval-verify capture functions
         self.target_filters = Filters(0.6, 0.9)
+        # the penalties of the TARGET's distribution and their state (ops.PenaltyState: counts of the answer's
+        # tokens, the context's token set) — allocated only when an initialize_* call turns penalties on
+        self.target_penalties = Penalties()
+        self.penalty_state = None
         # (1, rows, V) fp32 logits of the last target verify that went through verify_probs / verify_probs_ids — a captured
         # graph's static buffer or the eager forward's result; valid until the next target forward (what a runner with
         # ``logprobs`` scores; the replay_in_place route leaves them in its _TargetGraph.logits)
@@ -512,9 +525,11 @@ class GraphInferenceEngine:
 
     @torch.inference_mode()
     def initialize_cuda_graph(self, gamma=6, probs=False, temperature=0.6, top_p=0.9, verbose=True,
-                              capture_target=True, top_k=-1, min_p=0.0):
+                              capture_target=True, top_k=-1, min_p=0.0, repetition_penalty=1.0, frequency_penalty=0.0,
+                              presence_penalty=0.0):
         """gamma + 3 draft graphs (one per gamma_offset) and one retrieval-verify graph, sharing one memory pool.
-        ``top_k`` and ``min_p`` go to the captured target verifies only."""
+        ``top_k``, ``min_p`` and the three penalties go to the captured target verifies only."""
+        self._set_penalties(repetition_penalty, frequency_penalty, presence_penalty)
         gc.collect()
         self.mempool = torch.cuda.graphs.graph_pool_handle()
         self.sampling = dict(probs=probs, temperature=temperature, top_p=top_p)
@@ -538,18 +553,30 @@ class GraphInferenceEngine:
             for q_len in sorted({1, gamma + 1, gamma + 2}):
                 # the two verify lengths read their tokens from the head of the shared token buffer (see _TargetGraph)
                 self.target_graphs[q_len] = _TargetGraph(self.engine, q_len, self.mempool, 3, probs and q_len > 1,
-                                                         self.target_filters, ids=self.tok_buf[:, :q_len] if q_len > 1 else None)
+                                                         self.target_filters, ids=self.tok_buf[:, :q_len] if q_len > 1 else None,
+                                                         penalties=self.target_penalties, state=self.penalty_state)
         self.dev_len = None                        # cache length the verify graphs' device scalars encode (None: unknown)
         self.engine.clear_kv()
 
-    def initialize_eager(self, gamma=6, probs=True, temperature=0.6, top_p=0.9, top_k=-1, min_p=0.0):
+    def initialize_eager(self, gamma=6, probs=True, temperature=0.6, top_p=0.9, top_k=-1, min_p=0.0, repetition_penalty=1.0,
+                         frequency_penalty=0.0, presence_penalty=0.0):
         """Same surface without graph capture (debugging / parity bisecting)."""
+        self._set_penalties(repetition_penalty, frequency_penalty, presence_penalty)
         self.sampling = dict(probs=probs, temperature=temperature, top_p=top_p)
         self.target_filters = Filters(temperature, top_p, top_k, min_p)
         eng, kw = self.engine, self.sampling
         self.callables = {off: (lambda ids, off=off: eng.draft_run(input_ids=ids, gamma_offset=off, **kw))
                           for off in range(gamma + 3)}
         self.callable_model_verify = lambda ids, pos: eng.model_verify(input_ids=ids, position_ids=pos, **kw)
+
+    def _set_penalties(self, repetition, frequency, presence):
+        """``target_penalties`` of an initialize_* call; the state exists only while they are on (its buffers keep their
+        addresses across re-initialisations with penalties: a vocabulary has one size)."""
+        self.target_penalties = Penalties(repetition, frequency, presence)
+        if not self.target_penalties.on:
+            self.penalty_state = None
+        elif self.penalty_state is None:
+            self.penalty_state = ops.PenaltyState(self.engine.model.config.vocab_size, self.engine.model.device)
 
     def clear_kv(self):
         self.engine.clear_kv()
@@ -575,30 +602,43 @@ class GraphInferenceEngine:
         tg = self.target_graphs.get(input_ids.shape[-1])
         return tg if (tg is not None and tg.cache is self.engine.kv_cache) else None   # cache swapped after capture: eager
 
-    def serves(self, filters):
-        """The captured target verifies were normalised with exactly these Filters: their probabilities may be used."""
-        return filters == self.target_filters
+    def serves(self, filters, penalties=None):
+        """The captured target verifies were normalised with exactly these Filters behind exactly these Penalties (None: off):
+        their probabilities may be used."""
+        return filters == self.target_filters and (penalties or Penalties()) == self.target_penalties
 
     @torch.inference_mode()
-    def verify_probs(self, input_ids, temperature, top_p, rebuild_retrieval=False, eager=False, top_k=-1, min_p=0.0):
+    def verify_probs(self, input_ids, temperature, top_p, rebuild_retrieval=False, eager=False, top_k=-1, min_p=0.0,
+                     penalties=None):
         """Target verify -> (rows, V) probabilities after temperature / top-k / top-p / min-p: one graph replay when captured with
-        these settings, else the eager forward + norm_logits.  The result is valid until the next target forward."""
+        these settings, else the eager forward + norm_logits.  The result is valid until the next target forward.
+        ``penalties`` on: the rows are penalised with the block's ids and the engine's state first, in
+        the graph or eagerly; ``last_logits`` stays raw either way."""
         filters = Filters(temperature, top_p, top_k, min_p)
         tg = None if (eager or rebuild_retrieval) else self._target_graph(input_ids)
-        if tg is not None and tg.probs and self.serves(filters):
+        if tg is not None and tg.probs and self.serves(filters, penalties):
             self.last_logits, probs = tg(input_ids)
             return probs
         logits = self.last_logits = self.inference(input_ids, rebuild_retrieval=rebuild_retrieval, eager=eager)
-        return norm_logits(logits[0], **filters.kw())
+        rows = logits[0]
+        if penalties is not None and penalties.on:
+            rows = _sampling.penalize(rows, input_ids.reshape(-1), self._penalty_state(), penalties)
+        return norm_logits(rows, **filters.kw())
+
+    def _penalty_state(self):
+        if self.penalty_state is None:
+            raise NotImplementedError("penalties need an engine initialised with them: pass repetition_penalty / "
+                                      "frequency_penalty / presence_penalty to initialize_cuda_graph / initialize_eager")
+        return self.penalty_state
 
     @torch.inference_mode()
-    def verify_probs_ids(self, ids, temperature, top_p, top_k=-1, min_p=0.0):
+    def verify_probs_ids(self, ids, temperature, top_p, top_k=-1, min_p=0.0, penalties=None):
         """``verify_probs`` for a python list of token ids when the captured target graph of that length exists with these
         sampling settings: (probabilities, the graph's (1, q_len) device token row), else None (caller: tensor path).
         One launch sets ids, positions and lengths (tf_set_tokens) in front of the replay."""
         tg = self.target_graphs.get(len(ids))
         if tg is None or tg.cache is not self.engine.kv_cache or not tg.probs or not tg.ids.is_cuda \
-                or not self.serves(Filters(temperature, top_p, top_k, min_p)):
+                or not self.serves(Filters(temperature, top_p, top_k, min_p), penalties):
             return None
         self.last_logits, probs = tg(list(ids))
         return probs, tg.ids

@@ -8,6 +8,7 @@ implementation-defined; here the sort is *stable* (lowest token id first among e
 emulation (temperature=1, top_p->0) is deterministic on every device.
 """
 import dataclasses
+import math
 
 import torch
 from torch.nn import functional as F
@@ -59,6 +60,76 @@ class Filters:
         if self.min_p > 0:
             kw["min_p"] = self.min_p
         return kw
+
+
+@dataclasses.dataclass(frozen=True)
+class Penalties:
+    """The stateful settings of the TARGET's distribution as one comparable value: ``repetition`` (HF's
+    rule over prompt and output, 1 = off), ``frequency`` and ``presence`` (OpenAI's, over the output only, 0 = off; negative
+    values are legal).  Kept apart from Filters: they act on the logits before the normaliser and need the engine's state."""
+    repetition: float = 1.0
+    frequency: float = 0.0
+    presence: float = 0.0
+
+    def __post_init__(self):
+        for name in ("repetition", "frequency", "presence"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                raise ValueError(f"{name}_penalty={v!r} is not a finite number")
+            object.__setattr__(self, name, float(v))
+        if not self.repetition > 0.0:
+            raise ValueError(f"repetition_penalty={self.repetition} must be > 0 (1 = off)")
+
+    @property
+    def on(self):
+        return self.repetition != 1.0 or self.frequency != 0.0 or self.presence != 0.0
+
+
+def _penalize_torch(logits, ids, state, penalties):
+    """The formula of include/triforce_hip.h "SAMPLING PENALTIES" in torch: fp32, one operation per statement."""
+    rows, V = logits.shape
+    dev = logits.device
+    x = logits.float()
+    c = state.gen_count.to(device=dev, dtype=torch.int32).unsqueeze(0).repeat(rows, 1)
+    if ids is not None:
+        block = ids.reshape(-1)[:rows].to(dev)
+        hit = torch.zeros(rows, V, dtype=torch.int32, device=dev)
+        ok = (block >= 0) & (block < V)
+        hit[torch.arange(rows, device=dev)[ok], block[ok]] = 1
+        c = c + torch.cumsum(hit, dim=0, dtype=torch.int32)            # row i counts ids[0 .. i]
+    seen = (state.prompt_seen.to(dev) != 0).unsqueeze(0) | (c > 0)
+    r = torch.tensor(penalties.repetition, dtype=torch.float32, device=dev)
+    f = torch.tensor(penalties.frequency, dtype=torch.float32, device=dev)
+    p = torch.tensor(penalties.presence, dtype=torch.float32, device=dev)
+    y = x
+    if float(r) != 1.0:
+        divided = x / r
+        multiplied = x * r
+        y = torch.where(seen, torch.where(x > 0, divided, multiplied), x)
+    fc = f * c.to(torch.float32)
+    less = y - fc
+    less = less - p
+    return torch.where(c > 0, less, y)
+
+
+def penalize(logits, ids, state, penalties, out=None):
+    """(rows, V) logits of the target -> the penalised rows: row i counts ``state.gen_count`` plus the
+    block's input tokens ids[0 .. i] (``ids`` None: none).  Out of place, the state is only read.  fp32 device logits go to
+    the kernel (ops.penalize_logits), anything else takes the torch restatement."""
+    assert logits.dim() == 2
+    if logits.is_cuda and logits.dtype == torch.float32:
+        return ops.penalize_logits(logits, ids, state, penalties, out=out)
+    return _penalize_torch(logits, ids, state, penalties)
+
+
+def commit_penalties(state, ids_row, n):
+    """state.gen_count[ids_row[j]] += 1 for j < n: the tokens a step left in the full cache.  One launch on the device
+    (ops.penalty_commit), torch elsewhere; nothing is read back."""
+    if state.gen_count.is_cuda:
+        return ops.penalty_commit(state, ids_row, n)
+    row = ids_row.reshape(-1)[:n]
+    row = row[(row >= 0) & (row < state.V)]
+    state.gen_count.index_add_(0, row, torch.ones_like(row, dtype=torch.int32))
 
 
 # route of ops.topp_route -> the ops wrappers without top-k and min-p, with top-k, with min-p (DESIGN section 28)
