@@ -926,6 +926,32 @@ int tf_penalize_logits(const float* logits, int64_t ls_m, float* out, int64_t os
                        float frequency, float presence, void* stream);
 int tf_penalty_commit(int32_t* gen_count, const int64_t* ids, int n, int V, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * N-GRAM DRAFT: prompt lookup — a draft tier without weights, at any vocabulary.
+ * State (device): hist int32 [cap] — the confirmed tokens; len_dev int32 scalar L, read as clamp(L, 0, cap).
+ * tf_ngram_draft: blk int64, first m entries used — the speculative block in front of the proposal.
+ *     ctx = hist[0:L] ++ blk[0:m],  T = L + m
+ *     for 0 <= j <= T - 2:  l(j) = the largest n <= min(N, j + 1) with ctx[j - k] == ctx[T - 1 - k] for all 0 <= k < n, else 0
+ *     an id outside [0, V) equals nothing, itself included (an entry of blk outside int32 is such an id)
+ *     j* maximises (l(j), j) lexicographically: the longest match first, the most recent among equals
+ *     d = ctx[j* + 1] when l(j*) >= 1;  else (no match, or T == 1) d = ctx[T - 1];  d outside [0, V): d = 0
+ *     q[v] = (v == d) ? 1.0f : 0.0f for every v < V, whatever q held;  info[0..4) = (d, l(j*), l(j*) >= 1 ? j* : -1, T)
+ *   ONE launch of a fixed grid (thread t owns the candidates j of the groups of four 4 g .. 4 g + 3, g = t, t + threads, ...,
+ *   read with 16-byte loads; the <= 31 candidates inside blk belong to workgroup 0).  tf_ngram_draft_shape writes the HOST
+ *   array out[2] = (threads of the grid, bytes of ws); TF_EINVAL for NULL.
+ *   ws: that many bytes, 8-byte aligned, zero when first used; every launch leaves it zero — no zeroing between
+ *   launches, capturable, replayable back to back, no host read.  Launches that share a ws must be ordered (one stream).
+ *   TF_EINVAL before any launch: a NULL pointer, cap < 1, m outside [1, 32], N outside [1, 8], V < 1, cap + m > INT32_MAX,
+ *   hist not 16-byte, q not 4-byte or ws not 8-byte aligned.
+ * tf_ngram_commit: hist[L + i] = (int32)src[i] for i < n, then L += n (device ids; one wave, outside every graph).  L < 0 or
+ *   L + n > cap: nothing is written (the host checks the capacity first).  TF_EINVAL: NULL hist / len_dev / src (checked
+ *   BEFORE n == 0), cap < 1, n outside [0, 64]; n == 0 is a no-op returning 0.
+ * ------------------------------------------------------------------------------------------- */
+int tf_ngram_draft_shape(int32_t* out);
+int tf_ngram_draft(const int32_t* hist, int cap, const int32_t* len_dev, const int64_t* blk, int m, int N, int V, float* q,
+                   int32_t* info, void* ws, void* stream);
+int tf_ngram_commit(int32_t* hist, int cap, int32_t* len_dev, const int64_t* src, int n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@ from triforce_amd.models.cache import FlashSimpleCache, RetrievalCache, Streamin
 from triforce_amd.models import zoo  # noqa: E402
 from triforce_amd.models.modeling_llama import LlamaForCausalLM  # noqa: E402
 from triforce_amd.models.modeling_llama_68m import LlamaForCausalLM as LlamaForCausalLM_68M  # noqa: E402
+from triforce_amd.models.ngram_draft import NgramCache, NgramDraft  # noqa: E402
 from triforce_amd.utils import cli  # noqa: E402
 from triforce_amd.utils.decoding import Autoregressive, TriForce, TriForceSession  # noqa: E402
 from triforce_amd.utils.graph_infer import GraphInferenceEngine  # noqa: E402
@@ -36,14 +37,27 @@ def build_engine(args, target, draft):
         print(colored(f"retrieval budget {args.budget} > prefill {args.prefill}: using {budget}", "yellow"))
     retrieval = RetrievalCache(target, max_budget=budget, prefill=args.prefill, gamma=args.gamma,
                                chunk_size=args.chunk_size)
-    streaming = StreamingLLMEvictionCache(draft, start_size=16, recent_size=args.draft_cache_budget - 16 - args.gamma,
-                                          gamma=args.gamma)
+    if isinstance(draft, NgramDraft):              # --draft ngram: the token history of the full cache's rows, no K/V
+        streaming = NgramCache(full.max_budget, draft.device, gamma=args.gamma)
+    else:
+        streaming = StreamingLLMEvictionCache(draft, start_size=16, recent_size=args.draft_cache_budget - 16 - args.gamma,
+                                              gamma=args.gamma)
     engine = GraphInferenceEngine(target, full, retrieval, draft, streaming)
     engine.initialize_cuda_graph(args.gamma, probs=True, temperature=args.temp, top_p=args.top_p, top_k=args.top_k,
                                  min_p=args.min_p, **penalties(args))
     for c in (full, retrieval, streaming):
         c.print_status()
     return engine
+
+
+def load_draft(args, target):
+    """--draft llama-68M (default): the 68M-shaped draft of the target's vocabulary.  --draft ngram: the prompt-lookup draft
+     — no 68M is built or loaded."""
+    if cli.is_ngram_draft(args):
+        print(colored(f"--draft ngram (--ngram_max {args.ngram_max}): no 68M draft is built; --draft-weights "
+                      f"({args.draft_weights}) and --draft_cache_budget ({args.draft_cache_budget}) are ignored", "yellow"))
+        return NgramDraft(target.config.vocab_size, target.device, ngram_max=args.ngram_max)
+    return cli.load_causal_lm(LlamaForCausalLM_68M, cli.draft_weights(args), zoo.draft_for(args.target), DEVICE)
 
 
 def followups(args, tokenizer, engine, prompt, vocab_size, sampling):
@@ -88,7 +102,7 @@ def main():
     args = cli.parse("on_chip")
     cli.target_config(args.target)
     target = cli.load_causal_lm(LlamaForCausalLM, args.weights, args.target, DEVICE)
-    draft = cli.load_causal_lm(LlamaForCausalLM_68M, cli.draft_weights(args), zoo.draft_for(args.target), DEVICE)
+    draft = load_draft(args, target)
     tokenizer, prompts = cli.load_prompts(args, target.config.vocab_size)
     sampling = dict(top_k=args.top_k, top_p=args.top_p, temperature=args.temp)
     print_config(draft, target, args.prefill, args.gen_len, args.gamma, file_path=args.file, method="TriForce",

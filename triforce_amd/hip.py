@@ -195,6 +195,11 @@ for _name in ("tf_skinny_gemm", "tf_skinny_qkv_rope", "tf_skinny_qkv_rope_gqa"):
 SIGNATURES["tf_penalize_logits"] = (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _f32, _f32, _f32, _vp])
 SIGNATURES["tf_penalty_commit"] = (_i32, [_vp, _vp, _i32, _i32, _vp])
 
+# prompt-lookup n-gram draft (include/triforce_hip.h "N-GRAM DRAFT")
+SIGNATURES["tf_ngram_draft_shape"] = (_i32, [_vp])
+SIGNATURES["tf_ngram_draft"] = (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp])
+SIGNATURES["tf_ngram_commit"] = (_i32, [_vp, _i32, _vp, _vp, _i32, _vp])
+
 ABI_VERSION = 1
 _lib = None
 

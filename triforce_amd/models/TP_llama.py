@@ -75,6 +75,8 @@ class DistributedLlama:
         self.prefill_len = prefill
         self.retrieval_budget = retrieval_budget
         self.temperature, self.top_p, self.gamma, self.bsz = temperature, top_p, gamma, bsz
+        from .ngram_draft import refuse_ngram_draft
+        refuse_ngram_draft(draft, "the tensor-parallel / Sequoia engine (TP_llama.DistributedLlama, TP_llama_tree)")
         self.draft, self.draft_cache = draft, draft_cache
         on_gpu = self.device.type == "cuda"
         self.load_stream = torch.cuda.Stream(device=self.device) if on_gpu else None

@@ -1821,6 +1821,123 @@ def penalty_commit(state, ids_row, n):
               "tf_penalty_commit")
 
 
+# ---- prompt-lookup n-gram draft (include/triforce_hip.h "N-GRAM DRAFT") ------------------------------------
+NGRAM_MAX_N = 8
+NGRAM_MAX_BLOCK = 32
+NGRAM_MAX_COMMIT = 64
+_ngram_ws = {}
+
+
+@functools.lru_cache(maxsize=None)
+def _ngram_shape():
+    out = (ctypes.c_int32 * 2)()
+    hip.check(hip.lib().tf_ngram_draft_shape(out), "tf_ngram_draft_shape")
+    return int(out[0]), int(out[1])
+
+
+def ngram_draft_threads():
+    """Threads of tf_ngram_draft's fixed grid: thread t owns the candidates 4 g .. 4 g + 3 for g = t, t + threads, ..."""
+    return _ngram_shape()[0]
+
+
+def ngram_workspace(device):
+    """A zeroed workspace of tf_ngram_draft (packed key + ticket): every launch leaves it zero again."""
+    return torch.zeros(_ngram_shape()[1] // 8, dtype=torch.int64, device=device)
+
+
+def _ngram_default_ws(device):
+    """The per-device workspace of ngram_draft calls that bring none, allocated at the first call outside a capture (a graph's
+    warm-up passes always come first).  Its launches must be stream-ordered: a caller with two streams brings its own."""
+    key = _device_key(device)
+    ws = _ngram_ws.get(key)
+    if ws is None:
+        assert not torch.cuda.is_current_stream_capturing(), "ngram_draft: first call inside a capture without ws="
+        ws = _ngram_ws[key] = ngram_workspace(device)
+    return ws
+
+
+def ngram_draft(hist, len_dev, blk, N, V, q=None, info=None, ws=None):
+    """Prompt lookup over ctx = hist[0:L] ++ blk (L = len_dev[0] clamped to [0, hist.numel()]): the one-hot row ``q`` (fp32, V)
+    of the token that followed the most recent, longest (<= N) earlier occurrence of the context's last tokens, and ``info``
+    (int32, 4) = (token, match length, match position or -1, context length) — the rule of include/triforce_hip.h "N-GRAM
+    DRAFT".  ``hist`` int32, ``len_dev`` int32 scalar tensor, ``blk`` int64 with 1 <= numel <= 32, 1 <= N <= 8.  Device
+    tensors: tf_ngram_draft, one launch, capturable (``ws``: ngram_workspace(), default one per device).  CPU tensors: the
+    torch restatement ngram_draft_host (the tests' oracle; it lets the CPU suite drive the real loop).  Returns (q, info)."""
+    blk = blk.reshape(-1)
+    m, V, N = blk.numel(), int(V), int(N)
+    assert hist.dtype == torch.int32 and hist.dim() == 1 and hist.is_contiguous() and hist.numel() >= 1
+    assert len_dev.dtype == torch.int32 and len_dev.numel() == 1 and blk.dtype == torch.int64 and blk.is_contiguous()
+    assert 1 <= m <= NGRAM_MAX_BLOCK and 1 <= N <= NGRAM_MAX_N and V >= 1
+    if q is None:
+        q = torch.empty(V, dtype=torch.float32, device=hist.device)
+    if info is None:
+        info = torch.empty(4, dtype=torch.int32, device=hist.device)
+    assert q.dtype == torch.float32 and q.numel() == V and q.is_contiguous()
+    assert info.dtype == torch.int32 and info.numel() == 4 and info.is_contiguous()
+    if not hist.is_cuda:
+        return ngram_draft_host(hist, len_dev, blk, N, V, q, info)
+    _dev(hist, len_dev, blk, q, info)
+    if ws is None:
+        ws = _ngram_default_ws(hist.device)
+    assert ws.is_cuda and ws.dtype == torch.int64 and ws.numel() * 8 >= _ngram_shape()[1]
+    hip.check(hip.lib().tf_ngram_draft(_ptr(hist), hist.numel(), _ptr(len_dev), _ptr(blk), m, N, V, _ptr(q), _ptr(info), _ptr(ws),
+                                       _stream()), "tf_ngram_draft")
+    return q, info
+
+
+def ngram_draft_host(hist, len_dev, blk, N, V, q=None, info=None):
+    """tf_ngram_draft restated in torch for CPU tensors: same reads, same row, same info."""
+    blk = blk.reshape(-1)
+    L = min(max(int(len_dev), 0), hist.numel())
+    ctx = torch.cat([hist[:L].to(torch.int64), blk.to(torch.int64)])
+    T = ctx.numel()
+    valid = (ctx >= 0) & (ctx < V)
+    best, at = 0, -1
+    if T >= 2:
+        j = torch.arange(T - 1)
+        run = torch.ones(T - 1, dtype=torch.bool)
+        length = torch.zeros(T - 1, dtype=torch.int64)
+        for k in range(min(int(N), T - 1)):                # l(j): the run of k = 0, 1, .. with ctx[j - k] == ctx[T - 1 - k]
+            src = j - k
+            inside = src >= 0
+            src = src.clamp(min=0)
+            run &= inside & valid[src] & (ctx[src] == ctx[T - 1 - k])
+            length += run
+        best = int(length.max())
+        if best >= 1:
+            at = int((length == best).nonzero()[-1])       # the most recent among equals
+    d = int(ctx[at + 1]) if best >= 1 else int(ctx[T - 1])
+    if not 0 <= d < V:
+        d = 0
+    if q is None:
+        q = torch.empty(V, dtype=torch.float32)
+    if info is None:
+        info = torch.empty(4, dtype=torch.int32)
+    q.zero_()
+    q[d] = 1.0
+    info.copy_(torch.tensor([d, best, at, T], dtype=torch.int32))
+    return q, info
+
+
+def ngram_commit(hist, len_dev, src, n):
+    """hist[L + i] = (int32)src[i] for i < n, then len_dev += n (tf_ngram_commit: one wave, outside every graph; 0 <= n <= 64).
+    L + n > hist.numel() writes nothing: the caller checks the capacity first (models/ngram_draft.NgramCache.commit raises
+    IndexError).  ``src``: int64 tensor with at least n entries.  CPU tensors: the same in torch."""
+    src = src.reshape(-1)
+    n = int(n)
+    assert hist.dtype == torch.int32 and hist.dim() == 1 and hist.is_contiguous() and hist.numel() >= 1
+    assert len_dev.dtype == torch.int32 and len_dev.numel() == 1
+    assert src.dtype == torch.int64 and src.is_contiguous() and 0 <= n <= min(src.numel(), NGRAM_MAX_COMMIT)
+    if not hist.is_cuda:
+        L = int(len_dev)
+        if n > 0 and 0 <= L and L + n <= hist.numel():
+            hist[L:L + n] = src[:n].to(torch.int32)
+            len_dev.fill_(L + n)
+        return
+    _dev(hist, len_dev, src)
+    hip.check(hip.lib().tf_ngram_commit(_ptr(hist), hist.numel(), _ptr(len_dev), _ptr(src), n, _stream()), "tf_ngram_commit")
+
+
 # Rows of normalised hidden state that DecoderLayers.head scores per lm_head GEMM when it is asked for the prompt's
 # log-probabilities: the fp32 logits block is SCORE_BLOCK_ROWS x V (131 MB at 32 000) instead of chunk x V (DESIGN section 23).
 SCORE_BLOCK_ROWS = 1024

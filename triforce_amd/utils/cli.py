@@ -79,11 +79,19 @@ SCRIPT_OWN = {
         ("--reanchor_at", int, 0, "re-anchor the retrieval cache (fold the generated rows into the covered region and "
                                   "re-select) before its generated tail exceeds N rows, gamma + 2 <= N <= --budget: "
                                   "generation and follow-ups may then pass the budget; 0 = never"),
+        ("--ngram_max", int, 3, "--draft ngram: the longest suffix of the context the prompt-lookup draft matches (1 .. 8)"),
         ("--logprobs", "flag", None, "score the prompt during prefill and every emitted token (temperature 1, unfiltered): "
                                      "prints the prompt's mean negative log-likelihood and perplexity, and the mean "
                                      "log-probability of the generation and of each follow-up answer"),
     ],
+    # (the tensor-parallel and Sequoia scripts take --draft only to refuse --draft ngram by name: their draft is the 68M)
+    "offloading_TP": [("--draft", str, "llama-68M", "draft model (llama-68M)")],
+    "offloading_seqouia": [("--draft", str, "llama-68M", "draft model (llama-68M)")],
 }
+# --draft ngram: the prompt-lookup n-gram draft tier — no 68M is built or loaded; test/on_chip.py only
+NGRAM_ENTRY_POINTS = {"offloading": "the offloading entry point (test/offloading.py: OffloadingFlashSimpleCache engine)",
+                      "offloading_TP": "the tensor-parallel entry point (test/offloading_TP.py: DistributedLlama)",
+                      "offloading_seqouia": "the Sequoia entry point (test/offloading_seqouia.py: DistributedLlama + tree)"}
 
 
 def parse(script, argv=None):
@@ -94,6 +102,9 @@ def parse(script, argv=None):
         else:
             ap.add_argument(name, type=typ, default=default, help=help_)
     args = ap.parse_args(argv)
+    if script in NGRAM_ENTRY_POINTS:
+        from ..models.ngram_draft import refuse_ngram_draft
+        refuse_ngram_draft(getattr(args, "draft", None), NGRAM_ENTRY_POINTS[script])
     if getattr(args, "greedy", False):
         args.temp, args.top_p = 1.0, 1e-9
     return args
@@ -112,6 +123,11 @@ def load_causal_lm(cls, weights, config_name, device):
     from ..models import zoo
     cfg = zoo.config(config_name) if weights.startswith(("random", "aligned")) else None
     return cls.from_pretrained(weights, torch_dtype=torch.float16, device_map=device, config=cfg).eval()
+
+
+def is_ngram_draft(args):
+    from ..models.ngram_draft import DRAFT_NAME
+    return getattr(args, "draft", None) == DRAFT_NAME
 
 
 def draft_weights(args):

@@ -576,6 +576,11 @@ class TriForceRunner:
         # the steps appended since — and, with ``time_extend``, the split of the last extend() in seconds
         self.history, self._fed = None, []
         self.time_extend, self.extend_seconds = False, None
+        # the prompt-lookup n-gram draft tier: its NgramCache, whose history every step appends the rows it
+        # leaves in the full cache to; None over the 68M tier, where nothing below changes
+        from ..models.ngram_draft import NgramCache
+        dc = getattr(self.eng, "draft_cache", None)
+        self.ngram = dc if isinstance(dc, NgramCache) else None
 
     @torch.inference_mode()
     def prefill(self, input_ids, prompt_logprobs=None):
@@ -878,6 +883,10 @@ class TriForceRunner:
             # device row in every route (the accept kernel writes behind them).  One launch, outside every graph; the
             # resampled / bonus token stays pending and is counted by the next block's row 0
             _sampling.commit_penalties(self.penalty_state, verify_tokens.view(-1), count + 1)
+        if self.ngram is not None:
+            # the same head of the verify block's device row — the rows this step leaves in the full cache (``_fed`` below) —
+            # joins the n-gram draft's history: one launch, outside every graph, confirmed tokens only
+            self.ngram.commit(verify_tokens.view(-1), count + 1)
         if self.health is not None:
             self.health()
         dp = getattr(getattr(eng, "draft", None), "_persist", None)                        # one-launch draft forward: pinned mirror of its error word
@@ -919,7 +928,11 @@ class TriForceRunner:
         tok_buf = getattr(ge, "tok_buf", None)
         in_tok_buf = tok_buf is not None and tok_buf.shape[0] == 1 and tok_buf.shape[1] >= len(pass_tokens) and tok_buf.is_cuda \
             and len(pass_tokens) <= 32
-        if on_device:
+        if self.ngram is not None:
+            # the n-gram tier has no catch-up forward: its state is the history the commit above appended to
+            if on_device:
+                ge.dev_len = eng.kv_cache.seq_len - (g2 - count)
+        elif on_device:
             ge.dev_len = eng.kv_cache.seq_len - (g2 - count)            # what the accept kernel wrote: the rolled-back length
             ge.replay_draft(g2 + 1)                                      # the pass tokens are in the token buffer already
         elif in_tok_buf and hasattr(ge, "replay_draft") and getattr(ge, "static_outputs", False) and tok_buf.numel() <= 32:

@@ -98,6 +98,8 @@ class InferenceEngine:
     @torch.inference_mode()
     def draft_run(self, input_ids: torch.LongTensor, gamma_offset: int = 0, probs=False, temperature=0.6, top_p=0.9):
         n = input_ids.shape[-1]
+        if n > 64 and hasattr(self.draft, "set_history"):      # the n-gram draft: no forward over the prompt
+            return self.draft.set_history(input_ids, self.draft_cache)
         if n > 64:                                 # draft prefill, 64 tokens per forward with eviction (:44-52)
             logits = self._draft_prefill(input_ids)
         else:
@@ -679,6 +681,8 @@ class GraphInferenceEngine:
 
     @torch.inference_mode()
     def graph_draft_prefill(self, input_ids: torch.LongTensor):
+        if hasattr(self.engine.draft, "set_history"):          # the n-gram draft: the prompt IS its state, at any length
+            return self.engine.draft.set_history(input_ids, self.engine.draft_cache)
         return self.engine.draft_run(input_ids=input_ids)
 
     @torch.inference_mode()
