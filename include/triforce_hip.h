@@ -208,7 +208,12 @@ int tf_draft_persist_reset(void* ctl, void* host_mirror, int set_mirror);
  *                      (ROUNDING OF fp16(a * b), above).
  * tf_retrieval_topk  : idx[h][0] = 0, idx[h][1..sets-1] = the sets-1 best chunks of [1,C),
  *                      descending score, ascending chunk index among equal scores
- *                      (cache.py:159-162; torch.topk leaves the tie order undefined).  C <= 32768.
+ *                      (cache.py:159-162; torch.topk leaves the tie order undefined).
+ *                      ORDER: fp16 BIT-PATTERN order (sign-magnitude), so -0 sorts below +0 and
+ *                      +NaN first (above +inf).  "Equal scores" (ties) means equal bit patterns:
+ *                      a (+0, -0) pair is NOT a tie - it differs from IEEE equality there, and is
+ *                      equally admissible against the reference's unspecified tie order.
+ *                      2 <= C, 1 <= sets <= C (else TF_EINVAL); C <= 32768 (else TF_ERANGE).
  * tf_retrieval_gather: dst slot j of head h <- chunk idx[h][j] (chunk rows of D), K and V
  *                      (cache.py:163-175).
  * ------------------------------------------------------------------------------------------- */

@@ -32,7 +32,7 @@ def needs_build():
     t = os.path.getmtime(LIB_PATH)
     deps = sources() + [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "tree_mask.h"), os.path.join(CSRC, "select_common.h"),
                         os.path.join(CSRC, "topp_select.h"),
-                        os.path.join(CSRC, "sg_rule.h"),
+                        os.path.join(CSRC, "sg_rule.h"), os.path.join(CSRC, "retrieval_rule.h"),
                         os.path.join(HERE, "..", "include", "triforce_hip.h"), os.path.abspath(__file__)]   # (flags live here)
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 

@@ -11,6 +11,7 @@
 // All of it is HBM-bound byte work: K is streamed exactly once (16-B loads, 256-B row segments
 // per 16-lane group), nothing is staged in a temporary, the top-k runs in LDS.
 #include "common.h"
+#include "retrieval_rule.h"
 
 // ---- scoring ------------------------------------------------------------------------------
 // One 16-lane group per chunk (a wave scores 4 chunks per step); lane (c4, li) owns 8 d's.
@@ -310,14 +311,7 @@ extern "C" int tf_retrieval_score(const void* k, int64_t stride_t, int64_t strid
     if (!k || !q || !scores || C < 1 || chunk < 1 || H < 1) return TF_EINVAL;
     if ((stride_t % 8) || (stride_h % 8)) return TF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const int gpb = 256 / (D / 8);
-    int gx = (C + gpb - 1) / gpb;
-    // 8 resident workgroups per CU and NOT ONE MORE: with ceil(2048 / H) the 32 (H = 40) or 2 (H = 5) workgroups past
-    // 2 048 start when the others retire and stream their share alone, latency-bound (0.59 of peak at H = 40 against
-    // 0.81 at H = 32, profiles/r03_bench_13b_cfg4_world1.json); grid-stride beyond
-    const int cap = H <= 2048 ? 2048 / H : 1;
-    if (gx > cap) gx = cap;
-    if (gx < 1) gx = 1;
+    const int gx = rt_chunk_grid_x(C, H, D);          // (retrieval_rule.h: 8 resident workgroups per CU, grid-stride beyond)
     if (D == 128)
         hipLaunchKernelGGL((retrieval_score_kernel<128>), dim3(gx, H), dim3(256), 0, st, (const h16*)k, stride_t,
                            stride_h, (const h16*)q, (h16*)scores, C, chunk);
@@ -330,22 +324,13 @@ extern "C" int tf_retrieval_score(const void* k, int64_t stride_t, int64_t strid
     return TF_OK;
 }
 
-// workgroups along x for n chunk groups of work at H heads: the scorer's rule, 8 resident workgroups per CU and not one more
-static int chunk_grid_x(int n, int H, int D) {
-    const int gpb = 256 / (D / 8);
-    int gx = (n + gpb - 1) / gpb;
-    const int cap = H <= 2048 ? 2048 / H : 1;
-    if (gx > cap) gx = cap;
-    return gx < 1 ? 1 : gx;
-}
-
 extern "C" int tf_chunk_mean(const void* k, int64_t stride_t, int64_t stride_h, void* index_layer, int64_t index_stride_h,
                              int c0, int c1, int chunk, int H, int D, void* stream) {
     if (!k || !index_layer || c0 < 0 || c1 < c0 || chunk < 1 || H < 1 || (D != 128 && D != 64)) return TF_EINVAL;
     if ((stride_t % 8) || (stride_h % 8) || (index_stride_h % 8) || index_stride_h < (int64_t)c1 * D) return TF_EINVAL;
     if (c1 == c0) return TF_OK;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(chunk_grid_x(c1 - c0, H, D), H);
+    const dim3 grid(rt_chunk_grid_x(c1 - c0, H, D), H);
     if (D == 128)
         hipLaunchKernelGGL((chunk_mean_kernel<128>), grid, dim3(256), 0, st, (const h16*)k, stride_t, stride_h,
                            (h16*)index_layer, index_stride_h, c0, c1, chunk);
@@ -361,7 +346,7 @@ extern "C" int tf_retrieval_score_indexed(const void* index_layer, int64_t index
     if (!index_layer || !q || !scores || C < 1 || H < 1 || (D != 128 && D != 64)) return TF_EINVAL;
     if ((index_stride_h % 8) || index_stride_h < (int64_t)C * D) return TF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(chunk_grid_x(C, H, D), H);
+    const dim3 grid(rt_chunk_grid_x(C, H, D), H);
     if (D == 128)
         hipLaunchKernelGGL((retrieval_score_indexed_kernel<128>), grid, dim3(256), 0, st, (const h16*)index_layer,
                            index_stride_h, (const h16*)q, (h16*)scores, C);
@@ -372,42 +357,41 @@ extern "C" int tf_retrieval_score_indexed(const void* index_layer, int64_t index
     return TF_OK;
 }
 
+// ORDER of tf_retrieval_topk: chunk 0 first, then the sets - 1 best candidates of [1, C) by fp16 BIT-PATTERN order
+// (sortable_fp16: sign-magnitude, so -0 sorts below +0 and +NaN first, above +inf), ascending chunk among ties.  "Ties" means
+// equal bit patterns: a (+0, -0) pair is NOT a tie.  That differs from IEEE equality (torch.topk sees the pair as equal) and
+// is equally admissible against the reference, whose order among equal scores is unspecified.  Both kernels sort the same
+// distinct 32-bit keys, so the form rt_topk_pick chooses never shows in the output.
 extern "C" int tf_retrieval_topk(const void* scores, int32_t* idx, int C, int sets, int H, void* stream) {
     if (!scores || !idx || C < 2 || sets < 1 || sets > C || H < 1) return TF_EINVAL;
     if (C > 32768) return TF_ERANGE;
-    // select-then-sort when candidates + winners fit in LDS together (always for the paper's shapes)
-    int mpow2 = 2;
-    while (mpow2 < sets - 1) mpow2 <<= 1;
-    const size_t lds_sel = (size_t)((C - 1) + mpow2) * sizeof(uint32_t);
-    if (lds_sel <= 150 * 1024 && mpow2 <= 8192) {
-        if (lds_sel > 48 * 1024) {
+    const RtTopkPick pk = rt_topk_pick(C, sets);      // retrieval_rule.h: the form, its LDS, whether the attribute must be raised
+    if (pk.form == RT_TOPK_SELECT) {
+        if (pk.raise) {
             static bool raised_sel = false;
             if (!raised_sel) {
                 hipError_t e = hipFuncSetAttribute((const void*)retrieval_topk_select_kernel,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)pk.raise_to);
                 if (e != hipSuccess) return (int)e;
                 raised_sel = true;
             }
         }
-        hipLaunchKernelGGL(retrieval_topk_select_kernel, dim3(H), dim3(1024), lds_sel, (hipStream_t)stream,
-                           (const uint16_t*)scores, idx, C, sets, C - 1, mpow2);
+        hipLaunchKernelGGL(retrieval_topk_select_kernel, dim3(H), dim3(1024), pk.lds, (hipStream_t)stream,
+                           (const uint16_t*)scores, idx, C, sets, C - 1, pk.mpow2);
         TF_LAUNCH_CHECK();
         return TF_OK;
     }
-    int npow2 = 2;
-    while (npow2 < C - 1) npow2 <<= 1;
-    const size_t lds = (size_t)npow2 * sizeof(uint32_t);
-    if (lds > 64 * 1024) {
+    if (pk.raise) {
         static bool raised = false;
         if (!raised) {
             hipError_t e = hipFuncSetAttribute((const void*)retrieval_topk_kernel,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)pk.raise_to);
             if (e != hipSuccess) return (int)e;
             raised = true;
         }
     }
-    hipLaunchKernelGGL(retrieval_topk_kernel, dim3(H), dim3(1024), lds, (hipStream_t)stream,
-                       (const uint16_t*)scores, idx, C, sets, npow2);
+    hipLaunchKernelGGL(retrieval_topk_kernel, dim3(H), dim3(1024), pk.lds, (hipStream_t)stream,
+                       (const uint16_t*)scores, idx, C, sets, pk.npow2);
     TF_LAUNCH_CHECK();
     return TF_OK;
 }
@@ -465,8 +449,7 @@ static int kv_copy_rows_launch(const void* src, const void* src2, int64_t src_st
     if ((src_stride_t % 8) || (src_stride_h % 8) || (src_stride_l % 8) || (dst_stride_t % 8) || (dst_stride_h % 8) ||
         (dst_stride_l % 8))
         return TF_EINVAL;
-    int gx = (n * (D / 8) + 255) / 256;
-    if (gx > 64) gx = 64;
+    const int gx = rt_copy_grid_x(n, D);
     hipLaunchKernelGGL(kv_copy_rows_kernel, dim3(gx, L * H, src2 ? 2 : 1), dim3(256), 0, (hipStream_t)stream,
                        (const h16*)src, src_stride_l, src_stride_t, src_stride_h, (h16*)dst, dst_stride_l, dst_stride_t,
                        dst_stride_h, src_t0, dst_t0, n, H, D, (const h16*)src2, (h16*)dst2);

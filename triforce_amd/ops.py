@@ -1394,7 +1394,10 @@ def retrieval_score_indexed(index_layer, q, chunks):
 
 
 def retrieval_topk(scores, sets):
-    """(H, sets) int32: chunk 0 first, then the sets-1 best of [1,C), descending, ties -> lowest chunk."""
+    """(H, sets) int32: chunk 0 first, then the sets-1 best of [1,C), descending, ties -> lowest chunk.
+    The order is the fp16 BIT-PATTERN order (sign-magnitude): -0 below +0, +NaN first (above +inf).  "Ties" are equal bit
+    patterns: a (+0, -0) pair is not a tie - unlike IEEE equality, and equally admissible against torch.topk, whose order
+    among equal scores is unspecified."""
     _dev(scores)
     H, C = scores.shape
     assert scores.dtype == _HALF and scores.is_contiguous()
