@@ -872,6 +872,30 @@ int tf_token_logprobs_ids(const float* logits, int64_t row_stride, const int64_t
                           float* logprob, float* lse, void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * TOP-N ALTERNATIVES AND TOKEN RANKS, beside tf_token_logprobs.  Input as there: `rows` rows of fp32
+ * logits, unit stride on V, row r at logits + r * row_stride, row_stride >= V, any V >= 1, rows need not be 16-byte aligned.
+ * 1 <= N <= 20.  ORDER of a row's entries: value descending, then id ascending — a total order; -inf entries take part
+ * (-0 and +0 are equal values).  Rows with NaN are outside the contract (nothing is read or written out of bounds).
+ *   top_ids[r][j]  int32 [rows][N]: the id at place j of that order, j < min(N, V); places j >= V hold -1.
+ *   top_lp[r][j]   fp32  [rows][N]: x[id] - M - log S with the expression, the rounding points and the (M, S) accumulation
+ *                  order of tf_token_logprobs (one shared device function): bit-identical to what tf_token_logprobs
+ *                  returns for that row and id.  -inf entries give -inf; places j >= V hold -inf.
+ *   rank[r]        int32 [rows]: 1 + #{i : x_i > x_t, or x_i == x_t and i < t} for the row's target t; 0 for a target
+ *                  outside [0, V).  rank <= N exactly when top_ids[r][rank - 1] == t.
+ *   lp[r]          fp32 [rows], optional: what tf_token_logprobs would write for (row, target) — one launch serves both.
+ * Exact and deterministic bit for bit: integer counting only, no floating-point atomics, no global workspace; one launch,
+ * one workgroup per row, a number of walks over the row that does not depend on N (2 on rows without long ties, at most 9).
+ * tf_token_top_logprobs: targets is a DEVICE array of `rows` ids, or NULL — then rank and lp must be NULL too.
+ * tf_token_top_logprobs_ids: the ids (host memory, rows <= 32) travel as kernel arguments; rank is required.
+ * TF_EINVAL before anything is launched or written: NULL logits / top_ids / top_lp, N outside [1, 20], rows < 1, V < 1,
+ * row_stride < V, targets without rank, rank or lp without targets (and rows > 32, NULL host_ids / rank for the _ids form).
+ * ------------------------------------------------------------------------------------------- */
+int tf_token_top_logprobs(const float* logits, int64_t row_stride, const int64_t* targets, int rows, int V, int N,
+                          int32_t* top_ids, float* top_lp, int32_t* rank, float* lp, void* stream);
+int tf_token_top_logprobs_ids(const float* logits, int64_t row_stride, const int64_t* host_ids, int rows, int V, int N,
+                              int32_t* top_ids, float* top_lp, int32_t* rank, float* lp, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * ATTENTION BIAS: the q / k / v / o projections of a model with `attention_bias` (the reference builds
  * them with bias=config.attention_bias, models/modeling_llama.py:174-177).  Each entry is its bias-free neighbour — same
  * operands, layouts, launch forms and gates — plus `bias`: fp16 [N], 8-byte aligned, in the ROW ORDER OF THE PACKED WEIGHT

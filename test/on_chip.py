@@ -85,17 +85,24 @@ def followups(args, tokenizer, engine, prompt, vocab_size, sampling):
                           f"{cli.mean(st['logprobs']):.4f} over {len(st['logprobs'])} tokens", "red"))
 
 
-def report_logprobs(tokenizer, engine, prompts, run):
+def report_logprobs(tokenizer, engine, prompts, run, top_logprobs=0):
     """--logprobs: one more TriForce run per prompt that scores the prompt during its prefill and every emitted token
-    (DESIGN section 23), outside the timed runs above."""
+    (DESIGN section 23), outside the timed runs above.  --top_logprobs N: the run also lists the N most likely alternatives
+    of every emitted token and its rank; the mean rank and the share of tokens at rank 1 are printed."""
     import math
     for i, p in enumerate(prompts):
-        st = TriForce(tokenizer, engine, p, return_details=True, logprobs=True, prompt_logprobs=True, **run)
+        st = TriForce(tokenizer, engine, p, return_details=True, logprobs=True, prompt_logprobs=True,
+                      top_logprobs=top_logprobs, **run)
         nll = -float(st["prompt_logprobs"].double().mean())
         print(colored(f"[Logprobs] prompt {i + 1}/{len(prompts)} ({p.shape[1]} tokens): mean negative log-likelihood {nll:.4f}, "
                       f"perplexity {math.exp(nll):.3f}", "red"))
         print(colored(f"[Logprobs] generation: mean log-probability {cli.mean(st['logprobs']):.4f} over "
                       f"{len(st['logprobs'])} tokens", "red"))
+        if top_logprobs:
+            ranks = st["ranks"]
+            print(colored(f"[Logprobs] generation: mean rank {cli.mean(ranks):.3f}, "
+                          f"{100.0 * sum(r == 1 for r in ranks) / len(ranks):.1f}% of the tokens at rank 1 "
+                          f"(top {top_logprobs} alternatives per token kept)", "red"))
 
 
 def main():
@@ -130,8 +137,8 @@ def main():
     for _ in range(3):
         TriForce(tokenizer, engine, clip(prompts[0]), **run)
     results = [TriForce(tokenizer, engine, clip(p), file_path=args.file, **run) for p in prompts]
-    if args.logprobs:
-        report_logprobs(tokenizer, engine, [clip(p) for p in prompts], run)
+    if args.logprobs or args.top_logprobs:
+        report_logprobs(tokenizer, engine, [clip(p) for p in prompts], run, args.top_logprobs)
     method_latency = 1000 / cli.mean([speed for _, speed in results])
     print(colored(f"average acceptance rate (NOT per token): {cli.mean([acc for acc, _ in results])}", "red"))
     print(colored(f"[TriForce] average latency: {method_latency} ms", "red"))

@@ -5,37 +5,10 @@
 // rescaled sum — so it takes any V, any row stride and any number of rows.  One workgroup per row; wave reduction, then
 // one LDS step across the waves; no atomics, no hand-off inside the launch, a fixed summation order (results are
 // reproducible bit for bit).
-#include <math.h>
-#include "common.h"
-
-#define LP_THREADS 1024
-#define LP_WAVES (LP_THREADS / 64)
-#define LP_MAX_IDS 32
-
-struct LpIds { int v[LP_MAX_IDS]; };
-
-// running (max, sum of exp(x - max)) over the entries seen so far; m = -inf, s = 0 before the first finite entry
-__device__ __forceinline__ void lp_take4(f32x4 v, float& m, float& s) {
-    const float vm = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
-    if (vm > m) {                                                   // rare after the first few vectors of a thread
-        s *= expf(m - vm);                                          // m = -inf: s is 0 and stays 0
-        m = vm;
-    }
-    if (m > -INFINITY) {                                            // (all -inf so far: mass 0, and -inf - -inf is NaN)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s += expf(v[j] - m);            // a -inf entry adds expf(-inf) = 0
-    }
-}
-
-__device__ __forceinline__ void lp_take1(float x, float& m, float& s) {
-    if (x > m) {
-        s *= expf(m - x);
-        m = x;
-    }
-    if (m > -INFINITY) s += expf(x - m);
-}
+#include "logprobs_row.h"
 
 // use_ids: the row's target is ids.v[row] (rows <= 32, kernel arguments), else targets[row] (device memory, may be NULL).
+// The walk, the fold and the value expression live in logprobs_row.h, shared with top_logprobs.hip.
 __global__ __launch_bounds__(LP_THREADS) void token_logprobs_kernel(const float* __restrict__ logits, int64_t row_stride,
                                                                     const int64_t* __restrict__ targets, LpIds ids,
                                                                     int use_ids, int V, float* __restrict__ logprob,
@@ -44,45 +17,14 @@ __global__ __launch_bounds__(LP_THREADS) void token_logprobs_kernel(const float*
     __shared__ float red_s[LP_WAVES];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* x = logits + (int64_t)row * row_stride;
-    // [0, head) scalar up to the first 16-byte boundary, then nvec aligned 16-byte loads, then [tail0, V) scalar: whatever
-    // the base address and the stride are, all but at most six entries of a row travel in 16-byte loads
-    const int head = min(V, (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(x) & 15u)) & 15u) >> 2));
-    const int nvec = (V - head) >> 2;
-    const int tail0 = head + 4 * nvec;
-    const f32x4* xv = reinterpret_cast<const f32x4*>(x + head);
     float m = -INFINITY, s = 0.f;
-    int i = tid;
-    for (; i + 3 * LP_THREADS < nvec; i += 4 * LP_THREADS) {        // four loads in flight per thread
-        const f32x4 a = xv[i], b = xv[i + LP_THREADS], c = xv[i + 2 * LP_THREADS], d = xv[i + 3 * LP_THREADS];
-        lp_take4(a, m, s);
-        lp_take4(b, m, s);
-        lp_take4(c, m, s);
-        lp_take4(d, m, s);
-    }
-    for (; i < nvec; i += LP_THREADS) lp_take4(xv[i], m, s);
-    if (tid < head) lp_take1(x[tid], m, s);
-    if (tid < V - tail0) lp_take1(x[tail0 + tid], m, s);
-
-    // wave: common maximum, sums rescaled to it
-    const float wm = wave_max(m);
-    const float ws = wave_sum(m > -INFINITY ? s * expf(m - wm) : 0.f);
-    if (lane == 0) {
-        red_m[wave] = wm;
-        red_s[wave] = ws;
-    }
-    __syncthreads();
-    if (wave == 0) {
-        const float pm = lane < LP_WAVES ? red_m[lane] : -INFINITY;
-        const float ps = lane < LP_WAVES ? red_s[lane] : 0.f;
-        const float M = wave_max(pm);
-        const float S = wave_sum(pm > -INFINITY ? ps * expf(pm - M) : 0.f);
-        if (lane == 0) {
-            const float logS = logf(S);
-            if (lse) lse[row] = M + logS;
-            if (logprob) {
-                const int64_t t = use_ids ? (int64_t)ids.v[row] : (targets ? targets[row] : (int64_t)-1);
-                logprob[row] = (t >= 0 && t < (int64_t)V) ? (x[t] - M) - logS : 0.f;     // outside [0, V): no target
-            }
+    lp_for_each(x, V, tid, [&](f32x4 v, int) { lp_take4(v, m, s); }, [&](float v, int) { lp_take1(v, m, s); });
+    float M, logS;
+    if (lp_fold(m, s, red_m, red_s, lane, wave, M, logS)) {
+        if (lse) lse[row] = M + logS;
+        if (logprob) {
+            const int64_t t = use_ids ? (int64_t)ids.v[row] : (targets ? targets[row] : (int64_t)-1);
+            logprob[row] = lp_value(x, t, V, M, logS);                                       // outside [0, V): no target
         }
     }
 }

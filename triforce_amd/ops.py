@@ -1980,6 +1980,78 @@ def token_logprobs(logits, targets=None, out=None, lse=None):
     return lse if targets is None else out
 
 
+TOP_LOGPROBS_MAX = 20
+
+
+def token_top_logprobs(logits, targets, n, top_ids=None, top_lp=None, rank=None, out=None):
+    """The ``n`` (1 .. 20) most likely entries of every row of the (rows, V) fp32 device ``logits`` — ordered by value
+    descending, then id ascending — with their log-probabilities, and the rank of every row's target in that order
+    (tf_token_top_logprobs, one launch).  ``targets`` as in token_logprobs: an int64 device tensor of
+    ``rows`` ids, a python list of <= 32 ids (kernel arguments, no upload), or None (no rank).  ``top_ids`` (rows, n) int32,
+    ``top_lp`` (rows, n) fp32, ``rank`` (rows,) int32: contiguous device tensors to write, allocated when not given; ``out``
+    (rows,) fp32, optional: the targets' own log-probabilities, what token_logprobs would write.  Places past V hold id -1
+    and -inf; a target outside [0, V) has rank 0.  Returns (top_ids, top_lp, rank) — rank is None without targets."""
+    _dev(logits, top_ids, top_lp, rank, out)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and logits.numel() > 0
+    rows, V = logits.shape
+    n = int(n)
+    assert 1 <= n <= TOP_LOGPROBS_MAX, f"top-N: n = {n} is outside [1, {TOP_LOGPROBS_MAX}]"
+    stride = logits.stride(0) if rows > 1 else max(logits.stride(0), V)
+    assert stride >= V, "rows of the logits block overlap"
+    assert targets is not None or (rank is None and out is None), "rank / out need targets"
+    if top_ids is None:
+        top_ids = torch.empty(rows, n, dtype=torch.int32, device=logits.device)
+    if top_lp is None:
+        top_lp = torch.empty(rows, n, dtype=torch.float32, device=logits.device)
+    if rank is None and targets is not None:
+        rank = torch.empty(rows, dtype=torch.int32, device=logits.device)
+    for t, dtype, count in ((top_ids, torch.int32, rows * n), (top_lp, torch.float32, rows * n), (rank, torch.int32, rows),
+                            (out, torch.float32, rows)):
+        assert t is None or (t.dtype == dtype and t.numel() == count and t.is_contiguous())
+    if isinstance(targets, (list, tuple)):
+        assert len(targets) == rows <= TOKEN_LOGPROBS_MAX_IDS
+        host = (ctypes.c_int64 * rows)(*[int(t) for t in targets])
+        hip.check(hip.lib().tf_token_top_logprobs_ids(_ptr(logits), stride, host, rows, V, n, _ptr(top_ids), _ptr(top_lp),
+                                                      _ptr(rank), _ptr(out), _stream()), "tf_token_top_logprobs_ids")
+        return top_ids, top_lp, rank
+    if targets is not None:
+        _dev(targets)
+        targets = targets.reshape(-1)
+        assert targets.dtype == torch.int64 and targets.numel() == rows and targets.is_contiguous()
+    hip.check(hip.lib().tf_token_top_logprobs(_ptr(logits), stride, _ptr(targets), rows, V, n, _ptr(top_ids), _ptr(top_lp),
+                                              _ptr(rank), _ptr(out), _stream()), "tf_token_top_logprobs")
+    return top_ids, top_lp, rank
+
+
+def token_top_logprobs_ref(logits, targets, n):
+    """Host restatement of token_top_logprobs on a (rows, V) fp32 CPU tensor -> (top_ids, top_lp, rank) as it returns them:
+    a stable descending sort for the order, the counting formula for the rank, and the kernel's rounding points for the
+    values — (x - M) - log S in fp32 with M the row maximum; S is summed here in float64 and rounded once, so the values
+    agree with the kernel's to the few fp32 spacings of its own summation order, the ids and ranks exactly."""
+    x = logits.detach().float().cpu()
+    rows, V = x.shape
+    n = int(n)
+    assert 1 <= n <= TOP_LOGPROBS_MAX
+    k = min(n, V)
+    order = torch.sort(x, dim=1, descending=True, stable=True).indices[:, :k]
+    M = x.max(dim=1, keepdim=True).values
+    logS = torch.exp((x - M).double()).sum(dim=1, keepdim=True).float().log()
+    vals = x.gather(1, order)
+    top_ids = torch.full((rows, n), -1, dtype=torch.int32)
+    top_lp = torch.full((rows, n), -float("inf"), dtype=torch.float32)
+    top_ids[:, :k] = order.to(torch.int32)
+    top_lp[:, :k] = torch.where(torch.isinf(vals) & (vals < 0), vals, (vals - M) - logS)
+    if targets is None:
+        return top_ids, top_lp, None
+    t = torch.as_tensor(targets, dtype=torch.int64).reshape(-1)
+    ok = (t >= 0) & (t < V)
+    tc = t.clamp(0, V - 1)
+    xt = x.gather(1, tc[:, None])
+    before = (x > xt) | ((x == xt) & (torch.arange(V)[None, :] < tc[:, None]))
+    rank = torch.where(ok, 1 + before.sum(dim=1), torch.zeros_like(t)).to(torch.int32)
+    return top_ids, top_lp, rank
+
+
 def sample_inverse_cdf(probs, u, token_out):
     """token_out[0] <- first index with inclusive cumsum(probs) > u[0]*sum(probs).  All device tensors."""
     _dev(probs, u)

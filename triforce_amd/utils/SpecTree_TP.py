@@ -80,7 +80,11 @@ def _worst_walk(successors):
 class SpecTree:
     def __init__(self, engine, temperature: float = 0.6, top_p: float = 0.9, max_length=256, vocab_size=32000,
                  grow_map=None, residual_graph=None, sampling_callables=None, sample_gather_indices=None,
-                 tokenizer=None, rng=None, rand_values=None, logprobs=False, prompt_logprobs=False) -> None:
+                 tokenizer=None, rng=None, rand_values=None, logprobs=False, prompt_logprobs=False, top_logprobs=0) -> None:
+        if top_logprobs:                                 # (refused before anything is captured: DESIGN section 33)
+            raise NotImplementedError("top_logprobs (like logprobs / prompt_logprobs) is implemented for the single-GPU "
+                                      "resident TriForce and autoregressive loops only, not for the Sequoia tree loop "
+                                      "(SpecTree)")
         if logprobs or prompt_logprobs:                  # (refused before anything is captured: DESIGN section 23)
             raise NotImplementedError("logprobs / prompt_logprobs are implemented for the single-GPU resident TriForce and "
                                       "autoregressive loops only, not for the Sequoia tree loop (SpecTree)")

@@ -83,6 +83,9 @@ SCRIPT_OWN = {
         ("--logprobs", "flag", None, "score the prompt during prefill and every emitted token (temperature 1, unfiltered): "
                                      "prints the prompt's mean negative log-likelihood and perplexity, and the mean "
                                      "log-probability of the generation and of each follow-up answer"),
+        ("--top_logprobs", int, 0, "implies --logprobs: also keep the N most likely alternatives of every emitted token and "
+                                   "its rank (1 <= N <= 20, scored on the device in the same launch); prints the mean rank "
+                                   "and the share of tokens at rank 1; 0 = off"),
     ],
     # (the tensor-parallel and Sequoia scripts take --draft only to refuse --draft ngram by name: their draft is the 68M)
     "offloading_TP": [("--draft", str, "llama-68M", "draft model (llama-68M)")],

@@ -36,8 +36,10 @@ def _eos(tokenizer):
 @torch.inference_mode()
 def Autoregressive(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, top_p=0.9, temperature=0.6, verbose=False,
                    rng=None, return_tokens=False, logprobs=False, min_p=0.0, repetition_penalty=1.0, frequency_penalty=0.0,
-                   presence_penalty=0.0):
-    """``min_p`` > 0: min-p behind top-k / top-p.  ``logprobs``: also the log-probability (temperature 1, unfiltered: DESIGN section 23) of every emitted token, scored
+                   presence_penalty=0.0, top_logprobs=0):
+    """``top_logprobs`` = N in 1 .. 20 (implies ``logprobs``): also the N most likely alternatives of every
+    step and the emitted token's rank, from the same launch -> (tokens / s, ids, logprobs, top_logprobs, ranks).
+    ``min_p`` > 0: min-p behind top-k / top-p.  ``logprobs``: also the log-probability (temperature 1, unfiltered: DESIGN section 23) of every emitted token, scored
     on the device from the step's own logits -> (tokens / s, ids, logprobs).  The three penalties: every
     step's row is penalised with the engine's state and its own input token, which is then committed — on the device, no
     host sync in the loop; the log-probabilities stay those of the raw logits."""
@@ -45,12 +47,15 @@ def Autoregressive(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, to
     device = eng.model.device
     pen = Penalties(repetition_penalty, frequency_penalty, presence_penalty)
     state = _penalty_state(graph_engine, pen)
-    lp = None
-    if logprobs:
-        refusal = _logprobs_refusal(graph_engine, "logprobs")
+    lp = top = None
+    top_n = _top_logprobs_n(top_logprobs)
+    if logprobs or top_n:
+        refusal = _logprobs_refusal(graph_engine, "top_logprobs" if top_n else "logprobs")
         if refusal is not None:
             raise NotImplementedError(refusal)
         lp = torch.empty(max_len + 1, dtype=torch.float32, device=device)
+        if top_n:
+            top = _TopBuffers(device, top_n, max_len + 1)
     rng = rng or UniformSource(device)
     kw = Filters(temperature, top_p, top_k, min_p).kw()
     eng.kv_cache.reset()
@@ -60,7 +65,9 @@ def Autoregressive(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, to
         state.reset(input_ids)
         row = _sampling.penalize(row, None, state, pen)
     next_token = sample(norm_logits(row, **kw), rng=rng)
-    if lp is not None:
+    if top is not None:
+        top.score(logits[:, -1, :], next_token.view(-1), 0, lp)
+    elif lp is not None:
         ops.token_logprobs(logits[:, -1, :], next_token.view(-1), out=lp[0:1])
     toks = [next_token]
     n = 0
@@ -78,16 +85,20 @@ def Autoregressive(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, to
             next_token = sample(norm_logits(logits[:, -1, :], **kw), rng=rng)
         toks.append(next_token)
         n += 1
-        if lp is not None:                  # device targets, the step's own logits (a graph's static buffer until its next replay)
+        if top is not None:                 # (one launch for the value, the alternatives and the rank)
+            top.score(logits[:, -1, :], next_token.view(-1), n, lp)
+        elif lp is not None:                # device targets, the step's own logits (a graph's static buffer until its next replay)
             ops.token_logprobs(logits[:, -1, :], next_token.view(-1), out=lp[n:n + 1])
     _sync(device)
     time2 = time.time()
-    if verbose or return_tokens or logprobs:
+    if verbose or return_tokens or lp is not None:
         ids = torch.cat(toks, dim=1)[0].tolist()
         if verbose:
             for t in ids:
                 spec_stream(t, tokenizer, "cyan")
-        if logprobs:
+        if top is not None:
+            return (n / (time2 - time1), ids, lp[:n + 1].tolist()) + top.read(n + 1)
+        if lp is not None:
             return n / (time2 - time1), ids, lp[:n + 1].tolist()
         if return_tokens:
             return n / (time2 - time1), ids
@@ -107,6 +118,50 @@ def _penalty_state(graph_engine, penalties):
             f"(initialize_cuda_graph / initialize_eager(repetition_penalty=..., frequency_penalty=..., presence_penalty=...)); "
             f"{type(graph_engine).__name__} holds no penalty state")
     return state
+
+
+TOP_LOGPROBS_REFUSAL = ("top_logprobs (like logprobs / prompt_logprobs) is implemented for the single-GPU resident "
+                        "GraphInferenceEngine only, not for {} (tensor-parallel loop)")
+
+
+def _top_logprobs_n(top_logprobs):
+    """The ``top_logprobs`` keyword as an int: 0 = off, 1 .. 20 alternatives per emitted token."""
+    given = top_logprobs or 0
+    n = int(given)
+    if n != given or not 0 <= n <= ops.TOP_LOGPROBS_MAX:
+        raise ValueError(f"top_logprobs={top_logprobs!r} is outside [0, {ops.TOP_LOGPROBS_MAX}] (0 = off)")
+    return n
+
+
+class _TopBuffers:
+    """Device buffers of the top-N alternatives and ranks of the emitted tokens, in emission order beside the log-probability
+    buffer: (n, N) int32 ids, (n, N) fp32 values, (n,) int32 ranks.  score() is one ops.token_top_logprobs launch that also
+    writes the tokens' own log-probabilities; nothing is read back before read()."""
+
+    def __init__(self, device, top_n, rows):
+        self.device, self.top_n = device, top_n
+        self.ids = torch.empty(rows, top_n, dtype=torch.int32, device=device)
+        self.lp = torch.empty(rows, top_n, dtype=torch.float32, device=device)
+        self.rank = torch.empty(rows, dtype=torch.int32, device=device)
+
+    def reserve(self, n, rows):
+        """Room for rows [0, rows); rows [0, n) are kept."""
+        if rows <= self.rank.numel():
+            return
+        old = (self.ids, self.lp, self.rank)
+        self.__init__(self.device, self.top_n, max(1024, 2 * rows))
+        for new, was in zip((self.ids, self.lp, self.rank), old):
+            new[:n].copy_(was[:n])
+
+    def score(self, logits, targets, at, lp):
+        k = logits.shape[0]
+        ops.token_top_logprobs(logits, targets, self.top_n, top_ids=self.ids[at:at + k], top_lp=self.lp[at:at + k],
+                               rank=self.rank[at:at + k], out=lp[at:at + k])
+
+    def read(self, n):
+        """(per token the N (id, logprob) pairs in order, the ranks) of rows [0, n): the one device-to-host read."""
+        ids, lp = self.ids[:n].tolist(), self.lp[:n].tolist()
+        return [list(zip(i, v)) for i, v in zip(ids, lp)], self.rank[:n].tolist()
 
 
 def _logprobs_refusal(graph_engine, what):
@@ -505,7 +560,8 @@ class TriForceRunner:
 
     def __init__(self, tokenizer, graph_engine, gamma, top_k=-1, top_p=0.9, temperature=0.6, verbose=False, rng=None,
                  inclusive_accept=False, sync_record=None, rebuild_every=0, reanchor_at=0, logprobs=False,
-                 prompt_logprobs=False, min_p=0.0, repetition_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0):
+                 prompt_logprobs=False, min_p=0.0, repetition_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0,
+                 top_logprobs=0):
         # filters: what the TARGET's distribution (first token, target verify) is normalised with.  top_k > 0 and min_p > 0 (a
         #              token stays only if its probability is at least min_p times the most likely token's, behind top-k / top-p:
         #              DESIGN section 27) apply to it alone; the draft tiers stay unfiltered
@@ -518,8 +574,11 @@ class TriForceRunner:
         # logprobs: keep the log-probability (temperature 1, unfiltered: DESIGN section 23) of every emitted token, scored on the
         #              device from the logits of the verify that produced it — one launch per step, no host read before stats()
         # prompt_logprobs: prefill() also scores the prompt, log p(input_ids[i + 1] | input_ids[:i + 1]) for i = 0 .. n - 2
-        self.logprobs, self.want_prompt_logprobs = bool(logprobs), bool(prompt_logprobs)
-        self._lp, self._lp_n, self.prompt_logprobs = None, 0, None
+        # top_logprobs: N in 1 .. 20 (implies logprobs): also the N most likely alternatives at every emitted
+        #              token and the token's rank, from the same single launch; stats() gains ``top_logprobs`` and ``ranks``
+        self.top_logprobs = _top_logprobs_n(top_logprobs)
+        self.logprobs, self.want_prompt_logprobs = bool(logprobs) or self.top_logprobs > 0, bool(prompt_logprobs)
+        self._lp, self._lp_n, self.prompt_logprobs, self._top = None, 0, None, None
         # rebuild_every: N > 0 re-selects the retrieval cache's prefill chunks during every N-th target verify
         #                (SURVEY 8f row 4); 0 = the reference's behaviour, one build per prompt
         self.rebuild_every, self.rebuilds = int(rebuild_every), 0
@@ -542,7 +601,7 @@ class TriForceRunner:
         self.tokenizer, self.ge, self.eng = tokenizer, graph_engine, graph_engine.engine
         self.gamma, self.verbose = gamma, verbose
         if self.logprobs or self.want_prompt_logprobs:  # (refused before anything is captured or allocated)
-            refusal = self._extend_refusal("logprobs / prompt_logprobs")
+            refusal = self._extend_refusal("top_logprobs" if self.top_logprobs else "logprobs / prompt_logprobs")
             if refusal is not None:
                 raise NotImplementedError(refusal)
         if self.reanchor_at != 0:                      # (refused before anything is captured or allocated)
@@ -769,7 +828,13 @@ class TriForceRunner:
             if n:
                 grown[:n].copy_(self._lp[:n])
             self._lp = grown
-        ops.token_logprobs(logits[:k], list(ids), out=self._lp[n:n + k])
+        if self.top_logprobs:                          # the same single launch also lists the alternatives and the rank
+            if self._top is None:
+                self._top = _TopBuffers(self.device, self.top_logprobs, self._lp.numel())
+            self._top.reserve(n, n + k)
+            self._top.score(logits[:k], list(ids), n, self._lp)
+        else:
+            ops.token_logprobs(logits[:k], list(ids), out=self._lp[n:n + k])
         self._lp_n = n + k
 
     def _device_sets(self):
@@ -988,6 +1053,8 @@ class TriForceRunner:
         if self.logprobs:                              # the one device-to-host read of the values
             extra["logprobs"] = self._lp[:self._lp_n].tolist()
             assert len(extra["logprobs"]) == len(self.emitted)
+            if self.top_logprobs:
+                extra["top_logprobs"], extra["ranks"] = self._top.read(self._lp_n)
         if self.prompt_logprobs is not None:
             extra["prompt_logprobs"] = self.prompt_logprobs.float().cpu()
         look = self.bufs.lookahead
@@ -1009,15 +1076,17 @@ class TriForceRunner:
 def TriForce(tokenizer, graph_engine, input_ids, gamma=4, max_len=256, top_k=-1, top_p=0.9, temperature=0.6, verbose=False,
              file_path=None, dataset=None, spec_args=None, rng=None, return_details=False, rebuild_every=0, reanchor_at=0,
              logprobs=False, prompt_logprobs=False, min_p=0.0, repetition_penalty=1.0, frequency_penalty=0.0,
-             presence_penalty=0.0):
-    """``min_p`` > 0: min-p on the target tier.
+             presence_penalty=0.0, top_logprobs=0):
+    """``top_logprobs`` = N in 1 .. 20 (implies ``logprobs``): ``return_details`` also carries
+    ``top_logprobs`` — per emitted token the N most likely (id, logprob) pairs in order — and ``ranks``.
+    ``min_p`` > 0: min-p on the target tier.
     ``repetition_penalty`` / ``frequency_penalty`` / ``presence_penalty``: penalties on the target tier.
     ``logprobs`` / ``prompt_logprobs``: ``return_details`` then carries ``logprobs`` — a list aligned
     with ``tokens`` — and ``prompt_logprobs`` — an fp32 host tensor of n - 1 values."""
     run = TriForceRunner(tokenizer, graph_engine, gamma, top_k, top_p, temperature, verbose, rng,
                          rebuild_every=rebuild_every, reanchor_at=reanchor_at, logprobs=logprobs,
                          prompt_logprobs=prompt_logprobs, min_p=min_p, repetition_penalty=repetition_penalty,
-                         frequency_penalty=frequency_penalty, presence_penalty=presence_penalty)
+                         frequency_penalty=frequency_penalty, presence_penalty=presence_penalty, top_logprobs=top_logprobs)
     run.prefill(input_ids)
     eng, device = run.eng, run.device
     _sync(device)
@@ -1053,11 +1122,12 @@ class TriForceSession:
 
     def __init__(self, tokenizer, graph_engine, gamma=4, top_k=-1, top_p=0.9, temperature=0.6, verbose=False, rng=None,
                  rebuild_every=0, reanchor_at=0, logprobs=False, prompt_logprobs=False, min_p=0.0, repetition_penalty=1.0,
-                 frequency_penalty=0.0, presence_penalty=0.0):
+                 frequency_penalty=0.0, presence_penalty=0.0, top_logprobs=0):
         self.run = TriForceRunner(tokenizer, graph_engine, gamma, top_k, top_p, temperature, verbose, rng,
                                   rebuild_every=rebuild_every, reanchor_at=reanchor_at, logprobs=logprobs,
                                   prompt_logprobs=prompt_logprobs, min_p=min_p, repetition_penalty=repetition_penalty,
-                                  frequency_penalty=frequency_penalty, presence_penalty=presence_penalty)
+                                  frequency_penalty=frequency_penalty, presence_penalty=presence_penalty,
+                                  top_logprobs=top_logprobs)
         self.ttft = None
 
     @property
@@ -1198,7 +1268,9 @@ def sample_dist(probs, rng=None):
 class _DistEngine:
     """Presents a DistributedLlama through the GraphInferenceEngine surface the decode loops drive."""
 
-    def __init__(self, llm, logprobs=False, prompt_logprobs=False):
+    def __init__(self, llm, logprobs=False, prompt_logprobs=False, top_logprobs=0):
+        if _top_logprobs_n(top_logprobs):
+            raise NotImplementedError(TOP_LOGPROBS_REFUSAL.format("_DistEngine"))
         if logprobs or prompt_logprobs:                # (refused before anything is captured: DESIGN section 23)
             raise NotImplementedError("logprobs / prompt_logprobs are implemented for the single-GPU resident "
                                       "GraphInferenceEngine only, not for _DistEngine (tensor-parallel loop)")
@@ -1298,8 +1370,10 @@ class _DistEngine:
 
 @torch.inference_mode()
 def Baseline_Dist(tokenizer, graph_engine, input_ids, max_len=256, top_k=-1, top_p=0.9, temperature=0.6, verbose=False,
-                  local_rank=0, rng=None, logprobs=False):
+                  local_rank=0, rng=None, logprobs=False, top_logprobs=0):
     """Autoregressive TP baseline (reference decoding.py:243-287): returns (ms per token, generated ids)."""
+    if _top_logprobs_n(top_logprobs):
+        raise NotImplementedError(TOP_LOGPROBS_REFUSAL.format("Baseline_Dist"))
     if logprobs:
         raise NotImplementedError("logprobs is implemented for the single-GPU resident GraphInferenceEngine only, not for "
                                   "Baseline_Dist (tensor-parallel loop)")
@@ -1347,8 +1421,10 @@ def Middle_Spec_Dist(next_token, llm, gamma, verbose, tokenizer, rng=None):
 @torch.inference_mode()
 def TriForce_Dist(tokenizer, llm, input_ids, gamma=4, max_len=256, top_k=-1, top_p=0.9, temperature=0.6, verbose=False,
                   file_path=None, dataset=None, spec_args=None, rng=None, return_details=False, logprobs=False,
-                  prompt_logprobs=False):
+                  prompt_logprobs=False, top_logprobs=0):
     """Reference decoding.py:291-428: returns (avg accepted tokens, seconds per token)."""
+    if _top_logprobs_n(top_logprobs):                  # (refused before the engine wrapper or anything else is built)
+        raise NotImplementedError(TOP_LOGPROBS_REFUSAL.format("TriForce_Dist"))
     if logprobs or prompt_logprobs:                    # (refused before the engine wrapper or anything else is built)
         raise NotImplementedError("logprobs / prompt_logprobs are implemented for the single-GPU resident "
                                   "GraphInferenceEngine only, not for TriForce_Dist (tensor-parallel loop)")
