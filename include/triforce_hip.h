@@ -214,12 +214,20 @@ int tf_draft_persist_reset(void* ctl, void* host_mirror, int set_mirror);
  *                      a (+0, -0) pair is NOT a tie - it differs from IEEE equality there, and is
  *                      equally admissible against the reference's unspecified tie order.
  *                      2 <= C, 1 <= sets <= C (else TF_EINVAL); C <= 32768 (else TF_ERANGE).
+ * tf_retrieval_topk_large : the same arguments, output and ORDER for 2 <= C <= 1048576
+ *                      (TF_RETRIEVAL_TOPK_LARGE_MAX_CHUNKS) and sets - 1 <= 8192; above either bound
+ *                      TF_ERANGE, after the TF_EINVAL checks of tf_retrieval_topk.  One workgroup per
+ *                      head streams the row three times (radix select of the threshold pattern, ordered
+ *                      compaction, 64-bit sort of the winners: DESIGN section 34); no workspace.
+ *                      For C <= 32768 bit-identical to tf_retrieval_topk.
  * tf_retrieval_gather: dst slot j of head h <- chunk idx[h][j] (chunk rows of D), K and V
  *                      (cache.py:163-175).
  * ------------------------------------------------------------------------------------------- */
 int tf_retrieval_score(const void* k, int64_t stride_t, int64_t stride_h, const void* q,
                        void* scores, int C, int chunk, int H, int D, void* stream);
 int tf_retrieval_topk(const void* scores, int32_t* idx, int C, int sets, int H, void* stream);
+#define TF_RETRIEVAL_TOPK_LARGE_MAX_CHUNKS 1048576
+int tf_retrieval_topk_large(const void* scores, int32_t* idx, int C, int sets, int H, void* stream);
 int tf_retrieval_gather(const void* k_src, const void* v_src, int64_t src_stride_t, int64_t src_stride_h,
                         const int32_t* idx, void* k_dst, void* v_dst, int64_t dst_stride_t,
                         int64_t dst_stride_h, int sets, int chunk, int H, int D, void* stream);

@@ -245,6 +245,195 @@ __global__ __launch_bounds__(1024) void retrieval_topk_select_kernel(const uint1
     for (int i = tid; i < m; i += nt) out[1 + i] = 65535 - (int32_t)(sel[i] & 0xFFFFu);
 }
 
+// ---- per-head top-k above 32 768 chunks: streamed radix select, ordered compaction, 64-bit sort ----------------------
+// Neither the candidates (131 072 keys are 512 KiB) nor (score, chunk) in 32 bits fit any more, so nothing but the winners
+// is held: one 1024-thread workgroup per head streams its score row from global memory three times (the whole [H][C] fp16
+// array is a few MB and stays in L2 / Infinity Cache between the passes).
+//   steps     the row is walked in STEPS of at most 8 192 entries in ascending chunk order: step 0 is the unaligned head
+//             (chunks [1, a), scalar loads, one entry per lane), steps 1 .. nb the 16-byte-aligned body (one 16-byte load
+//             of 8 consecutive scores per lane), the last step the tail (< 8 entries, scalar loads).  Row h starts at byte
+//             2 h C: unaligned whenever C is not a multiple of 8.
+//   threshold radix select on the 16-bit sortable pattern alone: pass one histograms its high byte, pass two the low byte
+//             of the entries whose high byte matched; one private 256-bin LDS histogram per wave, folded after the pass
+//             (integer counts: deterministic).  Gives T, the pattern of the m-th best entry, and r, how many entries equal
+//             to T belong to the result.
+//   compact   every entry above T is a winner (slot from an LDS counter: the winners are sorted afterwards); an entry
+//             equal to T is one only while fewer than r of them were taken IN CHUNK ORDER: a workgroup-wide exclusive scan
+//             of the per-lane tie counts per step plus the running total of the steps before.  This is what keeps
+//             "ascending chunk among ties" exact when thousands of equal scores straddle the threshold.
+//   sort      the m <= 8 192 winners as 64-bit keys pattern << 32 | (0xFFFFFFFF - chunk), padding 0 (sorts last: a real
+//             key has a non-zero low word), bitonic, descending, in place.
+constexpr int RTL_THREADS = 1024, RTL_WAVES = RTL_THREADS / TF_WAVE, RTL_VEC = 8;
+
+struct RtlRow {                // how one head's row splits into steps
+    const uint16_t* sc;        // the row (chunk 0 first)
+    int a, nvec, t, C, nsteps; // body = chunks [a, t) in nvec vectors of 8; head [1, a), tail [t, C); nsteps = nb + 2
+};
+
+__device__ __forceinline__ RtlRow rtl_row(const uint16_t* sc, int C) {
+    RtlRow r;
+    r.sc = sc;
+    r.C = C;
+    const int to_aligned = (int)(((16u - (unsigned)((uintptr_t)(sc + 1) & 15u)) & 15u) >> 1);   // entries before a 16-byte bound
+    r.a = min(1 + to_aligned, C);
+    r.nvec = (C - r.a) / RTL_VEC;
+    r.t = r.a + r.nvec * RTL_VEC;
+    r.nsteps = (r.nvec + RTL_THREADS - 1) / RTL_THREADS + 2;
+    return r;
+}
+
+// The entries of this lane in step s: n sortable patterns p[0 .. n) of the consecutive chunks c0, c0 + 1, ...; lanes in
+// thread order hold ascending chunks.
+__device__ __forceinline__ void rtl_load(const RtlRow& r, int s, int tid, uint32_t (&p)[RTL_VEC], int& n, int& c0) {
+    n = 0;
+    if (s == 0 || s == r.nsteps - 1) {
+        c0 = (s == 0 ? 1 : r.t) + tid;
+        if (c0 < (s == 0 ? r.a : r.C)) {
+            p[0] = sortable_fp16(r.sc[c0]);
+            n = 1;
+        }
+        return;
+    }
+    const int v = (s - 1) * RTL_THREADS + tid;
+    c0 = r.a + v * RTL_VEC;
+    if (v < r.nvec) {
+        const uint4 w = *reinterpret_cast<const uint4*>(r.sc + c0);
+        const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            p[2 * j] = sortable_fp16(ws[j] & 0xFFFFu);
+            p[2 * j + 1] = sortable_fp16(ws[j] >> 16);
+        }
+        n = RTL_VEC;
+    }
+}
+
+__global__ __launch_bounds__(RTL_THREADS) void retrieval_topk_large_kernel(const uint16_t* __restrict__ scores,
+                                                                          int32_t* __restrict__ idx, int C, int sets,
+                                                                          int mpow2) {
+    extern __shared__ unsigned long long rtl_keys[];                     // [mpow2] the winners, then sorted in place
+    __shared__ int hist[RTL_WAVES][256];
+    __shared__ int wave_ties[RTL_WAVES];
+    __shared__ int s_digit, s_remaining, s_count;
+    const int h = blockIdx.x, tid = threadIdx.x, lane = tid & (TF_WAVE - 1), wave = tid / TF_WAVE;
+    const RtlRow row = rtl_row(scores + (int64_t)h * C, C);
+    const int m = sets - 1;
+    int32_t* out = idx + (int64_t)h * sets;
+    if (tid == 0) out[0] = 0;
+    if (m == 0) return;
+    for (int i = tid; i < mpow2; i += RTL_THREADS) rtl_keys[i] = 0ull;   // padding sorts last
+    if (tid == 0) { s_remaining = m; s_count = 0; }
+    uint32_t p[RTL_VEC];
+    int n, c0;
+
+    // ---- threshold: high byte, then low byte among the entries whose high byte matched ----
+    uint32_t hi = 0u;
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int i = tid; i < RTL_WAVES * 256; i += RTL_THREADS) (&hist[0][0])[i] = 0;
+        __syncthreads();
+#pragma unroll 1
+        for (int s = 0; s < row.nsteps; ++s) {
+            rtl_load(row, s, tid, p, n, c0);
+#pragma unroll
+            for (int j = 0; j < RTL_VEC; ++j)
+                if (j < n) {
+                    if (pass == 0) atomicAdd(&hist[wave][p[j] >> 8], 1);
+                    else if ((p[j] >> 8) == hi) atomicAdd(&hist[wave][p[j] & 255u], 1);
+                }
+        }
+        __syncthreads();
+        if (tid < 256) {                                                 // fold the waves' histograms into wave 0's
+            int sum = 0;
+#pragma unroll
+            for (int w = 0; w < RTL_WAVES; ++w) sum += hist[w][tid];
+            hist[0][tid] = sum;
+        }
+        __syncthreads();
+        if (tid == 0) {                                                  // digit of the remaining-th best entry
+            int rem = s_remaining, b = 255, cum = 0;
+            for (; b > 0; --b) {
+                if (cum + hist[0][b] >= rem) break;
+                cum += hist[0][b];
+            }
+            s_remaining = rem - cum;
+            s_digit = b;
+        }
+        __syncthreads();
+        if (pass == 0) hi = (uint32_t)s_digit;
+    }
+    const uint32_t T = (hi << 8) | (uint32_t)s_digit;                    // pattern of the m-th best entry
+    const int r = s_remaining;                                           // entries equal to T that belong to the result, >= 1
+
+    // ---- compaction, in ascending chunk order ----
+    int taken = 0;                                                       // ties seen in the steps before (uniform)
+#pragma unroll 1
+    for (int s = 0; s < row.nsteps; ++s) {
+        rtl_load(row, s, tid, p, n, c0);
+        int ties = 0;
+#pragma unroll
+        for (int j = 0; j < RTL_VEC; ++j)
+            if (j < n) {
+                if (p[j] > T) {
+                    const int slot = atomicAdd(&s_count, 1);
+                    if (slot < mpow2)
+                        rtl_keys[slot] = ((unsigned long long)p[j] << 32) | (0xFFFFFFFFu - (uint32_t)(c0 + j));
+                } else if (p[j] == T) {
+                    ++ties;
+                }
+            }
+        if (taken >= r) continue;                                        // (uniform) every tie of the result is taken
+        int inc = ties;
+#pragma unroll
+        for (int o = 1; o < TF_WAVE; o <<= 1) {
+            const int up = __shfl_up(inc, o, TF_WAVE);
+            if (lane >= o) inc += up;
+        }
+        __syncthreads();                                                 // (the step before has read wave_ties)
+        if (lane == TF_WAVE - 1) wave_ties[wave] = inc;
+        __syncthreads();
+        int rank = taken + inc - ties, total = 0;                        // ties in front of this lane's, in chunk order
+#pragma unroll
+        for (int w = 0; w < RTL_WAVES; ++w) {
+            const int t = wave_ties[w];
+            if (w < wave) rank += t;
+            total += t;
+        }
+        taken += total;
+        if (ties > 0 && rank < r) {
+#pragma unroll
+            for (int j = 0; j < RTL_VEC; ++j)
+                if (j < n && p[j] == T) {
+                    if (rank < r) {
+                        const int slot = atomicAdd(&s_count, 1);
+                        if (slot < mpow2)
+                            rtl_keys[slot] = ((unsigned long long)T << 32) | (0xFFFFFFFFu - (uint32_t)(c0 + j));
+                    }
+                    ++rank;
+                }
+        }
+    }
+    __syncthreads();
+
+    // ---- sort the winners, descending ----
+    for (int kk = 2; kk <= mpow2; kk <<= 1) {
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < mpow2; i += RTL_THREADS) {
+                const int ixj = i ^ j;
+                if (ixj > i) {
+                    const bool desc = ((i & kk) == 0);
+                    const unsigned long long a = rtl_keys[i], b = rtl_keys[ixj];
+                    if ((a < b) == desc) {
+                        rtl_keys[i] = b;
+                        rtl_keys[ixj] = a;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int i = tid; i < m; i += RTL_THREADS) out[1 + i] = (int32_t)(0xFFFFFFFFu - (uint32_t)rtl_keys[i]);
+}
+
 // ---- gather ---------------------------------------------------------------------------------
 // One 128-thread workgroup per (slot, head, K | V): a 2-KiB chunk, one 16-byte vector per thread.  In situ 24.9 us for the
 // 134 MB (67 read + 67 written) of a cfg2 layer = 5.4 TB/s.  A coarser form — one workgroup per 8 slots, all chunk ids
@@ -392,6 +581,27 @@ extern "C" int tf_retrieval_topk(const void* scores, int32_t* idx, int C, int se
     }
     hipLaunchKernelGGL(retrieval_topk_kernel, dim3(H), dim3(1024), pk.lds, (hipStream_t)stream,
                        (const uint16_t*)scores, idx, C, sets, pk.npow2);
+    TF_LAUNCH_CHECK();
+    return TF_OK;
+}
+
+// tf_retrieval_topk's contract, word for word, for 2 <= C <= 1 048 576 and sets - 1 <= 8 192 (retrieval_topk_large_kernel).
+static_assert(TF_RETRIEVAL_TOPK_LARGE_MAX_CHUNKS == RT_LARGE_MAX_CHUNKS, "header macro and launch rule disagree");
+extern "C" int tf_retrieval_topk_large(const void* scores, int32_t* idx, int C, int sets, int H, void* stream) {
+    if (!scores || !idx || C < 2 || sets < 1 || sets > C || H < 1) return TF_EINVAL;
+    if (C > RT_LARGE_MAX_CHUNKS || sets - 1 > RT_SELECT_MPOW2_MAX) return TF_ERANGE;
+    const RtTopkLargePick pk = rt_topk_large_pick(C, sets);   // retrieval_rule.h: the LDS, whether the attribute must be raised
+    if (pk.raise) {
+        static bool raised_large = false;
+        if (!raised_large) {
+            hipError_t e = hipFuncSetAttribute((const void*)retrieval_topk_large_kernel,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)pk.raise_to);
+            if (e != hipSuccess) return (int)e;
+            raised_large = true;
+        }
+    }
+    hipLaunchKernelGGL(retrieval_topk_large_kernel, dim3(H), dim3(RTL_THREADS), pk.lds, (hipStream_t)stream,
+                       (const uint16_t*)scores, idx, C, sets, pk.mpow2);
     TF_LAUNCH_CHECK();
     return TF_OK;
 }

@@ -37,6 +37,27 @@ inline RtTopkPick rt_topk_pick(int C, int sets) {
     return {RT_TOPK_FULL, lds, mpow2, npow2, lds > RT_FULL_LDS_PLAIN, RT_FULL_LDS_MAX};
 }
 
+// The large form (tf_retrieval_topk_large): only the winners are held, as 64-bit keys, so C does not enter the LDS size.
+constexpr int RT_LARGE_MAX_CHUNKS = 1 << 20;        // TF_RETRIEVAL_TOPK_LARGE_MAX_CHUNKS of the header
+constexpr size_t RT_LARGE_LDS_PLAIN = 48 * 1024;    // dynamic LDS above which the launch needs the raised attribute
+constexpr size_t RT_LARGE_LDS_MAX = (size_t)RT_SELECT_MPOW2_MAX * sizeof(uint64_t);   // 64 KiB (+ ~16 KiB static histograms)
+
+struct RtTopkLargePick {
+    size_t lds;          // dynamic LDS bytes of the launch: mpow2 64-bit keys
+    int mpow2;           // sets - 1 rounded up to a power of two, >= 2
+    bool raise;          // the launch needs hipFuncAttributeMaxDynamicSharedMemorySize raised (to raise_to) first
+    size_t raise_to;
+};
+
+// 2 <= C <= RT_LARGE_MAX_CHUNKS, 1 <= sets <= C and sets - 1 <= RT_SELECT_MPOW2_MAX are the caller's to check.
+inline RtTopkLargePick rt_topk_large_pick(int C, int sets) {
+    (void)C;
+    int mpow2 = 2;
+    while (mpow2 < sets - 1) mpow2 <<= 1;
+    const size_t lds = (size_t)mpow2 * sizeof(uint64_t);
+    return {lds, mpow2, lds > RT_LARGE_LDS_PLAIN, RT_LARGE_LDS_MAX};
+}
+
 // Workgroups along x for n chunk groups of work at H heads (the scorer, tf_chunk_mean, the indexed scorer): one 16-byte lane
 // per 8 d's, 256 / (D / 8) chunks per workgroup and trip, and 8 resident workgroups per CU and NOT ONE MORE: with
 // ceil(2048 / H) the 32 (H = 40) or 2 (H = 5) workgroups past 2 048 start when the others retire and stream their share

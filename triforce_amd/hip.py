@@ -32,6 +32,7 @@ SIGNATURES = {
     "tf_attn_rope_on_read": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _vp]),
     "tf_retrieval_score": (_i32, [_vp, _i64, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "tf_retrieval_topk": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "tf_retrieval_topk_large": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "tf_retrieval_gather": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
     "tf_chunk_mean": (_i32, [_vp, _i64, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "tf_retrieval_score_indexed": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp]),

@@ -385,6 +385,15 @@ class RetrievalCache(Cache):
         self.max_budget = max_budget
         assert prefill % self.chunk_size == 0, f"prefill should be multiple of chunk_size, got {prefill} % {self.chunk_size}"
         assert max_budget % self.chunk_size == 0, f"max_budget should be multiple of chunk_size, got {max_budget} % {self.chunk_size}"
+        # the top-k this cache was built for: tf_retrieval_topk up to TOPK_MAX_CHUNKS chunks, above that
+        # tf_retrieval_topk_large.  The limit is fixed here: a cache built below TOPK_MAX_CHUNKS does not grow past it
+        if self.chunks > ops.TOPK_LARGE_MAX_CHUNKS:
+            raise ValueError(f"prefill={prefill} is {self.chunks} chunks of {chunk_size} rows, more than the large top-k's "
+                             f"limit of {ops.TOPK_LARGE_MAX_CHUNKS} chunks")
+        if self.chunks > TOPK_MAX_CHUNKS and self.select_sets > ops.TOPK_LARGE_MAX_SETS:
+            raise ValueError(f"max_budget={max_budget} is {self.select_sets} chunks of {chunk_size} rows, more than the "
+                             f"{ops.TOPK_LARGE_MAX_SETS} the large top-k selects above {TOPK_MAX_CHUNKS} chunks")
+        self.topk_max_chunks = TOPK_MAX_CHUNKS if self.chunks <= TOPK_MAX_CHUNKS else ops.TOPK_LARGE_MAX_CHUNKS
         self.real_budget = max_budget + gamma + 1
         self.layers, self.num_heads, self.head_dim = _geom(model)
         self.hidden_size = model.config.hidden_size
@@ -436,9 +445,9 @@ class RetrievalCache(Cache):
             raise ValueError(f"new_prefill={new_prefill} is not a multiple of chunk_size={c}")
         if new_prefill < self.prefill0:
             raise ValueError(f"new_prefill={new_prefill} is below prefill0={self.prefill0}, the region the cache was built over")
-        if new_prefill // c > TOPK_MAX_CHUNKS:
+        if new_prefill // c > self.topk_max_chunks:
             raise ValueError(f"new_prefill={new_prefill} is {new_prefill // c} chunks of {c} rows, more than the top-k's limit "
-                             f"of {TOPK_MAX_CHUNKS} chunks")
+                             f"of {self.topk_max_chunks} chunks")
         self.prefill, self.chunks = new_prefill, new_prefill // c
         self._tail_plan = None                       # (it holds the tail's first row)
         self.indexed_chunks = [min(n, self.chunks) for n in self.indexed_chunks]
@@ -483,7 +492,10 @@ class RetrievalCache(Cache):
             scores = ops.retrieval_score_indexed(index, q[0].contiguous(), self.chunks)
         else:
             scores = ops.retrieval_score(src_k, q[0].contiguous(), self.chunks, self.chunk_size)
-        idx = ops.retrieval_topk(scores, self.select_sets)
+        if self.chunks <= TOPK_MAX_CHUNKS:
+            idx = ops.retrieval_topk(scores, self.select_sets)
+        else:                                         # (only a cache built above the limit gets here: topk_max_chunks)
+            idx = ops.retrieval_topk_large(scores, self.select_sets)
         if not self.fp8:
             ops.retrieval_gather(src_k, src_v, idx, self.k[layer_idx], self.v[layer_idx], self.chunk_size)
         elif kv_cache.fp8:                            # codes -> codes: the middle tier reads the deq the target reads

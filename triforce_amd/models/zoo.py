@@ -45,6 +45,11 @@ CONFIGS = {
                           model_type="qwen2",
                           rope_scaling=dict(type="yarn", factor=16.0, original_max_position_embeddings=256),
                           _name_or_path="tiny-yarn-gqa-bias-target"),
+    # "tiny-gqa-bias" with plain RoPE at theta 1e7 over 524 288 positions (the Qwen2.5-1M form at toy size): the small target
+    # whose prompts reach the retrieval top-k above 32 768 chunks
+    "tiny-512K": dict(hidden_size=512, intermediate_size=768, num_hidden_layers=2, num_attention_heads=4,
+                      num_key_value_heads=2, max_position_embeddings=524288, rms_norm_eps=1e-6, attention_bias=True,
+                      model_type="qwen2", rope_theta=1e7, _name_or_path="tiny-512k-gqa-bias-target"),
     # Qwen/Qwen2.5-7B-Instruct-1M shape (grouped-query 28 / 4 heads, q/k/v bias, plain RoPE with theta 1e7).  Written from
     # memory of the model card: there is no hub access offline, so these values are NOT checked against the published
     # config.json.  With g = 7 the decode attention stacks gs = 1 query head at 7 rows (ops.gqa_stack): K / V is read per

@@ -1406,6 +1406,22 @@ def retrieval_topk(scores, sets):
     return idx
 
 
+TOPK_LARGE_MAX_CHUNKS = 1048576                       # TF_RETRIEVAL_TOPK_LARGE_MAX_CHUNKS of include/triforce_hip.h
+TOPK_LARGE_MAX_SETS = 8193                            # chunk 0 + the 8 192 winners tf_retrieval_topk_large sorts, at most
+
+
+def retrieval_topk_large(scores, sets):
+    """retrieval_topk for (H, C) scores of up to TOPK_LARGE_MAX_CHUNKS chunks and sets <= TOPK_LARGE_MAX_SETS — the same
+    (H, sets) int32 output and order (tf_retrieval_topk_large); bit-identical to retrieval_topk where both
+    apply."""
+    _dev(scores)
+    H, C = scores.shape
+    assert scores.dtype == _HALF and scores.is_contiguous()
+    idx = torch.empty(H, sets, dtype=torch.int32, device=scores.device)
+    hip.check(hip.lib().tf_retrieval_topk_large(_ptr(scores), _ptr(idx), C, sets, H, _stream()), "tf_retrieval_topk_large")
+    return idx
+
+
 def retrieval_gather(k_src, v_src, idx, k_dst, v_dst, chunk):
     _dev(k_src, v_src, idx, k_dst, v_dst)
     H, _, D = k_src.shape

@@ -698,7 +698,6 @@ class TriForceRunner:
         re-anchors the retrieval cache to the chunk boundary below the last row fed, between the body rows and the last
         row's forward; and keep=k may lie below the covered region once that has grown (prefill0 <= k): the cache is
         re-anchored down to the chunk boundary below k first."""
-        from ..models.cache import TOPK_MAX_CHUNKS
         eng, ge, gamma = self.eng, self.ge, self.gamma
         refusal = self._extend_refusal()
         if refusal is not None:
@@ -735,9 +734,9 @@ class TriForceRunner:
                                  f"retrieval budget max_budget={rc.max_budget}: the covered region [0, {P}) is fixed when the "
                                  "engine is built")
             P_last = ((k + rows - 1) // chunk) * chunk
-            if P_last // chunk > TOPK_MAX_CHUNKS:
+            if P_last // chunk > rc.topk_max_chunks:
                 raise ValueError(f"{k} + {rows} rows need the retrieval cache to cover {P_last // chunk} chunks of {chunk} rows, "
-                                 f"more than the top-k's limit of {TOPK_MAX_CHUNKS} chunks")
+                                 f"more than the top-k's limit of {rc.topk_max_chunks} chunks")
         if k + rows + room > kv.max_budget:
             raise ValueError(f"{k} + {rows} rows + {room} rows for one decode step exceeds the full cache's capacity "
                              f"max_budget={kv.max_budget}")
