@@ -812,6 +812,12 @@ int tf_ar_inject_error(void* flags_local, int code);
  *   ws: tf_attn_decode_ws_floats(cols, gs * sq, D, nsplit) floats; split count: tf_attn_decode_pick_nsplit(cols, sk);
  *   tickets: cols zeroed words = one launch (left zero), NULL = two launches; both bit-identical.  sk_dev as in
  *   tf_attn_decode_act.  K / V fp16.
+ * tf_attn_decode_gqa_wide_act: tf_attn_decode_gqa_act for a wider stack: ALL g query heads of a KV head
+ *   are one problem of R = g * sq <= 64 stacked rows (stacked row r = query head j * g + r / sq, token r % sq of KV head j),
+ *   one workgroup column per KV head, so K / V is read from HBM once per KV head.  1 <= sq <= 32, g * sq <= 64 (else
+ *   TF_EINVAL).  ws: tf_attn_decode_ws_floats(Hkv, g * sq, D, nsplit) floats; split count: tf_attn_decode_pick_nsplit(Hkv, sk);
+ *   tickets: Hkv zeroed words = one launch for up to 8 splits (left zero), NULL = two launches; both bit-identical, and
+ *   bit-identical to tf_attn_decode_act on the repeated K / V for the same nsplit.  K / V fp16.
  * tf_attn_prefill_gqa: tf_attn_prefill (utils/graph_infer.py:30-37 -> models/modeling_llama.py:240 with q_len = the chunk),
  *   1 <= sq <= 4096; split count and workspace from tf_attn_prefill_pick_nsplit / _ws_floats with H = the QUERY heads.
  * tf_skinny_qkv_rope_gqa_act: tf_skinny_qkv_rope_act (models/modeling_llama.py:213-224: q / k / v projections + RoPE, then
@@ -823,6 +829,9 @@ int tf_ar_inject_error(void* flags_local, int code);
 int tf_attn_decode_gqa_act(const void* q, const void* k, const void* v, void* out, int64_t out_sm, int64_t out_sk,
                            int64_t stride_t, int64_t stride_h, int sq, int sk, const int32_t* sk_dev, int H, int Hkv, int D,
                            float scale, int nsplit, float* ws, int64_t ws_floats, uint32_t* tickets, void* stream);
+int tf_attn_decode_gqa_wide_act(const void* q, const void* k, const void* v, void* out, int64_t out_sm, int64_t out_sk,
+                                int64_t stride_t, int64_t stride_h, int sq, int sk, const int32_t* sk_dev, int H, int Hkv, int D,
+                                float scale, int nsplit, float* ws, int64_t ws_floats, uint32_t* tickets, void* stream);
 int tf_attn_prefill_gqa(const void* q, const void* k, const void* v, void* out, int64_t stride_t, int64_t stride_h,
                         int sq, int sk, int H, int Hkv, int D, float scale, int nsplit, float* ws, int64_t ws_floats,
                         void* stream);

@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
 """Decode attention of a grouped-query target against its two multi-head neighbours.
 
-At sq rows x sk keys, D = 128, four launches are timed with HIP events, alternating, after a warm-up of each:
+At sq rows x sk keys, D = 128, five launches are timed with HIP events, alternating, after a warm-up of each:
   (i)   tf_attn_decode_act, H = Hkv heads           — the same K/V bytes as (ii), 1/g of its query rows
   (ii)  tf_attn_decode_gqa_act, H query / Hkv KV heads
   (iii) tf_attn_decode_act, H heads                 — the multi-head launch of the same query rows, g times the bytes
   (iv)  tf_attn_decode_act, Hkv heads x gs * sq rows — (i)'s bytes with (ii)'s q-tile count and no stacking: what the second
         q-tile costs by itself
+  (v)   tf_attn_decode_gqa_wide_act, where g * sq <= 64: all g heads of a KV head as one stack — (i)'s bytes
+        where (ii) launches g / gs columns per KV head and reads g / gs times as much
 One JSON line per form: median / min / max microseconds per launch over the rounds, the K/V bytes the launch must read
 (2 * heads * sk * D * 2) and bytes / median time.  (ii) is also checked against (iii) on the repeated K/V (same bits).
 
     python tools/gqa_attn_bench.py --out profiles/gqa_decode_attention.jsonl
+    python tools/gqa_attn_bench.py --shape 28/4/7 --shape 64/8/7 --shape 28/4/9 --out profiles/gqa_wide_decode_attention.jsonl
 """
 import argparse
 import json
@@ -31,13 +34,20 @@ def main():
     ap.add_argument("--kv-heads", type=int, default=8)
     ap.add_argument("--launches", type=int, default=40, help="launches per timed batch")
     ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--shape", action="append", default=[], metavar="H/HKV/ROWS",
+                    help="query heads / KV heads / rows; repeatable, replaces --heads --kv-heads --rows")
     ap.add_argument("--out", default="profiles/gqa_decode_attention.jsonl")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("gqa_attn_bench needs a HIP device: a timing on anything else says nothing")
+    shapes = [tuple(int(x) for x in s.split("/")) for s in args.shape] or [(args.heads, args.kv_heads, args.rows)]
+    for H, Hkv, sq in shapes:
+        bench(args, H, Hkv, sq)
+
+
+def bench(args, H, Hkv, sq):
     from triforce_amd import ops
-    dev, D = "cuda:0", 128
-    sq, sk, H, Hkv = args.rows, args.keys, args.heads, args.kv_heads
+    dev, D, sk = "cuda:0", 128, args.keys
     g = H // Hkv
     gen = torch.Generator().manual_seed(1)
     q = torch.randn(sq, H, D, generator=gen).to(torch.float16).to(dev)
@@ -55,7 +65,12 @@ def main():
         "mha_kv_heads_stacked_row_count": (lambda: ops.attn_decode(q_tall, k, v, sk, scale), Hkv, Hkv,
                                            ops._pick_nsplit(Hkv, sk)),
     }
+    wide = g * sq <= ops.GQA_WIDE_MAX_ROWS
+    if wide:
+        forms["gqa_wide"] = (lambda: ops.attn_decode_gqa_wide(q, k, v, sk, scale), H, Hkv, ops._pick_nsplit(Hkv, sk))
     n = ops._pick_nsplit(Hkv * sub, sk)
+    wide_same = wide and torch.equal(ops.attn_decode_gqa_wide(q, k, v, sk, scale, nsplit=n),
+                                     ops.attn_decode(q, ke, ve, sk, scale, nsplit=n))
     same = torch.equal(ops.attn_decode_gqa(q, k, v, sk, scale, nsplit=n), ops.attn_decode(q, ke, ve, sk, scale, nsplit=n))
     for fn, *_ in forms.values():                                      # warm-up: code objects, allocator, tickets
         for _ in range(10):
@@ -78,11 +93,13 @@ def main():
             kv_bytes = 2 * kv_heads * sk * D * 2
             row = dict(what="decode attention, HIP events around batches of launches (includes the launch gaps)", form=name,
                        rows=sq, keys=sk, D=D, query_heads=heads, kv_heads=kv_heads, nsplit=nsplit,
-                       stacked_rows=gs * sq if name in ("gqa", "mha_kv_heads_stacked_row_count") else sq,
+                       stacked_rows={"gqa_wide": g * sq, "gqa": gs * sq, "mha_kv_heads_stacked_row_count": gs * sq}.get(name, sq),
+                       kv_passes=sub if name == "gqa" else 1,
                        launches_per_batch=args.launches, rounds=args.rounds,
                        us_median=round(us, 2), us_min=round(min(times[name]), 2), us_max=round(max(times[name]), 2),
                        kv_bytes=kv_bytes, tb_per_s=round(kv_bytes / us * 1e-6, 3),
-                       gqa_bits_equal_mha_on_repeated_kv=same, device=torch.cuda.get_device_name(0))
+                       gqa_bits_equal_mha_on_repeated_kv=same,
+                       gqa_wide_bits_equal_mha_on_repeated_kv=wide_same if wide else None, device=torch.cuda.get_device_name(0))
             line = json.dumps(row)
             print(line, flush=True)
             f.write(line + "\n")

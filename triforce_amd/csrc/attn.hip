@@ -803,6 +803,255 @@ __global__ __launch_bounds__(256, QT == 2 ? ATTN_QT2_OCC : 1) void attn_split_gq
                                                ws, tickets, out, osm, osk, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 0, gs, g_kv);
 }
 
+// ---- the WIDE grouped-query form (tf_attn_decode_gqa_wide_act) ---------------------------------------------
+// All g query heads of a KV head are ONE problem of R = g * sq <= 64 stacked rows (stacked row r = query head hkv * g + r / sq,
+// token r % sq), so K / V is read from HBM once per KV head where the stacked kernel above launches g / gs columns that each
+// stream it again.  Four q-tiles do not fit one wave's registers (two sit at 248 VGPRs), so the rows are split over waves:
+//   * a workgroup = 8 waves = 4 key STREAMS x 2 ROW HALVES.  Stream s takes the key tiles t_begin + s, + 4, ... exactly as
+//     wave s of attn_split_body does; row half r owns q-tiles 2 r and 2 r + 1 and carries AttnState<D, 2> — the register state
+//     of the two-q-tile form, at the 2 waves per SIMD a 512-thread workgroup implies.
+//   * the two waves of a stream share ONE HBM read of each tile: the wave of row half 0 fetches the tile's 16 K rows, the wave
+//     of row half 1 its 16 V rows (full 256-byte rows, the load_kv_rows pattern), into a staging tile that belongs to the stream
+//     pair.  Both waves then read the fragments rows_to_frags would have given them and run attn_tile<D, 2, ..., GQA>.
+//   * the staging tile is double-buffered and a wave holds two more tiles' rows in registers: while tile i is multiplied, tile
+//     i + 1 goes registers -> LDS and tiles i + 2, i + 3 are in flight (4 KiB per wave, 32 KiB per CU).  One workgroup barrier
+//     per tile orders "written" before "read" and "read" before "overwritten"; every wave runs the same number of steps
+//     (a stream without a tile in its last step skips the arithmetic, not the barrier), and every load is unconditional
+//     (past the last tile it re-reads it) so the waitcnt pass keeps the younger tile in flight.
+// A row's arithmetic is the multi-head kernel's: the same tile body, the same tile -> stream assignment, the same merge of the
+// four streams in stream order, the same split merge — the output bits equal tf_attn_decode_act's on the repeated K / V for
+// the same nsplit.  ws layout: attn_split_body's with Hkv columns and QR = 16 * ceil(R / 16) rows.
+template <int D>
+__device__ __forceinline__ void wide_load_rows(const h16* __restrict__ base, int64_t stride_t, int tile, int sk, int lane,
+                                               half8 (&r)[D / 32]) {
+    constexpr int LPR = D / 8, RPI = 64 / LPR;
+    const int rl = lane / LPR, q = lane % LPR;
+#pragma unroll
+    for (int j = 0; j < D / 32; ++j) {
+        int key = tile * 16 + RPI * j + rl;
+        key = key < sk ? key : sk - 1;                 // clamp: masked below, but must stay in-bounds
+        r[j] = load_half8_stream(base + (int64_t)key * stride_t + 8 * q);
+    }
+}
+// dst: this wave's [16][D + 8] half of a staging buffer (K rows or V rows)
+template <int D>
+__device__ __forceinline__ void wide_store_rows(const half8 (&r)[D / 32], h16* dst, int lane) {
+    constexpr int LPR = D / 8, RPI = 64 / LPR, LDR = D + 8;
+    const int rl = lane / LPR, q = lane % LPR;
+#pragma unroll
+    for (int j = 0; j < D / 32; ++j) *reinterpret_cast<half8*>(dst + (RPI * j + rl) * LDR + 8 * q) = r[j];
+}
+// buf: one staging buffer [K | V][16][D + 8]; the fragment reads of rows_to_frags
+template <int D>
+__device__ __forceinline__ void wide_read_frags(const h16* buf, int li, int g, half8 (&kf)[D / 32], half8 (&vf)[D / 32]) {
+    constexpr int LDR = D + 8;
+#pragma unroll
+    for (int c = 0; c < D / 32; ++c) {
+        kf[c] = *reinterpret_cast<const half8*>(buf + li * LDR + 32 * c + 8 * g);
+        vf[c] = *reinterpret_cast<const half8*>(buf + (16 + li) * LDR + 32 * c + 8 * g);
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(512) void attn_split_gqa_wide_kernel(
+    const h16* __restrict__ q, const h16* __restrict__ k, const h16* __restrict__ v, const int32_t* __restrict__ sk_dev,
+    int sq, int sk_host, int H, int nsplit, int stride_t, int stride_h, float scale,      // <- 14 dwords preloaded into SGPRs
+    float* __restrict__ ws, unsigned* __restrict__ tickets, h16* __restrict__ out, int64_t osm, int64_t osk, int g_kv) {
+    constexpr int NC = D / 32, NT = D / 16, QT = 2, LDR = D + 8;
+    constexpr int NS = 4, NH = 2, NWW = NS * NH;       // key streams, row halves, waves
+    const int split = blockIdx.x, hkv = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int strm = wave & (NS - 1), rh = wave / NS;
+    const int li = lane & 15, g = lane >> 4;
+    int sk = sk_dev ? *sk_dev : sk_host;
+    if (sk > sk_host) sk = sk_host;
+    if (sk < 1) sk = 1;
+
+    const int ntiles = (sk + 15) >> 4;
+    const int tps = (ntiles + nsplit - 1) / nsplit;
+    const int t_begin = split * tps;
+    const int t_end = min(ntiles, t_begin + tps);
+
+    const int rows = g_kv * sq;                        // stacked rows of this KV head
+    const int QR = ((rows + 15) >> 4) << 4;            // rows of the workspace layout
+    AttnState<D, QT> st;
+    int qtok[QT];                                      // token index of this lane's row per q-tile (padding rows: a valid one)
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) {
+        const int row = (QT * rh + qt) * 16 + li;
+        qtok[qt] = row % sq;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            half8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+            st.qf[qt][c] = (row < rows) ? load_half8(q + ((int64_t)qtok[qt] * H + hkv * g_kv + row / sq) * D + 32 * c + 8 * g) : z;
+        }
+#pragma unroll
+        for (int t = 0; t < NT; ++t) st.acc[qt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        st.m[qt] = NEG_BIG;
+        st.l[qt] = 0.f;
+    }
+    half8 sel0, sel1;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        sel0[e] = (8 * g + e == li) ? (h16)1.0f : (h16)0.0f;
+        sel1[e] = (8 * g + e == 16 + li) ? (h16)1.0f : (h16)0.0f;
+    }
+
+    // One block of LDS: the stream pairs' staging buffers, then — behind a barrier — the merge of the waves' partial results
+    constexpr size_t BUF = (size_t)2 * 16 * LDR;       // halves of one staging buffer [K | V][16][LDR]
+    constexpr size_t STAGE_BYTES = (size_t)NS * 2 * BUF * sizeof(h16);
+    constexpr size_t MERGE_BYTES = sizeof(float) * ((size_t)NWW * 16 * (D + 1) + 2 * NWW * 16);
+    __shared__ __attribute__((aligned(16))) unsigned char sm_raw[MERGE_BYTES > STAGE_BYTES ? MERGE_BYTES : STAGE_BYTES];
+    h16* buf0 = reinterpret_cast<h16*>(sm_raw) + (size_t)strm * 2 * BUF;
+    h16* buf1 = buf0 + BUF;
+    // the rows this wave fetches: K (row half 0) or V (row half 1) of the stream's tile, and where they go in a buffer
+    const h16* src = (rh == 0 ? k : v) + (int64_t)hkv * stride_h;
+    const int mine = rh * 16 * LDR;
+
+    const int n_it = t_begin < t_end ? (t_end - t_begin + NS - 1) / NS : 0;    // steps of EVERY wave of the workgroup
+    if (n_it > 0) {
+        const int tl = t_end - 1;
+        int t = t_begin + strm;
+        half8 ra[NC], rb[NC];
+        wide_load_rows<D>(src, stride_t, min(t, tl), sk, lane, ra);
+        wide_store_rows<D>(ra, buf0 + mine, lane);
+        wide_load_rows<D>(src, stride_t, min(t + NS, tl), sk, lane, ra);
+        wide_load_rows<D>(src, stride_t, min(t + 2 * NS, tl), sk, lane, rb);
+        __syncthreads();
+        // one step: fragments of tile T from CUR; the rows in R (tile T + NS) to NXT; R refilled with tile T + 3 NS; the
+        // tile's arithmetic (the "fully visible" shortcut keeps the TOKEN count, as in attn_split_body's GQA form); barrier
+#define WIDE_STEP(CUR, NXT, R, T)                                                                                            \
+    do {                                                                                                                     \
+        half8 kf_[NC], vf_[NC];                                                                                              \
+        wide_read_frags<D>(CUR, li, g, kf_, vf_);                                                                            \
+        wide_store_rows<D>(R, NXT + mine, lane);                                                                             \
+        wide_load_rows<D>(src, stride_t, min((T) + 3 * NS, tl), sk, lane, R);                                                \
+        if ((T) < t_end) {                                                                                                   \
+            if ((T) * 16 + 15 <= sk - sq) attn_tile<D, QT, false, false>(st, kf_, vf_, sel0, sel1, (T), sk, sq, scale, li, g); \
+            else attn_tile<D, QT, false, true, true>(st, kf_, vf_, sel0, sel1, (T), sk, sq, scale, li, g, 0,               \
+                                                     TreeMask{nullptr, 0, 0, 0}, qtok);                                     \
+        }                                                                                                                    \
+        __syncthreads();                                                                                                     \
+    } while (0)
+        // (pairs of steps, then the odd one: with a `break` between the two steps the loop header gains an edge on which
+        // ra is the YOUNGEST load, and the waitcnt pass then drains rb's loads too in front of every store of ra)
+        for (int it = 0; it + 1 < n_it; it += 2) {
+            WIDE_STEP(buf0, buf1, ra, t);
+            WIDE_STEP(buf1, buf0, rb, t + NS);
+            t += 2 * NS;
+        }
+        if (n_it & 1) WIDE_STEP(buf0, buf1, ra, t);
+#undef WIDE_STEP
+    }
+
+    // ---- merge the four streams of each row half through LDS, one q-tile per row half at a time: attn_split_body's merge
+    // of its four waves, stream s in the place of wave s ----
+    float (*sm_o)[16][D + 1] = reinterpret_cast<float (*)[16][D + 1]>(sm_raw);
+    float (*sm_m)[16] = reinterpret_cast<float (*)[16]>(sm_raw + sizeof(float) * (size_t)NWW * 16 * (D + 1));
+    float (*sm_l)[16] = sm_m + NWW;
+    const int Hkv = gridDim.y;
+    float* ws_o = ws;
+    float* ws_m = ws + (int64_t)Hkv * nsplit * QR * D;
+    float* ws_l = ws_m + (int64_t)Hkv * nsplit * QR;
+    const int64_t pbase = ((int64_t)hkv * nsplit + split) * QR;
+    const int w0 = rh * NS;                            // the four waves of this thread's row half
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) {
+        float lsum = st.l[qt];
+        lsum += __shfl_xor(lsum, 16, 64);
+        lsum += __shfl_xor(lsum, 32, 64);
+#pragma unroll
+        for (int tt = 0; tt < NT; ++tt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sm_o[wave][li][16 * tt + 4 * g + r] = st.acc[qt][tt][r];
+        if (g == 0) {
+            sm_m[wave][li] = st.m[qt];
+            sm_l[wave][li] = lsum;
+        }
+        __syncthreads();
+        const int row0 = (QT * rh + qt) * 16;          // first stacked row of this q-tile (rows past QR have no workspace)
+        for (int e = tid & 255; e < 16 * D && row0 < QR; e += 256) {
+            const int qq = e / D, d = e - qq * D;
+            float mm = sm_m[w0][qq];
+#pragma unroll
+            for (int w = 1; w < NS; ++w) mm = fmaxf(mm, sm_m[w0 + w][qq]);
+            // sum over the streams in stream order: ((a0 w0 + a1 w1) + a2 w2) + a3 w3
+            float o = 0.f, lw = 0.f;
+#pragma unroll
+            for (int w = 0; w < NS; ++w) {
+                const float ww = __expf(sm_m[w0 + w][qq] - mm);
+                o = (w == 0) ? sm_o[w0 + w][qq][d] * ww : o + sm_o[w0 + w][qq][d] * ww;
+                lw = (w == 0) ? sm_l[w0 + w][qq] * ww : lw + sm_l[w0 + w][qq] * ww;
+            }
+            if (tickets == nullptr) {
+                ws_o[(pbase + row0 + qq) * D + d] = o;
+                if (d == 0) {
+                    ws_m[pbase + row0 + qq] = mm;
+                    ws_l[pbase + row0 + qq] = lw;
+                }
+            } else {                                   // one-launch form: write-through (sc1) stores
+                st_agent(&ws_o[(pbase + row0 + qq) * D + d], o);
+                if (d == 0) {
+                    st_agent(&ws_m[pbase + row0 + qq], mm);
+                    st_agent(&ws_l[pbase + row0 + qq], lw);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (tickets == nullptr) return;                    // two-launch form: attn_combine_gqa_kernel merges the splits
+
+    // ---- fused merge (<= FUSED_MERGE_MAX_SPLITS splits): attn_split_body's — own stores drained, ticket, and the last
+    // workgroup of the KV head folds the partials with each split its own chain of attn_combine_kernel ----
+    __shared__ int s_last;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0)
+        s_last = __hip_atomic_fetch_add(&tickets[hkv], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(nsplit - 1);
+    __syncthreads();
+    if (!s_last) return;
+    const int64_t hbase = (int64_t)hkv * nsplit * QR;
+    for (int e = tid; e < rows * (D / 4); e += 64 * NWW) {
+        const int r = e / (D / 4), d4 = e - r * (D / 4);
+        float pm[FUSED_MERGE_MAX_SPLITS], pl[FUSED_MERGE_MAX_SPLITS];
+        f32x4 px[FUSED_MERGE_MAX_SPLITS];
+#pragma unroll
+        for (int s = 0; s < FUSED_MERGE_MAX_SPLITS; ++s) {
+            if (s < nsplit) {
+                const float* xp = ws_o + (hbase + (int64_t)s * QR + r) * D + 4 * d4;
+                px[s] = f32x4{ld_agent(xp), ld_agent(xp + 1), ld_agent(xp + 2), ld_agent(xp + 3)};
+                pm[s] = ld_agent(&ws_m[hbase + (int64_t)s * QR + r]);
+                pl[s] = ld_agent(&ws_l[hbase + (int64_t)s * QR + r]);
+            } else {
+                px[s] = f32x4{0.f, 0.f, 0.f, 0.f};
+                pm[s] = NEG_BIG;
+                pl[s] = 0.f;
+            }
+        }
+        float mm = NEG_BIG;
+#pragma unroll
+        for (int s = 0; s < FUSED_MERGE_MAX_SPLITS; ++s) mm = fmaxf(mm, pm[s]);
+        float l = 0.f;
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < FUSED_MERGE_MAX_SPLITS; ++s) {
+            float w = 0.f;
+            if (s < nsplit) {
+                w = __expf(pm[s] - mm);
+                l += pl[s] * w;
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) acc[c] += fmaf(px[s][c], w, 0.f);
+        }
+        half4 o4;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) o4[c] = (h16)(acc[c] / l);
+        const int hq = hkv * g_kv + r / sq;            // stacked row r -> (token r % sq, query head hkv * g + r / sq)
+        *reinterpret_cast<half4*>(out + (int64_t)(r % sq) * osm + (int64_t)((hq * D + 4 * d4) >> 3) * osk + ((4 * d4) & 7)) = o4;
+    }
+    if (tid == 0) __hip_atomic_store(&tickets[hkv], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // left zero for the next launch
+}
+
 // The FP8-KV form (tf_attn_decode_fp8_act): k / v are code pointers, ke / ve the exponent bytes.  The one-q-tile form keeps the
 // fp16 kernel's bounds, the two-q-tile form its ATTN_QT2_OCC waves per SIMD.
 template <int QT>
@@ -2176,6 +2425,47 @@ extern "C" int tf_attn_decode_gqa_act(const void* q, const void* k, const void* 
     if (D == 64 && QT == 2) GQA_LAUNCH(64, 2);
 #undef GQA_LAUNCH
     return TF_EINVAL;
+}
+
+// tf_attn_decode_gqa_act for a wider stack: all g = H / Hkv query heads of a KV head are one problem of
+// R = g * sq <= 64 stacked rows, grid (nsplit, Hkv) — K / V is read once per KV head.  Workspace and split count:
+// tf_attn_decode_ws_floats(Hkv, R, D, nsplit), tf_attn_decode_pick_nsplit(Hkv, sk).  tickets: Hkv zeroed words (NULL: two
+// launches); every call leaves them zero.  More than FUSED_MERGE_MAX_SPLITS splits always take the two-launch merge.
+template <int D>
+static int launch_attn_gqa_wide(const void* q, const void* k, const void* v, void* out, int64_t osm, int64_t osk, int64_t stride_t,
+                                int64_t stride_h, int sq, int sk, const int32_t* sk_dev, int H, int Hkv, float scale, int nsplit,
+                                float* ws, unsigned* tickets, hipStream_t st) {
+    const int g = H / Hkv, R = g * sq;
+    dim3 grid(nsplit, Hkv), block(512);
+    if (tickets && nsplit > FUSED_MERGE_MAX_SPLITS) tickets = nullptr;      // many splits: the parallel merge kernel
+    hipLaunchKernelGGL((attn_split_gqa_wide_kernel<D>), grid, block, 0, st, (const h16*)q, (const h16*)k, (const h16*)v, sk_dev,
+                       sq, sk, H, nsplit, (int)stride_t, (int)stride_h, scale, ws, tickets, (h16*)out, osm, osk, g);
+    TF_LAUNCH_CHECK();
+    if (tickets) return TF_OK;
+    hipLaunchKernelGGL((attn_combine_gqa_kernel<D>), dim3(Hkv, R), dim3(D, COMBINE_GROUPS), 0, st, (const float*)ws, (h16*)out,
+                       sq, Hkv, nsplit, ((R + 15) / 16) * 16, osm, osk, g);
+    TF_LAUNCH_CHECK();
+    return TF_OK;
+}
+
+extern "C" int tf_attn_decode_gqa_wide_act(const void* q, const void* k, const void* v, void* out, int64_t out_sm, int64_t out_sk,
+                                           int64_t stride_t, int64_t stride_h, int sq, int sk, const int32_t* sk_dev, int H,
+                                           int Hkv, int D, float scale, int nsplit, float* ws, int64_t ws_floats,
+                                           uint32_t* tickets, void* stream) {
+    if (!q || !k || !v || !out || !ws) return TF_EINVAL;
+    if (sq < 1 || sq > 32 || sk < 1 || H < 1 || Hkv < 1 || (H % Hkv) || nsplit < 1 || nsplit > COMBINE_MAX_SPLITS) return TF_EINVAL;
+    if ((int64_t)(H / Hkv) * sq > 64) return TF_EINVAL;               // four q-tiles
+    if (D != 128 && D != 64) return TF_EINVAL;
+    if ((stride_t % 8) || (stride_h % 8)) return TF_EINVAL;          // 16-B loads
+    if (stride_t > 0x7fffffff || stride_h > 0x7fffffff) return TF_EINVAL;   // (the kernel takes the two strides as 32-bit arguments)
+    if (out_sm < 8 || out_sk < 8 || (out_sm % 4) || (out_sk % 4)) return TF_EINVAL;   // 8-byte output stores
+    if (ws_floats < tf_attn_decode_ws_floats(Hkv, (H / Hkv) * sq, D, nsplit)) return TF_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    if (D == 128)
+        return launch_attn_gqa_wide<128>(q, k, v, out, out_sm, out_sk, stride_t, stride_h, sq, sk, sk_dev, H, Hkv, scale, nsplit, ws,
+                                         tickets, st);
+    return launch_attn_gqa_wide<64>(q, k, v, out, out_sm, out_sk, stride_t, stride_h, sq, sk, sk_dev, H, Hkv, scale, nsplit, ws,
+                                    tickets, st);
 }
 
 // FP8 KV cache (include/triforce_hip.h): the same split / merge as tf_attn_decode_act (bit-identical to it on the

@@ -52,8 +52,8 @@ CONFIGS = {
                       model_type="qwen2", rope_theta=1e7, _name_or_path="tiny-512k-gqa-bias-target"),
     # Qwen/Qwen2.5-7B-Instruct-1M shape (grouped-query 28 / 4 heads, q/k/v bias, plain RoPE with theta 1e7).  Written from
     # memory of the model card: there is no hub access offline, so these values are NOT checked against the published
-    # config.json.  With g = 7 the decode attention stacks gs = 1 query head at 7 rows (ops.gqa_stack): K / V is read per
-    # query head (known limit)
+    # config.json.  With g = 7 a 7-row verify is 49 stacked rows: the wide grouped-query decode attention
+    # (ops.gqa_wide_applies, tf_attn_decode_gqa_wide_act) reads K / V once per KV head
     "qwen2.5-7B-1M": dict(vocab_size=152064, hidden_size=3584, intermediate_size=18944, num_hidden_layers=28,
                           num_attention_heads=28, num_key_value_heads=4, max_position_embeddings=1010000, rms_norm_eps=1e-6,
                           rope_theta=1e7, attention_bias=True, model_type="qwen2", bos_token_id=151643, eos_token_id=151645,

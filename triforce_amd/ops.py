@@ -104,6 +104,16 @@ def gqa_stack(g, sq):
     return gs, g // gs
 
 
+GQA_WIDE_MAX_ROWS = 64           # stacked rows of tf_attn_decode_gqa_wide_act: four q-tiles
+
+
+def gqa_wide_applies(g, sq):
+    """Launch rule of the wide grouped-query decode attention (tf_attn_decode_gqa_wide_act): the shapes at
+    which the stacked kernel needs more than one workgroup column per KV head — each column streams K / V again — while all
+    g * sq rows fit the wide kernel's 64."""
+    return gqa_stack(g, sq)[1] > 1 and g * sq <= GQA_WIDE_MAX_ROWS
+
+
 def group_mean_query(q, Hkv):
     """q̄ of the grouped-query retrieval selection: q (H, D) fp16 -> (Hkv, D) fp16, the fp32 mean over
     the H / Hkv query heads of each KV head rounded to fp16.  H == Hkv: q itself, bit for bit."""
@@ -827,8 +837,11 @@ def attn_decode(q, k_layer, v_layer, sk, scale, sk_dev=None, nsplit=None, packed
     q (sq,H,D); returns (sq, H*D) fp16 — a row-major tensor, or with ``packed`` an Act (what o_proj then reads)."""
     _dev(q, k_layer, v_layer, sk_dev)
     sq, H, D = q.shape
-    if k_layer.shape[0] != H:                          # fewer KV heads than query heads: the grouped-query kernel
-        return attn_decode_gqa(q, k_layer, v_layer, sk, scale, sk_dev=sk_dev, nsplit=nsplit, packed=packed)
+    if k_layer.shape[0] != H:                          # fewer KV heads than query heads: the grouped-query kernels
+        Hkv = k_layer.shape[0]
+        wide = GQA_WIDE and Hkv >= 1 and H % Hkv == 0 and sq <= SKINNY_MAX_ROWS and gqa_wide_applies(H // Hkv, sq)
+        return (attn_decode_gqa_wide if wide else attn_decode_gqa)(q, k_layer, v_layer, sk, scale, sk_dev=sk_dev, nsplit=nsplit,
+                                                                   packed=packed)
     assert q.dtype == _HALF and q.is_contiguous()
     st, sh = _kv(k_layer)
     assert _kv(v_layer) == (st, sh)
@@ -886,6 +899,38 @@ def attn_decode_gqa(q, k_layer, v_layer, sk, scale, sk_dev=None, nsplit=None, pa
     hip.check(hip.lib().tf_attn_decode_gqa_act(_ptr(q), _ptr(k_layer), _ptr(v_layer), op, osm, osk, st, sh, sq, int(sk),
                                                _ptr(sk_dev), H, Hkv, D, float(scale), nsplit, _ptr(ws), ws.numel(),
                                                _ptr(tickets), stream), "tf_attn_decode_gqa_act")
+    return out
+
+
+# TRIFORCE_GQA_WIDE=0: attn_decode never takes the wide kernel (every launch is tf_attn_decode_gqa_act's)
+GQA_WIDE = _os.environ.get("TRIFORCE_GQA_WIDE", "1") != "0"
+
+
+def attn_decode_gqa_wide(q, k_layer, v_layer, sk, scale, sk_dev=None, nsplit=None, packed=False, fused_merge=None, out=None):
+    """attn_decode_gqa with ALL g = H / Hkv query heads of a KV head stacked into one problem of g * sq <= 64 rows
+    (tf_attn_decode_gqa_wide_act): one workgroup column per KV head, K / V streamed once per KV head.
+    Arguments as attn_decode_gqa; the default split count is that of Hkv columns."""
+    _dev(q, k_layer, v_layer, sk_dev)
+    sq, H, D = q.shape
+    Hkv = k_layer.shape[0]
+    assert q.dtype == _HALF and q.is_contiguous() and v_layer.shape[0] == Hkv
+    if Hkv < 1 or H % Hkv or sq > SKINNY_MAX_ROWS or (H // Hkv) * sq > GQA_WIDE_MAX_ROWS:
+        raise hip.TriforceHipError(f"attn_decode_gqa_wide: {H} query heads over {Hkv} KV heads, {sq} rows")
+    st, sh = _kv(k_layer)
+    assert _kv(v_layer) == (st, sh)
+    if nsplit is None:
+        nsplit = _pick_nsplit(Hkv, int(sk))
+    ws = _workspace(q.device, _ws_floats(Hkv, (H // Hkv) * sq, D, nsplit))
+    if out is None:
+        out = Act.empty(sq, H * D, q.device) if packed else torch.empty(sq, H * D, dtype=_HALF, device=q.device)
+    assert tuple(out.shape) == (sq, H * D)
+    op, osm, osk = _lay(out)
+    stream = _stream()
+    fused = ATTN_FUSED_MERGE if fused_merge is None else fused_merge
+    tickets = _ticket_row(q.device, stream.value or 0) if fused and Hkv <= _TICKET_WORDS else None
+    hip.check(hip.lib().tf_attn_decode_gqa_wide_act(_ptr(q), _ptr(k_layer), _ptr(v_layer), op, osm, osk, st, sh, sq, int(sk),
+                                                    _ptr(sk_dev), H, Hkv, D, float(scale), nsplit, _ptr(ws), ws.numel(),
+                                                    _ptr(tickets), stream), "tf_attn_decode_gqa_wide_act")
     return out
 
 
