@@ -818,6 +818,11 @@ int tf_ar_inject_error(void* flags_local, int code);
  *   TF_EINVAL).  ws: tf_attn_decode_ws_floats(Hkv, g * sq, D, nsplit) floats; split count: tf_attn_decode_pick_nsplit(Hkv, sk);
  *   tickets: Hkv zeroed words = one launch for up to 8 splits (left zero), NULL = two launches; both bit-identical, and
  *   bit-identical to tf_attn_decode_act on the repeated K / V for the same nsplit.  K / V fp16.
+ * tf_attn_decode_gqa_wide128_act: the same call for R = g * sq <= 128 stacked rows, still one workgroup
+ *   column per KV head and one HBM read of K / V per KV head; R <= 64 is accepted.  Workspace, split count, tickets and merge
+ *   forms as tf_attn_decode_gqa_wide_act.  A workgroup runs two key streams where tf_attn_decode_act runs four, so the output
+ *   is NOT bit-identical to tf_attn_decode_act's: it is deterministic, the one- and two-launch merges are bit-identical to
+ *   each other for the same nsplit, and it is within the decode bounds of an exact evaluation.  K / V fp16.
  * tf_attn_prefill_gqa: tf_attn_prefill (utils/graph_infer.py:30-37 -> models/modeling_llama.py:240 with q_len = the chunk),
  *   1 <= sq <= 4096; split count and workspace from tf_attn_prefill_pick_nsplit / _ws_floats with H = the QUERY heads.
  * tf_skinny_qkv_rope_gqa_act: tf_skinny_qkv_rope_act (models/modeling_llama.py:213-224: q / k / v projections + RoPE, then
@@ -832,6 +837,9 @@ int tf_attn_decode_gqa_act(const void* q, const void* k, const void* v, void* ou
 int tf_attn_decode_gqa_wide_act(const void* q, const void* k, const void* v, void* out, int64_t out_sm, int64_t out_sk,
                                 int64_t stride_t, int64_t stride_h, int sq, int sk, const int32_t* sk_dev, int H, int Hkv, int D,
                                 float scale, int nsplit, float* ws, int64_t ws_floats, uint32_t* tickets, void* stream);
+int tf_attn_decode_gqa_wide128_act(const void* q, const void* k, const void* v, void* out, int64_t out_sm, int64_t out_sk,
+                                   int64_t stride_t, int64_t stride_h, int sq, int sk, const int32_t* sk_dev, int H, int Hkv, int D,
+                                   float scale, int nsplit, float* ws, int64_t ws_floats, uint32_t* tickets, void* stream);
 int tf_attn_prefill_gqa(const void* q, const void* k, const void* v, void* out, int64_t stride_t, int64_t stride_h,
                         int sq, int sk, int H, int Hkv, int D, float scale, int nsplit, float* ws, int64_t ws_floats,
                         void* stream);

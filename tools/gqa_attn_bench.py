@@ -9,11 +9,15 @@ At sq rows x sk keys, D = 128, five launches are timed with HIP events, alternat
         q-tile costs by itself
   (v)   tf_attn_decode_gqa_wide_act, where g * sq <= 64: all g heads of a KV head as one stack — (i)'s bytes
         where (ii) launches g / gs columns per KV head and reads g / gs times as much
+  (vi)  tf_attn_decode_gqa_wide128_act, where 64 < g * sq <= 128: the same, two key streams per workgroup
+        (checked against (iii) at the decode bounds: its bits are its own)
 One JSON line per form: median / min / max microseconds per launch over the rounds, the K/V bytes the launch must read
 (2 * heads * sk * D * 2) and bytes / median time.  (ii) is also checked against (iii) on the repeated K/V (same bits).
 
     python tools/gqa_attn_bench.py --out profiles/gqa_decode_attention.jsonl
     python tools/gqa_attn_bench.py --shape 28/4/7 --shape 64/8/7 --shape 28/4/9 --out profiles/gqa_wide_decode_attention.jsonl
+    python tools/gqa_attn_bench.py --shape 32/8/17 --shape 28/4/17 --shape 64/8/17 --shape 128/8/7 \
+        --out profiles/gqa_wide128_decode_attention.jsonl
 """
 import argparse
 import json
@@ -68,10 +72,15 @@ def bench(args, H, Hkv, sq):
     wide = g * sq <= ops.GQA_WIDE_MAX_ROWS
     if wide:
         forms["gqa_wide"] = (lambda: ops.attn_decode_gqa_wide(q, k, v, sk, scale), H, Hkv, ops._pick_nsplit(Hkv, sk))
+    wide128 = ops.GQA_WIDE_MAX_ROWS < g * sq <= ops.GQA_WIDE128_MAX_ROWS
+    if wide128:
+        forms["gqa_wide128"] = (lambda: ops.attn_decode_gqa_wide128(q, k, v, sk, scale), H, Hkv, ops._pick_nsplit(Hkv, sk))
     n = ops._pick_nsplit(Hkv * sub, sk)
     wide_same = wide and torch.equal(ops.attn_decode_gqa_wide(q, k, v, sk, scale, nsplit=n),
                                      ops.attn_decode(q, ke, ve, sk, scale, nsplit=n))
     same = torch.equal(ops.attn_decode_gqa(q, k, v, sk, scale, nsplit=n), ops.attn_decode(q, ke, ve, sk, scale, nsplit=n))
+    wide128_close = wide128 and torch.allclose(ops.attn_decode_gqa_wide128(q, k, v, sk, scale).float(),
+                                               ops.attn_decode(q, ke, ve, sk, scale).float(), atol=2e-5, rtol=1.5e-3)
     for fn, *_ in forms.values():                                      # warm-up: code objects, allocator, tickets
         for _ in range(10):
             fn()
@@ -93,13 +102,16 @@ def bench(args, H, Hkv, sq):
             kv_bytes = 2 * kv_heads * sk * D * 2
             row = dict(what="decode attention, HIP events around batches of launches (includes the launch gaps)", form=name,
                        rows=sq, keys=sk, D=D, query_heads=heads, kv_heads=kv_heads, nsplit=nsplit,
-                       stacked_rows={"gqa_wide": g * sq, "gqa": gs * sq, "mha_kv_heads_stacked_row_count": gs * sq}.get(name, sq),
+                       stacked_rows={"gqa_wide": g * sq, "gqa_wide128": g * sq, "gqa": gs * sq,
+                                     "mha_kv_heads_stacked_row_count": gs * sq}.get(name, sq),
                        kv_passes=sub if name == "gqa" else 1,
                        launches_per_batch=args.launches, rounds=args.rounds,
                        us_median=round(us, 2), us_min=round(min(times[name]), 2), us_max=round(max(times[name]), 2),
                        kv_bytes=kv_bytes, tb_per_s=round(kv_bytes / us * 1e-6, 3),
                        gqa_bits_equal_mha_on_repeated_kv=same,
-                       gqa_wide_bits_equal_mha_on_repeated_kv=wide_same if wide else None, device=torch.cuda.get_device_name(0))
+                       gqa_wide_bits_equal_mha_on_repeated_kv=wide_same if wide else None,
+                       gqa_wide128_within_decode_bounds_of_mha=wide128_close if wide128 else None,
+                       device=torch.cuda.get_device_name(0))
             line = json.dumps(row)
             print(line, flush=True)
             f.write(line + "\n")

@@ -851,6 +851,11 @@ __device__ __forceinline__ void wide_read_frags(const h16* buf, int li, int g, h
         vf[c] = *reinterpret_cast<const half8*>(buf + (16 + li) * LDR + 32 * c + 8 * g);
     }
 }
+// the one-launch split merge both wide kernels end in (defined behind the first of them)
+template <int D, int NTHR>
+__device__ __forceinline__ void gqa_wide_ticket_merge(const float* ws_o, const float* ws_m, const float* ws_l, unsigned* tickets,
+                                                      h16* __restrict__ out, int64_t osm, int64_t osk, int hkv, int nsplit, int QR,
+                                                      int rows, int sq, int g_kv, int tid);
 
 template <int D>
 __global__ __launch_bounds__(512) void attn_split_gqa_wide_kernel(
@@ -1000,9 +1005,16 @@ __global__ __launch_bounds__(512) void attn_split_gqa_wide_kernel(
         __syncthreads();
     }
     if (tickets == nullptr) return;                    // two-launch form: attn_combine_gqa_kernel merges the splits
+    gqa_wide_ticket_merge<D, 64 * NWW>(ws_o, ws_m, ws_l, tickets, out, osm, osk, hkv, nsplit, QR, rows, sq, g_kv, tid);
+}
 
-    // ---- fused merge (<= FUSED_MERGE_MAX_SPLITS splits): attn_split_body's — own stores drained, ticket, and the last
-    // workgroup of the KV head folds the partials with each split its own chain of attn_combine_kernel ----
+// ---- fused merge of the wide grouped-query kernels (<= FUSED_MERGE_MAX_SPLITS splits): attn_split_body's — own stores drained,
+// ticket, and the last workgroup of the KV head folds the partials with each split its own chain of attn_combine_kernel.
+// NTHR threads; rows = g_kv * sq stacked rows of QR = 16 * ceil(rows / 16) workspace rows ----
+template <int D, int NTHR>
+__device__ __forceinline__ void gqa_wide_ticket_merge(const float* ws_o, const float* ws_m, const float* ws_l, unsigned* tickets,
+                                                      h16* __restrict__ out, int64_t osm, int64_t osk, int hkv, int nsplit, int QR,
+                                                      int rows, int sq, int g_kv, int tid) {
     __shared__ int s_last;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -1011,7 +1023,7 @@ __global__ __launch_bounds__(512) void attn_split_gqa_wide_kernel(
     __syncthreads();
     if (!s_last) return;
     const int64_t hbase = (int64_t)hkv * nsplit * QR;
-    for (int e = tid; e < rows * (D / 4); e += 64 * NWW) {
+    for (int e = tid; e < rows * (D / 4); e += NTHR) {
         const int r = e / (D / 4), d4 = e - r * (D / 4);
         float pm[FUSED_MERGE_MAX_SPLITS], pl[FUSED_MERGE_MAX_SPLITS];
         f32x4 px[FUSED_MERGE_MAX_SPLITS];
@@ -1050,6 +1062,193 @@ __global__ __launch_bounds__(512) void attn_split_gqa_wide_kernel(
         *reinterpret_cast<half4*>(out + (int64_t)(r % sq) * osm + (int64_t)((hq * D + 4 * d4) >> 3) * osk + ((4 * d4) & 7)) = o4;
     }
     if (tid == 0) __hip_atomic_store(&tickets[hkv], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // left zero for the next launch
+}
+
+// ---- the 128-ROW grouped-query form (tf_attn_decode_gqa_wide128_act) --------------------------------------
+// The wide form above for R = g * sq <= 128 stacked rows (same row order), still one workgroup column per KV head and one HBM
+// read of K / V per KV head.  Eight q-tiles at two per wave are all eight waves of a CU, so the workgroup is cut the other way:
+//   * 8 waves = 2 key STREAMS x 4 ROW QUARTERS.  Stream s takes the key tiles t_begin + s, + 2, ...; row quarter r owns q-tiles
+//     2 r and 2 r + 1, carries AttnState<D, 2> and runs attn_tile<D, 2, ..., GQA> on every tile of its stream.
+//   * the four waves of a stream share ONE HBM read of each tile, a QUARTER each: row quarter 0 fetches K rows 0-7 of the tile,
+//     1 K rows 8-15, 2 V rows 0-7, 3 V rows 8-15 (full 256-byte rows, four per load instruction), into the stream's staging
+//     buffer [K | V][16][D + 8]; all four then read their fragments from it.
+//   * the staging buffer is double-buffered and a wave holds its quarter of FOUR more tiles in registers: while tile i is
+//     multiplied, tile i + 1 goes registers -> LDS and tiles i + 2 .. i + 5 are in flight — 8 KiB per wave at D = 128, 64 KiB
+//     per CU, what two resident workgroups of the two-q-tile multi-head form keep.  One workgroup barrier
+//     per tile; every load unconditional (past the last tile it re-reads it); the steps run in groups of four, one per register
+//     set, and EVERY wave runs the same whole number of groups — a step without a tile skips the arithmetic, not the barrier.
+// With two streams where tf_attn_decode_act has four, a row's partial sums are grouped differently: the output is NOT
+// bit-identical to the multi-head kernel's (the 64-row form above is).  It is deterministic, the one- and two-launch merges
+// are bit-identical to each other for the same nsplit, and it stays within the decode bounds of the fp64 reference.
+// ws layout: attn_split_body's with Hkv columns and QR = 16 * ceil(R / 16) rows; q-tiles past QR compute on zero queries and
+// store nothing.
+template <int D>
+__device__ __forceinline__ void wide128_load_quarter(const h16* __restrict__ base, int64_t stride_t, int tile, int half, int sk,
+                                                     int lane, half8 (&r)[D / 64]) {
+    constexpr int LPR = D / 8, RPI = 64 / LPR;
+    const int rl = lane / LPR, q = lane % LPR;
+#pragma unroll
+    for (int j = 0; j < D / 64; ++j) {
+        int key = tile * 16 + 8 * half + RPI * j + rl;
+        key = key < sk ? key : sk - 1;                 // clamp: masked below, but must stay in-bounds
+        r[j] = load_half8_stream(base + (int64_t)key * stride_t + 8 * q);
+    }
+}
+// dst: this wave's [8][D + 8] quarter of a staging buffer
+template <int D>
+__device__ __forceinline__ void wide128_store_quarter(const half8 (&r)[D / 64], h16* dst, int lane) {
+    constexpr int LPR = D / 8, RPI = 64 / LPR, LDR = D + 8;
+    const int rl = lane / LPR, q = lane % LPR;
+#pragma unroll
+    for (int j = 0; j < D / 64; ++j) *reinterpret_cast<half8*>(dst + (RPI * j + rl) * LDR + 8 * q) = r[j];
+}
+
+template <int D>
+__global__ __launch_bounds__(512) void attn_split_gqa_wide128_kernel(
+    const h16* __restrict__ q, const h16* __restrict__ k, const h16* __restrict__ v, const int32_t* __restrict__ sk_dev,
+    int sq, int sk_host, int H, int nsplit, int stride_t, int stride_h, float scale,      // <- 14 dwords preloaded into SGPRs
+    float* __restrict__ ws, unsigned* __restrict__ tickets, h16* __restrict__ out, int64_t osm, int64_t osk, int g_kv) {
+    constexpr int NC = D / 32, NT = D / 16, QT = 2, LDR = D + 8;
+    constexpr int NS = 2, NQ = 4, NWW = NS * NQ;       // key streams, row quarters, waves
+    constexpr int RING = 4;                            // register sets: tiles in flight per wave beyond the two in LDS
+    const int split = blockIdx.x, hkv = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int strm = wave & (NS - 1), rq = wave / NS;
+    const int li = lane & 15, g = lane >> 4;
+    int sk = sk_dev ? *sk_dev : sk_host;
+    if (sk > sk_host) sk = sk_host;
+    if (sk < 1) sk = 1;
+
+    const int ntiles = (sk + 15) >> 4;
+    const int tps = (ntiles + nsplit - 1) / nsplit;
+    const int t_begin = split * tps;
+    const int t_end = min(ntiles, t_begin + tps);
+
+    const int rows = g_kv * sq;                        // stacked rows of this KV head
+    const int QR = ((rows + 15) >> 4) << 4;            // rows of the workspace layout
+    AttnState<D, QT> st;
+    int qtok[QT];                                      // token index of this lane's row per q-tile (padding rows: a valid one)
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) {
+        const int row = (QT * rq + qt) * 16 + li;
+        qtok[qt] = row % sq;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            half8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+            st.qf[qt][c] = (row < rows) ? load_half8(q + ((int64_t)qtok[qt] * H + hkv * g_kv + row / sq) * D + 32 * c + 8 * g) : z;
+        }
+#pragma unroll
+        for (int t = 0; t < NT; ++t) st.acc[qt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        st.m[qt] = NEG_BIG;
+        st.l[qt] = 0.f;
+    }
+    half8 sel0, sel1;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        sel0[e] = (8 * g + e == li) ? (h16)1.0f : (h16)0.0f;
+        sel1[e] = (8 * g + e == 16 + li) ? (h16)1.0f : (h16)0.0f;
+    }
+
+    // One block of LDS: the two streams' staging buffers, then — behind a barrier — the merge of the waves' partial results
+    constexpr size_t BUF = (size_t)2 * 16 * LDR;       // halves of one staging buffer [K | V][16][LDR]
+    constexpr size_t STAGE_BYTES = (size_t)NS * 2 * BUF * sizeof(h16);
+    constexpr size_t MERGE_BYTES = sizeof(float) * ((size_t)NWW * 16 * (D + 1) + 2 * NWW * 16);
+    __shared__ __attribute__((aligned(16))) unsigned char sm_raw[MERGE_BYTES > STAGE_BYTES ? MERGE_BYTES : STAGE_BYTES];
+    h16* buf0 = reinterpret_cast<h16*>(sm_raw) + (size_t)strm * 2 * BUF;
+    h16* buf1 = buf0 + BUF;
+    // the quarter tile this wave fetches: K (row quarters 0, 1) or V (2, 3), rows 0-7 or 8-15, and where it goes in a buffer
+    const h16* src = (rq < 2 ? k : v) + (int64_t)hkv * stride_h;
+    const int half = rq & 1;
+    const int mine = ((rq >> 1) * 16 + 8 * half) * LDR;
+
+    const int n_it = t_begin < t_end ? (t_end - t_begin + NS - 1) / NS : 0;    // steps with a tile in SOME stream
+    if (n_it > 0) {
+        const int tl = t_end - 1;
+        int t = t_begin + strm;
+        half8 r0[D / 64], r1[D / 64], r2[D / 64], r3[D / 64];
+        wide128_load_quarter<D>(src, stride_t, min(t, tl), half, sk, lane, r0);
+        wide128_store_quarter<D>(r0, buf0 + mine, lane);
+        wide128_load_quarter<D>(src, stride_t, min(t + NS, tl), half, sk, lane, r0);
+        wide128_load_quarter<D>(src, stride_t, min(t + 2 * NS, tl), half, sk, lane, r1);
+        wide128_load_quarter<D>(src, stride_t, min(t + 3 * NS, tl), half, sk, lane, r2);
+        wide128_load_quarter<D>(src, stride_t, min(t + 4 * NS, tl), half, sk, lane, r3);
+        __syncthreads();
+        // one step: fragments of tile T from CUR; the quarter in R (tile T + NS) to NXT; R refilled with tile T + (RING + 1) NS;
+        // the tile's arithmetic (the "fully visible" shortcut keeps the TOKEN count, as in attn_split_body's GQA form); barrier
+#define WIDE128_STEP(CUR, NXT, R, T)                                                                                         \
+    do {                                                                                                                     \
+        half8 kf_[NC], vf_[NC];                                                                                              \
+        wide_read_frags<D>(CUR, li, g, kf_, vf_);                                                                            \
+        wide128_store_quarter<D>(R, NXT + mine, lane);                                                                       \
+        wide128_load_quarter<D>(src, stride_t, min((T) + (RING + 1) * NS, tl), half, sk, lane, R);                           \
+        if ((T) < t_end) {                                                                                                   \
+            if ((T) * 16 + 15 <= sk - sq) attn_tile<D, QT, false, false>(st, kf_, vf_, sel0, sel1, (T), sk, sq, scale, li, g); \
+            else attn_tile<D, QT, false, true, true>(st, kf_, vf_, sel0, sel1, (T), sk, sq, scale, li, g, 0,               \
+                                                     TreeMask{nullptr, 0, 0, 0}, qtok);                                     \
+        }                                                                                                                    \
+        __syncthreads();                                                                                                     \
+    } while (0)
+        // (whole groups only: a remainder loop would add edges on which an older register set is the youngest load, and the
+        // waitcnt pass then drains the ring in front of every LDS store — DESIGN section 35)
+        for (int it = 0; it < n_it; it += RING) {
+            WIDE128_STEP(buf0, buf1, r0, t);
+            WIDE128_STEP(buf1, buf0, r1, t + NS);
+            WIDE128_STEP(buf0, buf1, r2, t + 2 * NS);
+            WIDE128_STEP(buf1, buf0, r3, t + 3 * NS);
+            t += RING * NS;
+        }
+#undef WIDE128_STEP
+    }
+
+    // ---- merge the two streams of each row quarter through LDS, one q-tile per row quarter at a time, in stream order ----
+    float (*sm_o)[16][D + 1] = reinterpret_cast<float (*)[16][D + 1]>(sm_raw);
+    float (*sm_m)[16] = reinterpret_cast<float (*)[16]>(sm_raw + sizeof(float) * (size_t)NWW * 16 * (D + 1));
+    float (*sm_l)[16] = sm_m + NWW;
+    const int Hkv = gridDim.y;
+    float* ws_o = ws;
+    float* ws_m = ws + (int64_t)Hkv * nsplit * QR * D;
+    float* ws_l = ws_m + (int64_t)Hkv * nsplit * QR;
+    const int64_t pbase = ((int64_t)hkv * nsplit + split) * QR;
+    const int w0 = rq * NS;                            // the two waves of this thread's row quarter
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) {
+        float lsum = st.l[qt];
+        lsum += __shfl_xor(lsum, 16, 64);
+        lsum += __shfl_xor(lsum, 32, 64);
+#pragma unroll
+        for (int tt = 0; tt < NT; ++tt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sm_o[wave][li][16 * tt + 4 * g + r] = st.acc[qt][tt][r];
+        if (g == 0) {
+            sm_m[wave][li] = st.m[qt];
+            sm_l[wave][li] = lsum;
+        }
+        __syncthreads();
+        const int row0 = (QT * rq + qt) * 16;          // first stacked row of this q-tile (rows past QR have no workspace)
+        for (int e = tid & (64 * NS - 1); e < 16 * D && row0 < QR; e += 64 * NS) {
+            const int qq = e / D, d = e - qq * D;
+            const float mm = fmaxf(sm_m[w0][qq], sm_m[w0 + 1][qq]);
+            const float wa = __expf(sm_m[w0][qq] - mm), wb = __expf(sm_m[w0 + 1][qq] - mm);
+            const float o = sm_o[w0][qq][d] * wa + sm_o[w0 + 1][qq][d] * wb;
+            const float lw = sm_l[w0][qq] * wa + sm_l[w0 + 1][qq] * wb;
+            if (tickets == nullptr) {
+                ws_o[(pbase + row0 + qq) * D + d] = o;
+                if (d == 0) {
+                    ws_m[pbase + row0 + qq] = mm;
+                    ws_l[pbase + row0 + qq] = lw;
+                }
+            } else {                                   // one-launch form: write-through (sc1) stores
+                st_agent(&ws_o[(pbase + row0 + qq) * D + d], o);
+                if (d == 0) {
+                    st_agent(&ws_m[pbase + row0 + qq], mm);
+                    st_agent(&ws_l[pbase + row0 + qq], lw);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (tickets == nullptr) return;                    // two-launch form: attn_combine_gqa_kernel merges the splits
+    gqa_wide_ticket_merge<D, 64 * NWW>(ws_o, ws_m, ws_l, tickets, out, osm, osk, hkv, nsplit, QR, rows, sq, g_kv, tid);
 }
 
 // The FP8-KV form (tf_attn_decode_fp8_act): k / v are code pointers, ke / ve the exponent bytes.  The one-q-tile form keeps the
@@ -2466,6 +2665,46 @@ extern "C" int tf_attn_decode_gqa_wide_act(const void* q, const void* k, const v
                                          tickets, st);
     return launch_attn_gqa_wide<64>(q, k, v, out, out_sm, out_sk, stride_t, stride_h, sq, sk, sk_dev, H, Hkv, scale, nsplit, ws,
                                     tickets, st);
+}
+
+// tf_attn_decode_gqa_wide_act for R = g * sq <= 128 stacked rows: grid (nsplit, Hkv), K / V read once per
+// KV head.  Workspace, split count, tickets and the merge forms as above.  Deterministic, the two merge forms bit-identical
+// to each other for the same nsplit — but NOT to tf_attn_decode_act's bits: a workgroup runs two key streams, not four.
+template <int D>
+static int launch_attn_gqa_wide128(const void* q, const void* k, const void* v, void* out, int64_t osm, int64_t osk, int64_t stride_t,
+                                   int64_t stride_h, int sq, int sk, const int32_t* sk_dev, int H, int Hkv, float scale, int nsplit,
+                                   float* ws, unsigned* tickets, hipStream_t st) {
+    const int g = H / Hkv, R = g * sq;
+    dim3 grid(nsplit, Hkv), block(512);
+    if (tickets && nsplit > FUSED_MERGE_MAX_SPLITS) tickets = nullptr;      // many splits: the parallel merge kernel
+    hipLaunchKernelGGL((attn_split_gqa_wide128_kernel<D>), grid, block, 0, st, (const h16*)q, (const h16*)k, (const h16*)v, sk_dev,
+                       sq, sk, H, nsplit, (int)stride_t, (int)stride_h, scale, ws, tickets, (h16*)out, osm, osk, g);
+    TF_LAUNCH_CHECK();
+    if (tickets) return TF_OK;
+    hipLaunchKernelGGL((attn_combine_gqa_kernel<D>), dim3(Hkv, R), dim3(D, COMBINE_GROUPS), 0, st, (const float*)ws, (h16*)out,
+                       sq, Hkv, nsplit, ((R + 15) / 16) * 16, osm, osk, g);
+    TF_LAUNCH_CHECK();
+    return TF_OK;
+}
+
+extern "C" int tf_attn_decode_gqa_wide128_act(const void* q, const void* k, const void* v, void* out, int64_t out_sm,
+                                              int64_t out_sk, int64_t stride_t, int64_t stride_h, int sq, int sk,
+                                              const int32_t* sk_dev, int H, int Hkv, int D, float scale, int nsplit, float* ws,
+                                              int64_t ws_floats, uint32_t* tickets, void* stream) {
+    if (!q || !k || !v || !out || !ws) return TF_EINVAL;
+    if (sq < 1 || sq > 32 || sk < 1 || H < 1 || Hkv < 1 || (H % Hkv) || nsplit < 1 || nsplit > COMBINE_MAX_SPLITS) return TF_EINVAL;
+    if ((int64_t)(H / Hkv) * sq > 128) return TF_EINVAL;              // eight q-tiles
+    if (D != 128 && D != 64) return TF_EINVAL;
+    if ((stride_t % 8) || (stride_h % 8)) return TF_EINVAL;          // 16-B loads
+    if (stride_t > 0x7fffffff || stride_h > 0x7fffffff) return TF_EINVAL;   // (the kernel takes the two strides as 32-bit arguments)
+    if (out_sm < 8 || out_sk < 8 || (out_sm % 4) || (out_sk % 4)) return TF_EINVAL;   // 8-byte output stores
+    if (ws_floats < tf_attn_decode_ws_floats(Hkv, (H / Hkv) * sq, D, nsplit)) return TF_ENOSPC;
+    hipStream_t st = (hipStream_t)stream;
+    if (D == 128)
+        return launch_attn_gqa_wide128<128>(q, k, v, out, out_sm, out_sk, stride_t, stride_h, sq, sk, sk_dev, H, Hkv, scale, nsplit,
+                                            ws, tickets, st);
+    return launch_attn_gqa_wide128<64>(q, k, v, out, out_sm, out_sk, stride_t, stride_h, sq, sk, sk_dev, H, Hkv, scale, nsplit, ws,
+                                       tickets, st);
 }
 
 // FP8 KV cache (include/triforce_hip.h): the same split / merge as tf_attn_decode_act (bit-identical to it on the

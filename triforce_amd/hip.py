@@ -164,6 +164,7 @@ SIGNATURES["tf_draft_persist_reset"] = (_i32, [_vp, _vp, _i32])
 SIGNATURES["tf_attn_decode_gqa_act"] = (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _i32, _i32, _i32,
                                                _f32, _i32, _vp, _i64, _vp, _vp])
 SIGNATURES["tf_attn_decode_gqa_wide_act"] = SIGNATURES["tf_attn_decode_gqa_act"]       # 
+SIGNATURES["tf_attn_decode_gqa_wide128_act"] = SIGNATURES["tf_attn_decode_gqa_act"]    # 
 SIGNATURES["tf_attn_prefill_gqa"] = (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp,
                                             _i64, _vp])
 SIGNATURES["tf_skinny_qkv_rope_gqa_act"] = (_i32, [_vp, _vp, _i64, _i64, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,

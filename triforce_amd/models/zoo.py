@@ -34,6 +34,12 @@ CONFIGS = {
                      num_key_value_heads=2, max_position_embeddings=131072, rms_norm_eps=1e-6,
                      rope_scaling=dict(type="yarn", factor=16.0, original_max_position_embeddings=256),
                      _name_or_path="tiny-yarn-gqa-target"),
+    # "tiny-gqa" at 16 query heads over 1 KV head (hidden 2048): a 7-row verify stacks 112 rows, an 8-row one 128 — the shapes of
+    # the 128-row grouped-query decode attention (TRIFORCE_GQA_WIDE=128)
+    "tiny-gqa16": dict(hidden_size=2048, intermediate_size=768, num_hidden_layers=2, num_attention_heads=16,
+                       num_key_value_heads=1, max_position_embeddings=131072, rms_norm_eps=1e-6,
+                       rope_scaling=dict(type="yarn", factor=16.0, original_max_position_embeddings=256),
+                       _name_or_path="tiny-yarn-gqa16-target"),
     # the tiny targets with attention bias: "tiny" with q/k/v/o biases (the Llama-architecture form),
     # "tiny-gqa" with q/k/v biases only (the Qwen2 form: model_type qwen2, no o_proj bias)
     "tiny-bias": dict(hidden_size=256, intermediate_size=768, num_hidden_layers=2, num_attention_heads=2,

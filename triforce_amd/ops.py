@@ -114,6 +114,15 @@ def gqa_wide_applies(g, sq):
     return gqa_stack(g, sq)[1] > 1 and g * sq <= GQA_WIDE_MAX_ROWS
 
 
+GQA_WIDE128_MAX_ROWS = 128       # stacked rows of tf_attn_decode_gqa_wide128_act: eight q-tiles
+
+
+def gqa_wide128_applies(g, sq):
+    """Launch rule of the 128-row grouped-query decode attention (tf_attn_decode_gqa_wide128_act): the
+    shapes past the wide kernel's 64 rows that still fit 128, where the stacked kernel streams K / V g / gs times."""
+    return GQA_WIDE_MAX_ROWS < g * sq <= GQA_WIDE128_MAX_ROWS and gqa_stack(g, sq)[1] > 1
+
+
 def group_mean_query(q, Hkv):
     """q̄ of the grouped-query retrieval selection: q (H, D) fp16 -> (Hkv, D) fp16, the fp32 mean over
     the H / Hkv query heads of each KV head rounded to fp16.  H == Hkv: q itself, bit for bit."""
@@ -839,9 +848,13 @@ def attn_decode(q, k_layer, v_layer, sk, scale, sk_dev=None, nsplit=None, packed
     sq, H, D = q.shape
     if k_layer.shape[0] != H:                          # fewer KV heads than query heads: the grouped-query kernels
         Hkv = k_layer.shape[0]
-        wide = GQA_WIDE and Hkv >= 1 and H % Hkv == 0 and sq <= SKINNY_MAX_ROWS and gqa_wide_applies(H // Hkv, sq)
-        return (attn_decode_gqa_wide if wide else attn_decode_gqa)(q, k_layer, v_layer, sk, scale, sk_dev=sk_dev, nsplit=nsplit,
-                                                                   packed=packed)
+        fits = GQA_WIDE and Hkv >= 1 and H % Hkv == 0 and sq <= SKINNY_MAX_ROWS
+        fn = attn_decode_gqa
+        if fits and gqa_wide_applies(H // Hkv, sq):
+            fn = attn_decode_gqa_wide
+        elif fits and GQA_WIDE_ROWS == GQA_WIDE128_MAX_ROWS and gqa_wide128_applies(H // Hkv, sq):
+            fn = attn_decode_gqa_wide128
+        return fn(q, k_layer, v_layer, sk, scale, sk_dev=sk_dev, nsplit=nsplit, packed=packed)
     assert q.dtype == _HALF and q.is_contiguous()
     st, sh = _kv(k_layer)
     assert _kv(v_layer) == (st, sh)
@@ -902,20 +915,42 @@ def attn_decode_gqa(q, k_layer, v_layer, sk, scale, sk_dev=None, nsplit=None, pa
     return out
 
 
-# TRIFORCE_GQA_WIDE=0: attn_decode never takes the wide kernel (every launch is tf_attn_decode_gqa_act's)
-GQA_WIDE = _os.environ.get("TRIFORCE_GQA_WIDE", "1") != "0"
+def _gqa_wide_knob(env):
+    """TRIFORCE_GQA_WIDE of ``env`` -> (GQA_WIDE, GQA_WIDE_ROWS).  ``0``: attn_decode never takes a wide kernel (every launch is
+    tf_attn_decode_gqa_act's); ``1`` (the default): the 64-row kernel where gqa_wide_applies; ``128``: also the 128-row kernel
+    where gqa_wide128_applies (opt-in: its bits are not the multi-head kernel's)."""
+    value = env.get("TRIFORCE_GQA_WIDE", "1")
+    if value not in ("0", "1", "128"):
+        raise ValueError(f"TRIFORCE_GQA_WIDE={value!r}: expected 0, 1 or 128")
+    return value != "0", GQA_WIDE128_MAX_ROWS if value == "128" else GQA_WIDE_MAX_ROWS
+
+
+GQA_WIDE, GQA_WIDE_ROWS = _gqa_wide_knob(_os.environ)
 
 
 def attn_decode_gqa_wide(q, k_layer, v_layer, sk, scale, sk_dev=None, nsplit=None, packed=False, fused_merge=None, out=None):
     """attn_decode_gqa with ALL g = H / Hkv query heads of a KV head stacked into one problem of g * sq <= 64 rows
     (tf_attn_decode_gqa_wide_act): one workgroup column per KV head, K / V streamed once per KV head.
     Arguments as attn_decode_gqa; the default split count is that of Hkv columns."""
+    return _attn_decode_gqa_stack("tf_attn_decode_gqa_wide_act", GQA_WIDE_MAX_ROWS, q, k_layer, v_layer, sk, scale, sk_dev, nsplit,
+                                  packed, fused_merge, out)
+
+
+def attn_decode_gqa_wide128(q, k_layer, v_layer, sk, scale, sk_dev=None, nsplit=None, packed=False, fused_merge=None, out=None):
+    """attn_decode_gqa_wide for g * sq <= 128 stacked rows (tf_attn_decode_gqa_wide128_act).  Deterministic,
+    one- and two-launch merges bit-identical to each other; NOT bit-identical to the multi-head kernel on the repeated K / V."""
+    return _attn_decode_gqa_stack("tf_attn_decode_gqa_wide128_act", GQA_WIDE128_MAX_ROWS, q, k_layer, v_layer, sk, scale, sk_dev,
+                                  nsplit, packed, fused_merge, out)
+
+
+def _attn_decode_gqa_stack(entry, max_rows, q, k_layer, v_layer, sk, scale, sk_dev, nsplit, packed, fused_merge, out):
+    """The two whole-group kernels' launch: one workgroup column per KV head, workspace and tickets sized here."""
     _dev(q, k_layer, v_layer, sk_dev)
     sq, H, D = q.shape
     Hkv = k_layer.shape[0]
     assert q.dtype == _HALF and q.is_contiguous() and v_layer.shape[0] == Hkv
-    if Hkv < 1 or H % Hkv or sq > SKINNY_MAX_ROWS or (H // Hkv) * sq > GQA_WIDE_MAX_ROWS:
-        raise hip.TriforceHipError(f"attn_decode_gqa_wide: {H} query heads over {Hkv} KV heads, {sq} rows")
+    if Hkv < 1 or H % Hkv or sq > SKINNY_MAX_ROWS or (H // Hkv) * sq > max_rows:
+        raise hip.TriforceHipError(f"{entry}: {H} query heads over {Hkv} KV heads, {sq} rows")
     st, sh = _kv(k_layer)
     assert _kv(v_layer) == (st, sh)
     if nsplit is None:
@@ -928,9 +963,8 @@ def attn_decode_gqa_wide(q, k_layer, v_layer, sk, scale, sk_dev=None, nsplit=Non
     stream = _stream()
     fused = ATTN_FUSED_MERGE if fused_merge is None else fused_merge
     tickets = _ticket_row(q.device, stream.value or 0) if fused and Hkv <= _TICKET_WORDS else None
-    hip.check(hip.lib().tf_attn_decode_gqa_wide_act(_ptr(q), _ptr(k_layer), _ptr(v_layer), op, osm, osk, st, sh, sq, int(sk),
-                                                    _ptr(sk_dev), H, Hkv, D, float(scale), nsplit, _ptr(ws), ws.numel(),
-                                                    _ptr(tickets), stream), "tf_attn_decode_gqa_wide_act")
+    hip.check(getattr(hip.lib(), entry)(_ptr(q), _ptr(k_layer), _ptr(v_layer), op, osm, osk, st, sh, sq, int(sk), _ptr(sk_dev), H,
+                                        Hkv, D, float(scale), nsplit, _ptr(ws), ws.numel(), _ptr(tickets), stream), entry)
     return out
 
 
